@@ -12,9 +12,13 @@ launches N ranks of itself through `python -m torch.distributed.run` BEFORE impo
 relays their output and exits with their code.  Ranks exchange nothing on the data path; the timing barrier and
 the MAX-over-ranks reduction go through gloo on CPU tensors (no RCCL on this path).
 
-After the timed region the output of the last step is checked (`"verified"` in the line): sampled streams
-against the oracle (RMS <= 1e-4), duplicate-input streams bit-identical, and an exact checksum of the whole
-batch that must be the same after every step.
+A plain run sets up, warms up, times `--steps` steps and prints the line (`value`, `ms_per_step`, ...).  `--full` adds
+what takes work beyond that: HIP events inside the timed region and a copy-ceiling run for `"roofline"`, the CPU
+baseline, and the check of the last step's output (`"verified"`): sampled streams against the oracle (RMS <= 1e-4),
+duplicate-input streams bit-identical, and an exact checksum of the whole batch that must be the same after every step.
+
+`--dump-outputs DIR` writes the last timed step's output as .npy files (see dump_outputs()); the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -32,6 +36,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_BYTES = 60_000_000  # --dump-outputs writes at most this much over all ranks (headers aside)
 
 
 CONFIGS = {  # BASELINE.json configs[1..3]; configs[4] is cfg2 at 128 streams per GPU x 8 GPUs (the default workload)
@@ -230,6 +235,30 @@ def verify_outputs(torch, batch, d_in, out, dup_pairs, sample_streams, kw, flush
     return res
 
 
+def dump_outputs(torch, out, path, rank=0, world=1, budget=DUMP_BYTES):
+    """Write `out` (this rank's output batch, float32 [streams, channels, frames]) under `path` as .npy, within
+    budget / world bytes: `output.npy`, the whole batch, where it fits; otherwise `output_stream0.npy` (stream 0, cut
+    to half the budget) and `output_sample.npy`, every stream at the same frame positions, drawn with a fixed seed
+    and listed in `output_sample_frames.npy` (float64).  With world > 1 every name carries `_rank<r>`."""
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    budget //= world
+
+    def save(name, a):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+
+    if out.numel() * 4 <= budget:
+        save("output", out.cpu().numpy())
+        return
+    S, C, F = out.shape
+    first = out[0, :, :min(F, budget // 2 // (4 * C))]
+    save("output_stream0", first.cpu().numpy())
+    k = min(F, (budget - first.numel() * 4) // (4 * S * C + 8))
+    frames = np.sort(np.random.default_rng(0).choice(F, size=k, replace=False))
+    save("output_sample", out[:, :, torch.from_numpy(frames).to(out.device)].cpu().numpy())
+    save("output_sample_frames", frames.astype(np.float64))
+
+
 def host_io_leg(torch, E, args, kw, flush, device_index, d_in, d_out_ref, steps=2):
     """The same job with the staging included (never `value`): inputs and outputs in page-locked host memory, groups
     of streams triple-buffered through the GPU (H2D / kernels / D2H overlapped), float32 and int16 on the wire."""
@@ -268,6 +297,118 @@ def host_io_leg(torch, E, args, kw, flush, device_index, d_in, d_out_ref, steps=
     return res
 
 
+def roofline(torch, E, args, batch, info, ktimes, G, dt, device, arith):
+    """The line's "roofline" (--full): the dominant kernel's algorithmic bytes over its event-timed duration, beside
+    the HBM spec, a device copy measured here and the counter-derived figures of profiles/*.json for this code."""
+    per = args.streams // G
+    slices_per_step_gpu = batch.slices * 2 * args.streams
+    slices_per_launch = batch.slices * 2 * per / batch.launches  # one launch = one chunk of one group
+    N, H, s, h = info["fftsize"], info["fftsize"] // 2 + 1, info["hop_out_nominal"], info["hop_in"]
+    rs = 1 if info["resample"] else 0  # without resampling SURVEY 8(d) drops the s + h terms
+    # Algorithmic bytes per slice of each pipeline stage (DESIGN.md section 4); they sum to SURVEY 8(d)'s
+    # B_slice = 4*(3N+7H+2s+h).  The phase stage runs as two kernels (match + seq) in phase-locked
+    # mode and as one (prop) in coremode 0; a stage's time is the sum over its kernels.  The fused
+    # synthesis + overlap-add kernel carries the bytes of both of its stages.
+    stages = {
+        "analysis": (4 * (N + 2 * H), ["pv_analyze_kernel"]),
+        "phase": (4 * (3 * H), ["pv_match_kernel", "pv_seq_kernel", "pv_prop_kernel"]),
+        "synthesis": (4 * (2 * H + N), ["pv_synth_kernel"]),
+        "ola_resample": (4 * (N + s + rs * (s + h)), ["pv_ola_kernel"]),
+    }
+    assert sum(b for b, _ in stages.values()) == info["bytes_per_slice"]
+    per_kernel, per_stage = {}, {}
+    for k, (ms, n) in ktimes.items():
+        if n:
+            per_kernel[k] = {"avg_ms": round(ms / n, 4), "samples": int(n)}
+    if "pv_synth_ola_kernel" in per_kernel:
+        # fused path: synthesis + overlap-add in one kernel (frames never leave LDS); where the configuration
+        # resamples, pv_ola_kernel is the resampling kernel that follows it.  The fused kernel carries the
+        # synthesis stage's bytes and the overlap-add's N + s; the resampler its s + h.
+        stages["synthesis"] = (4 * (2 * H + N) + 4 * (N + s), ["pv_synth_ola_kernel"])
+        if rs:
+            stages["ola_resample"] = (4 * (s + h), ["pv_ola_kernel"])
+        else:
+            del stages["ola_resample"]
+    # Counter-derived HBM bytes per launch (profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of
+    # this workload, tools/profile_round.sh): quoted only when they were measured on THIS code (source hash), this
+    # geometry and this arithmetic setting -- a stale profile silently describing other kernels is worse than null.
+    traffic_db, traffic_note = {}, None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    src_hash = kernel_source_hash()
+    if os.path.exists(tpath):
+        tj = json.load(open(tpath))
+        if tj.get("source_sha16") == src_hash and tj.get("arithmetic", "exact") == arith:
+            traffic_db = tj.get("bytes_per_launch", {})
+        else:
+            traffic_note = (f"profiles/traffic.json was measured on other code or settings (its source hash "
+                            f"{tj.get('source_sha16')}, arithmetic {tj.get('arithmetic')}; this run {src_hash}, {arith})")
+    for name, (nbytes, ks) in stages.items():
+        live = [k for k in ks if k in per_kernel]
+        if not live:
+            continue
+        avg_ms = sum(per_kernel[k]["avg_ms"] for k in live)
+        per_stage[name] = {"kernels": live, "avg_ms": round(avg_ms, 4), "bytes_per_slice": nbytes,
+                           "GBps": round(nbytes * slices_per_launch / (avg_ms * 1e-3) / 1e9, 1)}
+    # With the pipelined batch path the phase stage's sequential kernel runs on a second HIP stream beside the others:
+    # its duration is not on the critical path, so the roofline entry is the longest kernel of the MAIN stream
+    # (a stage's GB/s is still computed over all of its kernels' durations).
+    overlapped = [k for k in ("pv_seq_kernel", "pv_prop_kernel") if batch.pipelined and k in per_kernel]
+    main = {k: v for k, v in per_kernel.items() if k not in overlapped}
+    if not main:  # --sample-every 0 (counter passes: no events in the stream): nothing per kernel to report
+        main = {"none": {"avg_ms": float("nan")}}
+        stages["none"] = (0, ["none"])
+        per_stage["none"] = {"GBps": 0.0}
+    dom = max(main, key=lambda k: main[k]["avg_ms"])
+    dom_stage = next(n for n, (_, ks) in stages.items() if dom in ks and n in per_stage)
+    dom_bytes = stages[dom_stage][0]
+    achieved = round(dom_bytes * slices_per_launch / (main[dom]["avg_ms"] * 1e-3) / 1e9, 1) \
+        if dom_stage != "phase" or not overlapped else per_stage[dom_stage]["GBps"]
+    if dom == "none":
+        achieved = 0.0
+    std_geometry = G == 1 and args.streams == 128 and args.config == "cfg2" and args.seconds == 60
+    traffic = traffic_db.get(dom) if std_geometry else None
+    hbm_real = None
+    if traffic:
+        hbm_real = traffic / (main[dom]["avg_ms"] * 1e-3) / 1e9  # the kernel's real HBM rate (counter bytes / live duration)
+    # Beside the contract's HBM figure: how close the same kernel runs to the chip's vector-instruction issue rate,
+    # which is what bounds this path (DESIGN.md section 3).  Instruction counts per slice and the mean issue cost
+    # of the kernel's instruction mix are a profile's (profiles/valu.json: PMC pass + tools/pk_probe.hip's price
+    # list), the duration is this run's.
+    valu = None
+    vpath = os.path.join(ROOT, "profiles", "valu.json")
+    if os.path.exists(vpath) and std_geometry and args.coremode == 1:
+        vdb = json.load(open(vpath))
+        vk = vdb.get("kernels", {}).get(dom) if (vdb.get("source_sha16") == src_hash and
+                                                 vdb.get("arithmetic", "exact") == arith) else None
+        if vk:
+            rate = vk["valu_insts_per_slice"] * slices_per_launch * vk["mean_cost"] / main[dom]["avg_ms"] / 1e6
+            valu = {"kernel": dom, "valu_insts_per_slice": vk["valu_insts_per_slice"], "mean_issue_cost": vk["mean_cost"],
+                    "weighted_M_insts_per_ms": round(rate, 1), "chip_peak_M_per_ms": vdb["chip_peak_M_per_ms"],
+                    "frac": round(rate / vdb["chip_peak_M_per_ms"], 3),
+                    "source": "profiles/valu.json (SQ_INSTS_VALU pass, static mix priced by tools/pk_probe.hip)"}
+    pipeline_gbps = info["bytes_per_slice"] * slices_per_step_gpu * args.steps / dt / 1e9
+    copy_gbps = copy_ceiling_gbps(torch, device)
+    # What binds the dominant kernel.  `achieved` is the contract's figure (algorithmic bytes / duration); it says how
+    # fast the work is done, not that HBM is busy.  When the kernel moves fewer real bytes than that (hbm_real_frac
+    # below frac) and runs closer to the chip's vector-issue rate than to its real HBM rate, the bound is named so.
+    bound = "hbm"
+    if valu is not None and hbm_real is not None and valu["frac"] > hbm_real / HBM_PEAK_GBPS:
+        bound = "valu_issue"
+    return {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+            "hbm_real_GBps": round(hbm_real, 1) if hbm_real else None,
+            "hbm_real_frac": round(hbm_real / HBM_PEAK_GBPS, 4) if hbm_real else None,
+            "traffic_note": traffic_note, "source_sha16": src_hash,
+            "copy_ceiling_GBps": round(copy_gbps, 1), "frac_of_copy_ceiling": round(achieved / copy_gbps, 4),
+            "stage": dom_stage, "slices_per_launch": round(slices_per_launch, 1),
+            "pipeline_GBps": round(pipeline_gbps, 1),
+            "pipeline_frac": round(pipeline_gbps / HBM_PEAK_GBPS, 4),
+            "overlapped_on_second_stream": overlapped,
+            "valu_issue": valu,
+            "per_stage": per_stage,
+            "per_kernel": per_kernel}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -278,20 +419,26 @@ def main():
     ap.add_argument("--coremode", type=int, default=1)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS),
                     help="BASELINE config to run (default cfg2 = configs[1], the one the metric is quoted on)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-timing check of the output")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beyond the headline figure: roofline (HIP events in the timed region, "
+                         "copy ceiling), CPU baseline, post-timing check of the output")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output under DIR as .npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the post-timing check of the output")
     ap.add_argument("--dist-backend", default="gloo",
                     help="gloo (default: barrier + MAX reduce on CPU tensors, no RCCL on this path) or nccl")
     ap.add_argument("--force-device", type=int, default=-1, help="use this device on every rank (rehearsals only)")
     ap.add_argument("--groups", type=int, default=1,
                     help="split the streams into this many batches run concurrently on separate HIP streams")
-    ap.add_argument("--sample-every", type=int, default=8, help="instrument every n-th chunk with HIP events")
+    ap.add_argument("--sample-every", type=int, default=8, help="with --full: instrument every n-th chunk with HIP events")
     ap.add_argument("--host-io", action="store_true",
                     help="also measure the host-staged path (page-locked host in / out, H2D / kernels / D2H overlapped)")
     ap.add_argument("--host-io-group", type=int, default=32, help="streams per staged group of the --host-io leg")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))  # nothing below has run: no torch import, no HIP call in this process
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -352,25 +499,31 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
+    verify = args.full and not args.no_verify
     warm_sum = None
-    if not args.no_verify and args.warmup > 0:
+    if verify and args.warmup > 0:
         warm_sum = signals.batch_checksum(torch, out_all)[0]
         barrier()
     # HIP events around the kernels of every 8th chunk of group 0, inside the timed region (an event record
-    # costs stream time: instrumenting every launch slows the run by ~10 %, every 8th by ~1 %)
-    batch.enable_timing(args.sample_every)
+    # costs stream time: instrumenting every launch slows the run by ~10 %, every 8th by ~1 %); --full only
+    if args.full:
+        batch.enable_timing(args.sample_every)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     dt = time.perf_counter() - t0
-    ktimes = batch.kernel_times()
-    batch.enable_timing(0)
+    ktimes = None
+    if args.full:
+        ktimes = batch.kernel_times()
+        batch.enable_timing(0)
     dt = max_over_ranks(dt, dist, red_device)
     ranks_reporting = int(round(sum_over_ranks(1.0, dist, red_device)))
+    if args.dump_outputs:
+        dump_outputs(torch, out_all, args.dump_outputs, rank, world)
 
     verified = None
-    if not args.no_verify:
+    if verify:
         digest, _ = signals.batch_checksum(torch, out_all)
         picks = sorted({0, S - 1} | ({S // 2, S // 3} if rank == 0 and S >= 8 else set()))
         verified = verify_outputs(torch, batch, d_in, out_all, dup_pairs, picks, kw, cfg_flush)
@@ -394,100 +547,7 @@ def main():
         ch_samples = total_streams * frames * 2 * args.steps
         value = ch_samples / dt / 1e6
         xrt_gpu = args.streams * args.seconds * args.steps / dt
-        slices_per_step_gpu = batch.slices * 2 * args.streams
-        slices_per_launch = batch.slices * 2 * per / batch.launches  # one launch = one chunk of one group
-        N, H, s, h = info["fftsize"], info["fftsize"] // 2 + 1, info["hop_out_nominal"], info["hop_in"]
-        rs = 1 if info["resample"] else 0  # without resampling SURVEY 8(d) drops the s + h terms
-        # Algorithmic bytes per slice of each pipeline stage; they sum to SURVEY 8(d)'s
-        # B_slice = 4*(3N+7H+2s+h).  The phase stage runs as two kernels (match + seq) in phase-locked
-        # mode and as one (prop) in coremode 0; a stage's time is the sum over its kernels.  The fused
-        # synthesis + overlap-add kernel carries the bytes of both of its stages.
-        stages = {
-            "analysis": (4 * (N + 2 * H), ["pv_analyze_kernel"]),
-            "phase": (4 * (3 * H), ["pv_match_kernel", "pv_seq_kernel", "pv_prop_kernel"]),
-            "synthesis": (4 * (2 * H + N), ["pv_synth_kernel"]),
-            "ola_resample": (4 * (N + s + rs * (s + h)), ["pv_ola_kernel"]),
-        }
-        assert sum(b for b, _ in stages.values()) == info["bytes_per_slice"]
-        per_kernel, per_stage = {}, {}
-        for k, (ms, n) in ktimes.items():
-            if n:
-                per_kernel[k] = {"avg_ms": round(ms / n, 4), "samples": int(n)}
-        if "pv_synth_ola_kernel" in per_kernel:
-            # fused path: synthesis + overlap-add in one kernel (frames never leave LDS); where the configuration
-            # resamples, pv_ola_kernel is the resampling kernel that follows it.  The fused kernel carries the
-            # synthesis stage's bytes and the overlap-add's N + s; the resampler its s + h.
-            stages["synthesis"] = (4 * (2 * H + N) + 4 * (N + s), ["pv_synth_ola_kernel"])
-            if rs:
-                stages["ola_resample"] = (4 * (s + h), ["pv_ola_kernel"])
-            else:
-                del stages["ola_resample"]
-        # Counter-derived HBM bytes per launch (profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of
-        # this workload, tools/profile_round.sh): quoted only when they were measured on THIS code (source hash), this
-        # geometry and this arithmetic setting -- a stale profile silently describing other kernels is worse than null.
-        traffic_db, traffic_note = {}, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        src_hash = kernel_source_hash()
         arith = "exact" if E.get_arithmetic() == E.ARITH_EXACT else "fast"
-        if os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            if tj.get("source_sha16") == src_hash and tj.get("arithmetic", "exact") == arith:
-                traffic_db = tj.get("bytes_per_launch", {})
-            else:
-                traffic_note = (f"profiles/traffic.json was measured on other code or settings (its source hash "
-                                f"{tj.get('source_sha16')}, arithmetic {tj.get('arithmetic')}; this run {src_hash}, {arith})")
-        for name, (nbytes, ks) in stages.items():
-            live = [k for k in ks if k in per_kernel]
-            if not live:
-                continue
-            avg_ms = sum(per_kernel[k]["avg_ms"] for k in live)
-            per_stage[name] = {"kernels": live, "avg_ms": round(avg_ms, 4), "bytes_per_slice": nbytes,
-                               "GBps": round(nbytes * slices_per_launch / (avg_ms * 1e-3) / 1e9, 1)}
-        # With the pipelined batch path the phase stage's sequential kernel runs on a second HIP stream beside the others:
-        # its duration is not on the critical path, so the roofline entry is the longest kernel of the MAIN stream
-        # (a stage's GB/s is still computed over all of its kernels' durations).
-        overlapped = [k for k in ("pv_seq_kernel", "pv_prop_kernel") if batch.pipelined and k in per_kernel]
-        main = {k: v for k, v in per_kernel.items() if k not in overlapped}
-        if not main:  # --sample-every 0 (counter passes: no events in the stream): nothing per kernel to report
-            main = {"none": {"avg_ms": float("nan")}}
-            stages["none"] = (0, ["none"])
-            per_stage["none"] = {"GBps": 0.0}
-        dom = max(main, key=lambda k: main[k]["avg_ms"])
-        dom_stage = next(n for n, (_, ks) in stages.items() if dom in ks and n in per_stage)
-        dom_bytes = stages[dom_stage][0]
-        achieved = round(dom_bytes * slices_per_launch / (main[dom]["avg_ms"] * 1e-3) / 1e9, 1) \
-            if dom_stage != "phase" or not overlapped else per_stage[dom_stage]["GBps"]
-        if dom == "none":
-            achieved = 0.0
-        std_geometry = G == 1 and args.streams == 128 and args.config == "cfg2" and args.seconds == 60
-        traffic = traffic_db.get(dom) if std_geometry else None
-        hbm_real = None
-        if traffic:
-            hbm_real = traffic / (main[dom]["avg_ms"] * 1e-3) / 1e9  # the kernel's real HBM rate (counter bytes / live duration)
-        # Beside the contract's HBM figure: how close the same kernel runs to the chip's vector-instruction issue rate,
-        # which is what bounds this path.  Instruction counts per slice and the mean issue cost
-        # of the kernel's instruction mix are a profile's (profiles/valu.json: PMC pass + tools/pk_probe.hip's price
-        # list), the duration is this run's.
-        valu = None
-        vpath = os.path.join(ROOT, "profiles", "valu.json")
-        if os.path.exists(vpath) and std_geometry and args.coremode == 1:
-            vdb = json.load(open(vpath))
-            vk = vdb.get("kernels", {}).get(dom) if (vdb.get("source_sha16") == src_hash and
-                                                     vdb.get("arithmetic", "exact") == arith) else None
-            if vk:
-                rate = vk["valu_insts_per_slice"] * slices_per_launch * vk["mean_cost"] / main[dom]["avg_ms"] / 1e6
-                valu = {"kernel": dom, "valu_insts_per_slice": vk["valu_insts_per_slice"], "mean_issue_cost": vk["mean_cost"],
-                        "weighted_M_insts_per_ms": round(rate, 1), "chip_peak_M_per_ms": vdb["chip_peak_M_per_ms"],
-                        "frac": round(rate / vdb["chip_peak_M_per_ms"], 3),
-                        "source": "profiles/valu.json (SQ_INSTS_VALU pass, static mix priced by tools/pk_probe.hip)"}
-        pipeline_gbps = info["bytes_per_slice"] * slices_per_step_gpu * args.steps / dt / 1e9
-        copy_gbps = copy_ceiling_gbps(torch, device)
-        # What binds the dominant kernel.  `achieved` is the contract's figure (algorithmic bytes / duration); it says how
-        # fast the work is done, not that HBM is busy.  When the kernel moves fewer real bytes than that (hbm_real_frac
-        # below frac) and runs closer to the chip's vector-issue rate than to its real HBM rate, the bound is named so.
-        bound = "hbm"
-        if valu is not None and hbm_real is not None and valu["frac"] > hbm_real / HBM_PEAK_GBPS:
-            bound = "valu_issue"
         line = {
             "metric": "Msamples/s (48 kHz stereo) phase-vocoder pitch-shift; x real-time per GPU",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": ranks_reporting, "steps": args.steps,
@@ -499,29 +559,18 @@ def main():
                                               "propagation bit-exact)" if arith == "fast" else
                                               " (reference operation order everywhere)"),
                        "streams_per_gpu": args.streams, "seconds_per_stream": args.seconds, "channels": 2,
-                       "block": 480, "hop_in": h, "slices_per_channel": int(batch.slices),
+                       "block": 480, "hop_in": info["hop_in"], "slices_per_channel": int(batch.slices),
                        "concurrent_stream_groups": G, "launches_per_step": int(batch.launches) * G,
                        "parallelism": f"stream-sharded x{world}, no collective",
                        "rank_sync": f"{args.dist_backend} (barrier + MAX of the wall time only)" if world > 1 else "none"},
-            "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "hbm_real_GBps": round(hbm_real, 1) if hbm_real else None,
-                         "hbm_real_frac": round(hbm_real / HBM_PEAK_GBPS, 4) if hbm_real else None,
-                         "traffic_note": traffic_note, "source_sha16": src_hash,
-                         "copy_ceiling_GBps": round(copy_gbps, 1), "frac_of_copy_ceiling": round(achieved / copy_gbps, 4),
-                         "stage": dom_stage, "slices_per_launch": round(slices_per_launch, 1),
-                         "pipeline_GBps": round(pipeline_gbps, 1),
-                         "pipeline_frac": round(pipeline_gbps / HBM_PEAK_GBPS, 4),
-                         "overlapped_on_second_stream": overlapped,
-                         "valu_issue": valu,
-                         "per_stage": per_stage,
-                         "per_kernel": per_kernel},
         }
+        if args.full:
+            line["roofline"] = roofline(torch, E, args, batch, info, ktimes, G, dt, device, arith)
         if verified is not None:
             line["verified"] = verified
         if host_io is not None:
             line["host_io"] = host_io
-        if world == 1 and not args.no_cpu_baseline and args.config == "cfg2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "cfg2":
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -70,7 +70,7 @@ def test_bench_gpus_2_really_runs_two_ranks():
     """`python bench.py --gpus 2` (the form the driver uses, no torchrun around it) must launch two ranks and say
     so; rehearsed on one card with --force-device 0.  Rank sync is gloo on CPU tensors: no RCCL on this path."""
     r = _bench(["--gpus", "2", "--force-device", "0", "--steps", "1", "--warmup", "1", "--streams", "16",
-                "--seconds", "10", "--no-cpu-baseline"])
+                "--seconds", "10", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2
@@ -81,13 +81,68 @@ def test_bench_gpus_2_really_runs_two_ranks():
 
 @pytest.mark.gpu
 def test_bench_line_carries_its_own_verification():
-    r = _bench(["--steps", "1", "--warmup", "1", "--streams", "8", "--seconds", "10", "--no-cpu-baseline"])
+    r = _bench(["--steps", "1", "--warmup", "1", "--streams", "8", "--seconds", "10", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     v = line["verified"]
     assert line["n_gpus"] == 1 and v["ok"] and v["duplicate_streams_bit_identical"]
     assert v["same_checksum_after_warmup_and_timed_steps"] is True
     assert len(v["batch_checksum_sha256"]) == 64 and len(v["streams_checked"]) >= 2
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line only, and --dump-outputs writes what its last timed step
+    computed: the same bits as the batch engine gives on bench.py's seeded input (8 streams: the whole batch fits)."""
+    import torch
+
+    from audiomod_amd import engine as E
+    from audiomod_amd import signals
+
+    r = _bench(["--steps", "2", "--warmup", "1", "--streams", "8", "--seconds", "10", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "Msamples/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["value"] > 0
+    assert not {"roofline", "verified", "cpu_baseline"} & set(line)
+    assert os.listdir(tmp_path) == ["output.npy"]
+    got = np.load(tmp_path / "output.npy")
+    S, F = 8, 10 * 48000
+    d_in = signals.synthetic_batch(torch, S, F, torch.device("cuda", 0), duplicates=[(S - 1, 0), (S // 2, 1)])
+    b = E.Batch(S, F, channels=2, block=480, flush=True, mode="normal_pitchshift", semitones=4.0, coremode=1,
+                fftsize=2048)
+    want = b.run(d_in)
+    torch.cuda.synchronize()
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.cpu().numpy().view(np.uint32))
+    b.close()
+
+
+def test_dump_outputs_samples_a_large_batch_within_its_budget(tmp_path):
+    """Above the budget: stream 0 (cut to half the budget) and every stream at the same seeded frame positions."""
+    import torch
+
+    import bench
+
+    out = torch.randn(16, 2, 50000)
+    budget = 1 << 20
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(torch, out, str(d), budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["output_sample.npy", "output_sample_frames.npy", "output_stream0.npy"]
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= budget
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))  # same positions every run
+    first = np.load(tmp_path / "a" / "output_stream0.npy")
+    assert np.array_equal(first, out[0, :, :first.shape[1]].numpy())
+    frames = np.load(tmp_path / "a" / "output_sample_frames.npy")
+    assert frames.dtype == np.float64 and np.all(np.diff(frames) > 0)
+    sample = np.load(tmp_path / "a" / "output_sample.npy")
+    assert np.array_equal(sample, out[:, :, frames.astype(np.int64)].numpy())
+
+
+def test_bench_refuses_zero_steps():
+    r = _bench(["--steps", "0"], timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():

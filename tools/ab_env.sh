@@ -6,7 +6,7 @@ O=gpurun_out/r02/ab_$T.txt
 : > $O
 for E in "$@"; do
   if [ "$E" = "-" ]; then EV=""; else EV="$E"; fi
-  env $EV timeout -k 10 200 python bench.py --no-cpu-baseline > /tmp/ab.json 2>/tmp/ab.err
+  env $EV timeout -k 10 200 python bench.py --full --no-cpu-baseline > /tmp/ab.json 2>/tmp/ab.err
   python - "$E" >> $O <<'PY'
 import json,sys
 try:

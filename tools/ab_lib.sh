@@ -9,7 +9,7 @@ for E in "$@"; do
   L=$1; shift
   EV="$*"
   if [ "$L" != "-" ]; then EV="$EV AUDIOMOD_PV_LIB=$PWD/audiomod_amd/lib/diag/$L/libaudiomod_pv.so"; fi
-  env $EV timeout -k 10 200 python bench.py --no-cpu-baseline > /tmp/ab.json 2>/tmp/ab.err
+  env $EV timeout -k 10 200 python bench.py --full --no-cpu-baseline > /tmp/ab.json 2>/tmp/ab.err
   python - "$E" >> $O <<'PY'
 import json,sys
 try:

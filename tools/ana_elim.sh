@@ -6,7 +6,7 @@ out=${1:-gpurun_out/ana_elim.txt}
 L=$PWD/audiomod_amd/lib/diag
 for v in base ana1 ana2 ana3 ana4 ana8 ana16 ana28 ana31; do
   if [ $v = base ]; then lib=$PWD/audiomod_amd/lib/libaudiomod_pv.so; else lib=$L/$v/libaudiomod_pv.so; fi
-  line=$(AUDIOMOD_PV_LIB=$lib AUDIOMOD_PV_PIPELINE=0 timeout -k 10 200 python bench.py --no-verify --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1)
+  line=$(AUDIOMOD_PV_LIB=$lib AUDIOMOD_PV_PIPELINE=0 timeout -k 10 200 python bench.py --full --no-verify --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1)
   python - "$v" "$line" >> $out <<'PY'
 import json, sys
 try:

@@ -5,7 +5,7 @@ shift
 : > $out
 for cfg in "cfg2 --coremode 1" "cfg2 --coremode 0" "cfg2 --coremode 2" "cfg3 --coremode 1" "cfg4_formant+7 --coremode 1" "cfg4_formant-7 --coremode 1" "cfg4_gender+7 --coremode 1" "cfg4_gender-7 --coremode 1"; do
   set -- $cfg
-  line=$(env "${EXTRA_ENV[@]}" timeout -k 10 400 python bench.py --config $1 $2 $3 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1)
+  line=$(env "${EXTRA_ENV[@]}" timeout -k 10 400 python bench.py --full --config $1 $2 $3 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1)
   python - "$cfg" "$line" >> $out <<'PY'
 import json, sys
 try:

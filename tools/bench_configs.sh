@@ -1,7 +1,7 @@
 #!/bin/bash
 # all BASELINE configs through bench.py (numbers for DESIGN.md); run on the GPU box
 for C in cfg2 cfg3 cfg4_formant+7 cfg4_formant-7 cfg4_gender+7 cfg4_gender-7; do
-  timeout -k 10 300 python bench.py --config $C --no-cpu-baseline 2>/dev/null > /tmp/b.json
+  timeout -k 10 300 python bench.py --full --config $C --no-cpu-baseline 2>/dev/null > /tmp/b.json
   python - <<PY
 import json
 d=json.load(open("/tmp/b.json"))
@@ -9,7 +9,7 @@ print("$C", d["value"], "Msamples/s", d["ms_per_step"], "ms/step", d["x_realtime
 PY
 done
 for CM in 0 2; do
-  timeout -k 10 300 python bench.py --coremode $CM --no-cpu-baseline 2>/dev/null > /tmp/b.json
+  timeout -k 10 300 python bench.py --full --coremode $CM --no-cpu-baseline 2>/dev/null > /tmp/b.json
   python - <<PY
 import json
 d=json.load(open("/tmp/b.json"))

@@ -5,7 +5,7 @@ out=${1:-gpurun_out/r02/diag}
 mkdir -p $out
 run() { # tag, env...
     tag=$1; shift
-    env "$@" AUDIOMOD_PV_PIPELINE=0 timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-verify --sample-every 4 > $out/$tag.json 2> $out/$tag.err || echo "$tag failed"
+    env "$@" AUDIOMOD_PV_PIPELINE=0 timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-verify --sample-every 4 > $out/$tag.json 2> $out/$tag.err || echo "$tag failed"
 }
 run base
 run nores AUDIOMOD_PV_CHAIN_DIAG=1

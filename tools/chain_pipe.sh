@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/r02/pipe}
 shift
 mkdir -p $out
-run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-verify --sample-every 4 $EXTRA > $out/$tag.json 2> $out/$tag.err || echo "$tag failed"; }
+run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-verify --sample-every 4 $EXTRA > $out/$tag.json 2> $out/$tag.err || echo "$tag failed"; }
 EXTRA="$*"
 run w16
 run w14 AUDIOMOD_PV_CHAIN_WAVES=14

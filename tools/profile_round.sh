@@ -10,9 +10,9 @@ set -e
 T=${1:-vX}
 export TMPDIR=/tmp
 O=$PWD/gpurun_out
-timeout -k 10 400 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout -k 10 400 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
 echo "bench done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/${T}_prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline > $O/${T}_bench_under_rocprof.json 2> $O/${T}_prof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/${T}_prof -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline > $O/${T}_bench_under_rocprof.json 2> $O/${T}_prof.err
 cp $(ls $O/${T}_prof/*/run_kernel_stats.csv $O/${T}_prof/run_kernel_stats.csv 2>/dev/null | head -1) $O/${T}_kernel_stats.csv
 rm -rf $O/${T}_prof
 echo "stats done"

@@ -2,7 +2,7 @@
 # the narrow rotation-chain kernel (three peaks per lane) beside the fused kernel: schedules and wave counts
 out=${1:-gpurun_out/r02/narrow}
 mkdir -p $out
-run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --sample-every 4 > $out/$tag.json 2> $out/$tag.err || echo "$tag failed"; }
+run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --sample-every 4 > $out/$tag.json 2> $out/$tag.err || echo "$tag failed"; }
 run base
 run narrow3 AUDIOMOD_PV_SEQ_NARROW=1
 run narrow2_w14 AUDIOMOD_PV_SEQ_NARROW=1 AUDIOMOD_PV_THREE_STAGE=0 AUDIOMOD_PV_CHAIN_WAVES=14

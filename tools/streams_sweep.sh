@@ -4,7 +4,7 @@ out=${1:-gpurun_out/streams_sweep.txt}; shift
 S=${@:-20 64 97 100 128 130 160 192}
 : > $out
 for s in $S; do
-  line=$(timeout -k 10 300 python bench.py --streams $s --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1)
+  line=$(timeout -k 10 300 python bench.py --full --streams $s --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1)
   python - "$s" "$line" >> $out <<'PY'
 import json, sys
 try:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/sweep_chunk.sh "32 64 128" [extra bench args]
 for T in $1; do
-  AUDIOMOD_PV_CHUNK_SLICES=$T timeout -k 10 200 python bench.py --no-cpu-baseline ${@:2} 2>/dev/null > /tmp/b_$T.json
+  AUDIOMOD_PV_CHUNK_SLICES=$T timeout -k 10 200 python bench.py --full --no-cpu-baseline ${@:2} 2>/dev/null > /tmp/b_$T.json
   python - <<PY
 import json
 d=json.load(open("/tmp/b_$T.json"))

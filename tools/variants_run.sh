@@ -14,8 +14,8 @@ except Exception as e:
 PY
 }
 export O
-timeout -k 10 200 python bench.py --no-cpu-baseline > /tmp/b_default.json 2>/tmp/b_default.err; show default /tmp/b_default.json
+timeout -k 10 200 python bench.py --full --no-cpu-baseline > /tmp/b_default.json 2>/tmp/b_default.err; show default /tmp/b_default.json
 for N in "$@"; do
-  timeout -k 10 200 python tools/diag_run.py $N --no-cpu-baseline > /tmp/b_$N.json 2>/tmp/b_$N.err; show $N /tmp/b_$N.json
+  timeout -k 10 200 python tools/diag_run.py $N --full --no-cpu-baseline > /tmp/b_$N.json 2>/tmp/b_$N.err; show $N /tmp/b_$N.json
 done
 cat $O
