@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <chrono>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -1278,6 +1279,45 @@ struct pv_engine {
     }
 };
 
+// ------------------------------------------------------------------------------------------
+// stream pool: many live streams, one launch sequence per call for all of them (audiomod_pv.h "Stream pool").
+// One Core of `capacity` streams; slot i owns rows [i*C, (i+1)*C) of every per-row buffer and the accumulator
+// images [i][2][C][AR].  Every slot keeps its own planner, overlap-add plan and accumulator half, so that it computes
+// exactly what a pv_engine fed the same calls computes.
+// ------------------------------------------------------------------------------------------
+struct pv_pool {
+    Core core;
+    int poisoned = 0;
+    std::string poison_reason;
+    int cap = 0, ring = 0;
+    hipStream_t stream = nullptr;
+    struct Slot {
+        bool open = false;
+        std::unique_ptr<Planner> planner;
+        std::unique_ptr<ChainBuilder> chain;
+        int64_t fed = 0, uploaded = 0, slices = 0;
+        int acc_half = 0; // which accumulator half the slot's next launch reads
+        std::vector<std::vector<float>> outq; // per channel FIFO
+        size_t outq_head = 0;
+    };
+    std::vector<Slot> slots;
+    DevBuf<float> d_in, d_stage; // device input rings [capacity * C][ring]; a call's packed new samples
+    PinBuf<float> h_stage;
+    const float *stage_src = nullptr; // what the ingest kernel reads: d_stage (or h_stage mapped, PV_POOL_MAPPED_INGEST)
+    double last_host_us = 0, last_wait_us = 0; // the last pv_pool_feed: host work up to the wait, and the wait
+    DevBuf<char> d_desc;
+    PinBuf<char> h_desc;
+    PinBuf<float> h_out; // output arena, mapped into the device's address space (out_dev)
+    float *out_dev = nullptr;
+    PinBuf<uint32_t> h_flag;
+    uint32_t *flag_dev = nullptr;
+    uint32_t flag_seq = 0;
+    bool wait_value = false; // the device supports stream memory operations: spin on a flag instead of synchronising
+    ~pv_pool() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 extern "C" {
 
 const char *pv_strerror(int s) {
@@ -2083,6 +2123,592 @@ int32_t pv_retrieve(pv_engine *e, float *const *out, int32_t n) {
         e->outq_head = 0;
     }
     return got;
+}
+
+// ---------------------------------------------------------------- stream pool
+// why a configuration is outside the pool's scope (nullptr: inside).  Each excluded mode needs side data that the
+// per-row kernels share across rows: the vocoders' carrier planes, WHISPER's process-wide random stream, CONSTANT's
+// channel-0 overrun flag; the cepstral mode and the sizes without a wave-per-frame transform have no per-slot kernels.
+static const char *pool_scope(const pv_config &cfg, const Derived &d) {
+    switch (cfg.mode) {
+    case PV_MODE_NORMAL_SHIFT: case PV_MODE_GENDER_CHANGE: case PV_MODE_FORMANT_PRESERVE: case PV_MODE_NORMAL_STRETCH:
+    case PV_MODE_ROBOTIC: break;
+    case PV_MODE_VOCODER_ROSENBERG: case PV_MODE_VOCODER_CHORD:
+        return "stream pool: the vocoder modes are not pooled (their carrier planes are shared by all rows)";
+    case PV_MODE_WHISPER: return "stream pool: WHISPER is not pooled (its phases come from one process-wide random stream)";
+    case PV_MODE_CONSTANT: return "stream pool: CONSTANT is not pooled (its overrun flag is per stream)";
+    case PV_MODE_FORMANT_CEPSTRAL: return "stream pool: FORMANT_CEPSTRAL is not pooled";
+    default: return "stream pool: unknown mode";
+    }
+    const int nc = d.fft.nc;
+    if (!(nc == 256 || nc == 512 || nc == 1024 || nc == 2048))
+        return "stream pool: fftsize 512 ... 4096 only (the sizes of the fused synthesis + overlap-add kernel)";
+    return nullptr;
+}
+
+static bool pool_slot_ok(const pv_pool *p, int32_t slot) {
+    return p && slot >= 0 && slot < p->cap && p->slots[(size_t)slot].open;
+}
+
+static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true);
+
+int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool **out) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!cfg || !out) return PV_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (capacity < 1) {
+        g_last_error = "stream pool: capacity must be at least 1";
+        return PV_ERR_INVALID_ARG;
+    }
+    // the configuration is checked before any device call (as Core::init does)
+    {
+        Derived d;
+        const int st = derive(*cfg, d);
+        if (st != PV_OK) return st;
+        if ((int64_t)capacity * cfg->channels > 65535) {
+            g_last_error = "stream pool: capacity x channels above 65535 (the kernels put the rows on grid.y)";
+            return PV_ERR_INVALID_ARG;
+        }
+        if (const char *why = pool_scope(*cfg, d)) {
+            g_last_error = why;
+            return PV_ERR_UNSUPPORTED;
+        }
+    }
+    std::unique_ptr<pv_pool> p(new pv_pool());
+    Core &c = p->core;
+    c.chain_required = true;
+    c.fast_arith = g_arith == PV_ARITH_FAST;
+    int st = c.init(*cfg, device, capacity, kStreamChunk);
+    if (st != PV_OK) return st;
+    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
+    if (!c.use_chain || !c.wave_fft()) {
+        g_last_error = "stream pool: needs the fused synthesis + overlap-add path (AUDIOMOD_PV_FUSED=0 turns it off)";
+        return PV_ERR_UNSUPPORTED;
+    }
+    if (!bypass && c.d.cfg.coremode == 1 && !pool_phase_supported(c.d.hs, c.PKP)) {
+        g_last_error = "stream pool: the phase-locked kernel of this configuration does not fit one workgroup";
+        return PV_ERR_UNSUPPORTED;
+    }
+    p->cap = capacity;
+    {
+        PoolLaunch probe{};
+        if ((st = pool_launch_group(p.get(), probe, false)) != PV_OK) return st; // (launches nothing)
+    }
+    HIPC(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    p->ring = next_pow2_i(3 * c.d.N + kStreamChunk * c.d.hop + 16); // (as pv_create)
+    if ((st = p->d_in.alloc((size_t)c.rows * p->ring)) != PV_OK) return st;
+    HIPC(hipMemset(p->d_in.p, 0, p->d_in.n * sizeof(float)));
+    if ((st = p->h_flag.alloc(16)) != PV_OK) return st;
+    p->h_flag.p[0] = 0;
+    {
+        int v = 0;
+        p->wait_value = hipDeviceGetAttribute(&v, hipDeviceAttributeCanUseStreamWaitValue, device) == hipSuccess && v != 0;
+    }
+    if (p->wait_value) {
+        void *fp = nullptr;
+        HIPC(hipHostGetDevicePointer(&fp, p->h_flag.p, 0));
+        p->flag_dev = static_cast<uint32_t *>(fp);
+    }
+    p->slots.resize((size_t)capacity);
+    *out = p.release();
+    return PV_OK;
+}
+
+void pv_pool_destroy(pv_pool *p) { delete p; }
+
+int pv_pool_last_timing(const pv_pool *p, double *host_us, double *wait_us) {
+    if (!p || !host_us || !wait_us) return PV_ERR_INVALID_ARG;
+    *host_us = p->last_host_us;
+    *wait_us = p->last_wait_us;
+    return PV_OK;
+}
+
+int32_t pv_pool_capacity(const pv_pool *p) { return p ? p->cap : -1; }
+
+int pv_pool_open(pv_pool *p, int32_t *slot) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p || !slot) return PV_ERR_INVALID_ARG;
+    if (p->poisoned) {
+        g_last_error = "pool unusable after an earlier failure: " + p->poison_reason;
+        return p->poisoned;
+    }
+    int32_t s = 0;
+    while (s < p->cap && p->slots[(size_t)s].open) ++s;
+    if (s == p->cap) {
+        g_last_error = "stream pool: all " + std::to_string(p->cap) + " slots are open";
+        return PV_ERR_INVALID_ARG;
+    }
+    Core &c = p->core;
+    HIPC(hipSetDevice(c.device));
+    // a fresh stream: what pv_create and Core::reset_state zero, for the slot's rows only (stream-ordered before its
+    // first launch)
+    const size_t r0 = (size_t)s * c.C, nr = (size_t)c.C;
+    auto clear = [&](void *base, size_t elem, size_t pitch) -> int {
+        if (!base) return PV_OK;
+        HIPC(hipMemsetAsync(static_cast<char *>(base) + r0 * pitch * elem, 0, nr * pitch * elem, p->stream));
+        return PV_OK;
+    };
+    int st = PV_OK;
+    if (st == PV_OK) st = clear(p->d_in.p, sizeof(float), (size_t)p->ring);
+    if (st == PV_OK) st = clear(c.st_pp.p, sizeof(float), (size_t)c.d.hs);
+    if (st == PV_OK) st = clear(c.st_po.p, sizeof(float), (size_t)c.d.hs);
+    if (st == PV_OK) st = clear(c.st_kind.p, sizeof(int32_t), 1);
+    if (st == PV_OK) st = clear(c.st_acc.p, sizeof(float), 2 * (size_t)c.chain_AR); // [slot][2][C][AR]
+    if (st != PV_OK) {
+        p->poisoned = st;
+        p->poison_reason = g_last_error;
+        return st;
+    }
+    pv_pool::Slot &sl = p->slots[(size_t)s];
+    sl.planner.reset(new Planner(c.d));
+    sl.chain.reset(new ChainBuilder(c.d, c.chain_AR, c.chain_smask));
+    sl.fed = sl.uploaded = sl.slices = 0;
+    sl.acc_half = 0;
+    sl.outq.assign((size_t)c.C, std::vector<float>());
+    sl.outq_head = 0;
+    sl.open = true;
+    *slot = s;
+    return PV_OK;
+}
+
+int pv_pool_close(pv_pool *p, int32_t slot) {
+    g_last_error.clear();
+    if (!pool_slot_ok(p, slot)) {
+        g_last_error = "stream pool: slot is not open";
+        return PV_ERR_INVALID_ARG;
+    }
+    pv_pool::Slot &sl = p->slots[(size_t)slot];
+    sl.open = false;
+    sl.planner.reset();
+    sl.chain.reset();
+    sl.outq.clear();
+    sl.outq_head = 0;
+    return PV_OK;
+}
+
+int32_t pv_pool_available(const pv_pool *p, int32_t slot) {
+    return pool_slot_ok(p, slot) ? p->slots[(size_t)slot].planner->available() : -1;
+}
+
+int pv_pool_get_info(const pv_pool *p, int32_t slot, pv_info *info) {
+    if (!pool_slot_ok(p, slot) || !info) return PV_ERR_INVALID_ARG;
+    fill_info(p->core.d, p->slots[(size_t)slot].planner->slices(), info);
+    return PV_OK;
+}
+
+int32_t pv_pool_retrieve(pv_pool *p, int32_t slot, float *const *out, int32_t n) {
+    if (!pool_slot_ok(p, slot) || n < 0 || (n > 0 && !out)) return -1;
+    pv_pool::Slot &sl = p->slots[(size_t)slot];
+    const size_t held = sl.outq.empty() ? 0 : sl.outq[0].size() - sl.outq_head;
+    if ((size_t)n > held) n = (int32_t)held;
+    const int32_t got = sl.planner->retrieve(n);
+    for (int ch = 0; ch < p->core.C && got > 0; ++ch)
+        memcpy(out[ch], sl.outq[(size_t)ch].data() + sl.outq_head, (size_t)got * sizeof(float));
+    sl.outq_head += (size_t)got;
+    if (sl.outq_head > (1u << 16)) {
+        for (auto &q : sl.outq) q.erase(q.begin(), q.begin() + (long)sl.outq_head);
+        sl.outq_head = 0;
+    }
+    return got;
+}
+
+// the stages of one launch group for every slot in it (the fields as Core::launch_chunk sets them, rows = C);
+// launch = false: launch nothing, only ask the launchers whether this configuration fits them (pv_pool_create)
+static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch) {
+    const Core &c = p->core;
+    const Derived &d = c.d;
+    hipStream_t st = p->stream;
+    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
+    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    auto refused = [](const char *what) {
+        g_last_error = std::string("stream pool: no per-slot ") + what + " kernel for this configuration";
+        return PV_ERR_UNSUPPORTED;
+    };
+    auto launched = [](const char *what) -> int {
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
+    };
+    int rc;
+    AnalyzeArgs aa{};
+    aa.tb = c.tb;
+    aa.ia.in = p->d_in.p;
+    aa.ia.stride_c = p->ring;
+    aa.ia.stride_s = (int64_t)p->ring * c.C;
+    aa.ia.mask = (uint64_t)(p->ring - 1);
+    aa.ia.len = INT64_MAX;
+    aa.hop = d.hop;
+    aa.TR = c.TR;
+    aa.rows = c.C;
+    aa.PKP = c.PKP;
+    aa.find_peaks = cm == 1 ? 1 : 0;
+    aa.split = c.split_analysis ? 1 : 0;
+    aa.mag = c.mag.p;
+    aa.phase = c.phase.p;
+    aa.peaks = c.peaks.p;
+    aa.npk = c.npk.p;
+    if (launch && !launch_pool_analyze(aa, pl, st)) return refused("analysis");
+    if (launch && (rc = launched("pool analysis launch")) != PV_OK) return rc;
+    if (!launch) {
+    } else if (cm == 1) {
+        MatchArgs ma{};
+        ma.N = d.N, ma.hs = d.hs, ma.HP = c.HP, ma.PKP = c.PKP, ma.C = c.C, ma.hop = d.hop, ma.TR = c.TR, ma.rows = c.C;
+        ma.two_pi_hop = d.two_pi_hop;
+        ma.phase = c.phase.p, ma.peaks = c.peaks.p, ma.npk = c.npk.p, ma.recs = c.recs.p, ma.modes = c.modes.p;
+        SeqArgs qa{};
+        qa.N = d.N, qa.hs = d.hs, qa.HP = c.HP, qa.PKP = c.PKP, qa.C = c.C, qa.hop = d.hop, qa.TR = c.TR, qa.rows = c.C;
+        qa.two_pi_hop = d.two_pi_hop;
+        qa.phase = c.phase.p, qa.peaks = c.peaks.p, qa.npk = c.npk.p, qa.recs = c.recs.p, qa.modes = c.modes.p;
+        qa.rot = c.rot.p, qa.outphase = c.outphase.p;
+        qa.st_kind = c.st_kind.p, qa.st_rot = c.st_rot.p, qa.st_po = c.st_po.p;
+        qa.high_prio = 1;
+        if (!launch_pool_phase(ma, qa, pl, st)) return refused("phase");
+        if ((rc = launched("pool phase launch")) != PV_OK) return rc;
+    } else if (cm == 0) {
+        PropArgs pa{};
+        pa.N = d.N, pa.hs = d.hs, pa.HP = c.HP, pa.C = c.C, pa.hop = d.hop, pa.TR = c.TR, pa.rows = c.C;
+        pa.two_pi_hop = d.two_pi_hop;
+        pa.phase = c.phase.p, pa.outphase = c.outphase.p, pa.st_pp = c.st_pp.p, pa.st_po = c.st_po.p;
+        if (!launch_pool_prop(pa, pl, st)) return refused("propagation");
+        if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
+    }
+    SynthArgs sa{};
+    sa.tb = c.tb;
+    sa.hop = d.hop;
+    sa.C = c.C;
+    sa.two_pi_hop = d.two_pi_hop;
+    sa.do_freq_comp = d.do_freq_comp ? 1 : 0;
+    sa.freq_comp = d.freq_comp;
+    sa.fixed_gain = d.fixed_gain;
+    sa.inv_n = d.inv_n;
+    sa.robotic = d.robotic ? 1 : 0;
+    sa.voc_band_len = -1;
+    sa.coremode = cm < 0 ? 0 : cm;
+    sa.TR = c.TR;
+    sa.rows = c.C;
+    sa.PKP = c.PKP;
+    sa.mag = c.mag.p, sa.phase = c.phase.p, sa.outphase = c.outphase.p, sa.peaks = c.peaks.p, sa.npk = c.npk.p;
+    sa.modes = c.modes.p, sa.rot = c.rot.p, sa.frames = c.frames.p, sa.FR = c.FR;
+    ChainArgs ca{};
+    ca.N = d.N;
+    ca.rows = c.C;
+    ca.C = c.C;
+    ca.AR = c.chain_AR;
+    ca.smask = c.chain_smask;
+    ca.waves = c.chain_waves;
+    ca.runs = 1;
+    ca.st_acc = c.st_acc.p;
+    ca.stream = c.stream.p;
+    ca.resample = d.resample ? 1 : 0;
+    ca.frames = c.frames.p;
+    ca.FR = c.FR;
+    ca.fast = c.fast_chain() ? 1 : 0;
+    if (!launch_pool_synth_chain(sa, ca, pl, st, launch)) return refused("synthesis + overlap-add");
+    if (launch && (rc = launched("pool synthesis + overlap-add launch")) != PV_OK) return rc;
+    if (d.resample) {
+        ResArgs ra{};
+        ra.rows = c.C;
+        ra.smask = c.chain_smask;
+        ra.stream = c.stream.p;
+        ra.interp = d.interp ? 1 : 0;
+        ra.filt_len = d.filt_len;
+        ra.oversample = d.oversample;
+        ra.sinc = c.sinc.p;
+        ra.sinc_len = (int)d.sinc.size();
+        ra.tab4 = c.tab4.p;
+        ra.lds_floats = c.ola_lds_floats;
+        ra.tab_bytes = d.interp ? d.oversample * (d.filt_len + 1) * 16 : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
+        ra.fast = c.fast_chain() ? 1 : 0;
+        if (!launch_pool_resample(ra, pl, st, launch)) return refused("resampling");
+        if (launch && (rc = launched("pool resampling launch")) != PV_OK) return rc;
+    }
+    return PV_OK;
+}
+
+int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *const *in, const int32_t *n) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p || count < 0 || (count > 0 && (!slots || !n))) return PV_ERR_INVALID_ARG;
+    if (p->poisoned) {
+        g_last_error = "pool unusable after an earlier failure: " + p->poison_reason;
+        return p->poisoned;
+    }
+    Core &c = p->core;
+    const int C = c.C;
+    {
+        std::vector<char> seen((size_t)p->cap, 0);
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t s = slots[i];
+            const char *bad = !pool_slot_ok(p, s) ? "is not open" : seen[(size_t)s] ? "is listed twice" : n[i] < 0 ? "has a negative size" : nullptr;
+            if (!bad && n[i] > 0) {
+                if (!in) bad = "has no input";
+                else
+                    for (int ch = 0; ch < C && !bad; ++ch)
+                        if (!in[(size_t)i * C + ch]) bad = "has no input";
+            }
+            if (bad) {
+                g_last_error = "stream pool: slot " + std::to_string(s) + " " + bad;
+                return PV_ERR_INVALID_ARG;
+            }
+            seen[(size_t)s] = 1;
+        }
+    }
+    if (count == 0) return PV_OK;
+    const auto t_call = std::chrono::steady_clock::now();
+    // 1. plan every slot; all or nothing
+    std::vector<std::vector<SliceRec>> fresh((size_t)count);
+    {
+        std::vector<Planner::State> before((size_t)count);
+        for (int32_t i = 0; i < count; ++i) {
+            Planner &pl = *p->slots[(size_t)slots[i]].planner;
+            before[(size_t)i] = pl.save();
+            const int st = pl.feed(n[i], fresh[(size_t)i]);
+            if (st != PV_OK) {
+                for (int32_t j = 0; j <= i; ++j) p->slots[(size_t)slots[j]].planner->restore(before[(size_t)j]);
+                g_last_error = "stream pool: slot " + std::to_string(slots[i]) + ": " +
+                               (g_last_error.empty() ? std::string(plan_reason()) : g_last_error);
+                return st;
+            }
+        }
+    }
+    // from here on device state and host bookkeeping move together; a failure poisons the pool
+    auto fail = [&](int code) {
+        p->poisoned = code;
+        p->poison_reason = g_last_error.empty() ? pv_strerror(code) : g_last_error;
+        return code;
+    };
+    {
+        const hipError_t e = hipSetDevice(c.device);
+        if (e != hipSuccess) return fail(hip_fail(e, "hipSetDevice", __LINE__));
+    }
+    // 2. the call's new samples, packed [slot][C][n] (one copy)
+    std::vector<int64_t> stage_off((size_t)count), out_base((size_t)count), out_cnt((size_t)count), k0((size_t)count);
+    std::vector<int64_t> call_base((size_t)count);
+    size_t stage_total = 0, out_total = 0;
+    int groups = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        stage_off[(size_t)i] = (int64_t)stage_total;
+        stage_total += (size_t)C * n[i];
+        const std::vector<SliceRec> &f = fresh[(size_t)i];
+        out_base[(size_t)i] = (int64_t)out_total;
+        out_cnt[(size_t)i] = f.empty() ? 0 : f.back().K0 + f.back().cnt - f.front().K0;
+        k0[(size_t)i] = f.empty() ? 0 : f.front().K0;
+        out_total += (size_t)C * out_cnt[(size_t)i];
+        const int g = (int)((f.size() + kStreamChunk - 1) / kStreamChunk);
+        if (g > groups) groups = g;
+        call_base[(size_t)i] = p->slots[(size_t)slots[i]].fed;
+    }
+    int st;
+    if (stage_total > p->h_stage.n) {
+        size_t capn = p->h_stage.n ? p->h_stage.n : 1 << 16;
+        while (capn < stage_total) capn *= 2;
+        if ((st = p->h_stage.alloc(capn)) != PV_OK) return fail(st);
+#ifdef PV_POOL_MAPPED_INGEST // (measurement build: the ingest kernel reads the page-locked staging over the bus)
+        void *sp = nullptr;
+        const hipError_t e = hipHostGetDevicePointer(&sp, p->h_stage.p, 0);
+        if (e != hipSuccess) return fail(hip_fail(e, "staging mapping", __LINE__));
+        p->stage_src = static_cast<float *>(sp);
+#else
+        if ((st = p->d_stage.alloc(capn)) != PV_OK) return fail(st);
+        p->stage_src = p->d_stage.p;
+#endif
+    }
+    for (int32_t i = 0; i < count; ++i)
+        for (int ch = 0; ch < C; ++ch)
+            if (n[i] > 0)
+                memcpy(p->h_stage.p + stage_off[(size_t)i] + (size_t)ch * n[i], in[(size_t)i * C + ch], (size_t)n[i] * sizeof(float));
+    if (out_total > p->h_out.n) {
+        size_t capn = p->h_out.n ? p->h_out.n : 1 << 16;
+        while (capn < out_total) capn *= 2;
+        if ((st = p->h_out.alloc(capn)) != PV_OK) return fail(st);
+        void *op = nullptr;
+        const hipError_t e = hipHostGetDevicePointer(&op, p->h_out.p, 0);
+        if (e != hipSuccess) return fail(hip_fail(e, "output arena mapping", __LINE__));
+        p->out_dev = static_cast<float *>(op);
+    }
+    // 3. descriptors of every group, one block: per group its PoolSlot table and ingest list, per slot its phase
+    // increments, run list, run offsets, denominators and resampling tiles
+    std::vector<char> blob;
+    auto put = [&](const void *src, size_t bytes) -> int64_t {
+        const size_t off = (blob.size() + 15) & ~(size_t)15;
+        blob.resize(off + bytes);
+        if (bytes) memcpy(blob.data() + off, src, bytes);
+        return (int64_t)off;
+    };
+    struct Group {
+        int64_t table_off, ingest_off;
+        int nslots, ningest, max_tn, max_tiles, max_in;
+    };
+    std::vector<Group> grp((size_t)groups + 1); // (+ the final ingest of what the call leaves unconsumed)
+    std::vector<PoolSlot> table;
+    std::vector<PoolIngest> ingest;
+    std::vector<int32_t> pinc;
+    std::vector<float> wden, wden_hi;
+    std::vector<ChainSlice> cs;
+    std::vector<int32_t> ro;
+    std::vector<ResTile> res_tiles;
+    std::vector<uint2> res_otab;
+    auto add_ingest = [&](int32_t i, int64_t upto, Group &g) {
+        pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+        if (upto <= sl.uploaded) return;
+        PoolIngest e{};
+        e.src_off = stage_off[(size_t)i] + (sl.uploaded - call_base[(size_t)i]);
+        e.src_pitch = n[i];
+        e.pos = sl.uploaded;
+        e.n = (int32_t)(upto - sl.uploaded);
+        e.row0 = slots[i] * C;
+        ingest.push_back(e);
+        if (e.n > g.max_in) g.max_in = e.n;
+        sl.uploaded = upto;
+    };
+    for (int32_t i = 0; i < count; ++i) p->slots[(size_t)slots[i]].fed += n[i];
+    for (int gi = 0; gi < groups; ++gi) {
+        Group &g = grp[(size_t)gi];
+        g = Group{0, 0, 0, 0, 0, 0, 0};
+        table.clear();
+        ingest.clear();
+        for (int32_t i = 0; i < count; ++i) {
+            const std::vector<SliceRec> &f = fresh[(size_t)i];
+            const int ta = gi * kStreamChunk;
+            if ((int)f.size() <= ta) continue;
+            const int tb = (int)f.size() - ta < kStreamChunk ? (int)f.size() : ta + kStreamChunk;
+            const int Tn = tb - ta;
+            pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+            const int64_t t0 = sl.slices + ta;
+            int64_t need = (t0 + Tn - 1) * (int64_t)c.d.hop + c.d.N;
+            if (need > sl.fed) need = sl.fed;
+            add_ingest(i, need, g);
+            PoolSlot ps{};
+            ps.t0 = t0;
+            ps.s0 = (int32_t)(t0 % c.TR);
+            ps.Tn = Tn;
+            ps.row0 = slots[i] * C;
+            ps.acc_sel = sl.acc_half | (t0 == 0 ? 2 : 0);
+            sl.acc_half ^= 1;
+            pinc.clear();
+            for (int t = ta; t < tb; ++t) pinc.push_back(f[(size_t)t].phase_inc);
+            ps.pinc_off = put(pinc.data(), pinc.size() * sizeof(int32_t));
+            wden.clear();
+            wden_hi.clear();
+            cs.clear();
+            ro.clear();
+            const int64_t ka = f[(size_t)ta].K0, kb = f[(size_t)tb - 1].K0 + f[(size_t)tb - 1].cnt;
+            sl.chain->begin_launch(f[(size_t)ta]);
+            for (int t = ta; t < tb; ++t) sl.chain->add(f[(size_t)t], INT64_MAX, wden, wden_hi);
+            sl.chain->end_launch(1, cs, ro);
+            while (wden.size() & 3) wden.push_back(1.f);
+            for (int k = 0; k < 4; ++k) wden.push_back(1.f);
+            if (c.fast_chain())
+                for (float &v : wden) v = 1.0f / v;
+            ps.cs_off = put(cs.data(), cs.size() * sizeof(ChainSlice));
+            const int32_t ro4[4] = {0, (int32_t)cs.size(), 0, 0};
+            ps.ro_off = put(ro4, sizeof ro4);
+            ps.wden_off = put(wden.data(), wden.size() * sizeof(float));
+            res_tiles.clear();
+            res_otab.clear();
+            if (c.d.resample && kb > ka) c.build_res_tiles(ka, kb, res_tiles, res_otab);
+            ps.res_ntiles = (int32_t)res_tiles.size();
+            ps.res_off = put(res_tiles.data(), res_tiles.size() * sizeof(ResTile));
+            ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
+            ps.out_off = out_base[(size_t)i] + (ka - k0[(size_t)i]);
+            ps.out_stride_row = out_cnt[(size_t)i];
+            ps.k_base = ka;
+            table.push_back(ps);
+            if (Tn > g.max_tn) g.max_tn = Tn;
+            if (ps.res_ntiles > g.max_tiles) g.max_tiles = ps.res_ntiles;
+        }
+        g.nslots = (int)table.size();
+        g.table_off = put(table.data(), table.size() * sizeof(PoolSlot));
+        g.ningest = (int)ingest.size();
+        g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
+    }
+    {
+        Group &g = grp[(size_t)groups];
+        g = Group{0, 0, 0, 0, 0, 0, 0};
+        ingest.clear();
+        for (int32_t i = 0; i < count; ++i) add_ingest(i, p->slots[(size_t)slots[i]].fed, g);
+        g.ningest = (int)ingest.size();
+        g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
+    }
+    for (int32_t i = 0; i < count; ++i) p->slots[(size_t)slots[i]].slices += (int64_t)fresh[(size_t)i].size();
+    if (blob.size() > p->h_desc.n) {
+        size_t capn = p->h_desc.n ? p->h_desc.n : 256 * 1024;
+        while (capn < blob.size()) capn *= 2;
+        if ((st = p->h_desc.alloc(capn)) != PV_OK || (st = p->d_desc.alloc(capn)) != PV_OK) return fail(st);
+    }
+    memcpy(p->h_desc.p, blob.data(), blob.size());
+    // 4. two copies and the launches; the previous call has finished with both staging buffers
+    hipError_t ce = hipSuccess;
+#ifndef PV_POOL_MAPPED_INGEST
+    if (stage_total)
+        ce = hipMemcpyAsync(p->d_stage.p, p->h_stage.p, stage_total * sizeof(float), hipMemcpyHostToDevice, p->stream);
+    if (ce != hipSuccess) return fail(hip_fail(ce, "input upload", __LINE__));
+#endif
+    ce = hipMemcpyAsync(p->d_desc.p, p->h_desc.p, blob.size(), hipMemcpyHostToDevice, p->stream);
+    if (ce != hipSuccess) return fail(hip_fail(ce, "descriptor upload", __LINE__));
+    for (int gi = 0; gi <= groups; ++gi) {
+        const Group &g = grp[(size_t)gi];
+        launch_pool_ingest(p->stage_src, p->d_in.p, p->ring, C, reinterpret_cast<const PoolIngest *>(p->d_desc.p + g.ingest_off),
+                           g.ningest, g.max_in, p->stream);
+        const hipError_t ie = hipGetLastError();
+        if (ie != hipSuccess) return fail(hip_fail(ie, "input ingest", __LINE__));
+        if (gi == groups || g.nslots == 0) continue;
+        PoolLaunch pl{};
+        pl.slots = reinterpret_cast<const PoolSlot *>(p->d_desc.p + g.table_off);
+        pl.desc = p->d_desc.p;
+        pl.out = p->out_dev;
+        pl.nslots = g.nslots;
+        pl.max_tn = g.max_tn;
+        pl.max_tiles = g.max_tiles;
+        if ((st = pool_launch_group(p, pl)) != PV_OK) return fail(st);
+    }
+    // 5. wait: a sequence number behind the launches, spun on with a wall-clock bound (or a stream synchronisation
+    // where the device has no stream memory operations)
+    hipError_t he = hipSuccess;
+    const auto t_wait = std::chrono::steady_clock::now();
+    if (p->wait_value) {
+        const uint32_t seq = ++p->flag_seq;
+        he = hipStreamWriteValue32(p->stream, p->flag_dev, seq, 0);
+        if (he == hipSuccess) {
+            volatile uint32_t *fl = p->h_flag.p;
+            const auto t_start = std::chrono::steady_clock::now();
+            uint32_t spins = 0;
+            while (__atomic_load_n(fl, __ATOMIC_ACQUIRE) != seq) {
+                if ((++spins & 0xfffu) != 0) continue;
+                const hipError_t q = hipStreamQuery(p->stream);
+                if (q != hipSuccess && q != hipErrorNotReady) {
+                    he = q;
+                    break;
+                }
+                if (__atomic_load_n(fl, __ATOMIC_ACQUIRE) == seq) break;
+                if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(10)) {
+                    g_last_error = "stream pool: the call's kernels did not finish within 10 s";
+                    return fail(PV_ERR_HIP);
+                }
+            }
+        }
+    } else {
+        he = hipStreamSynchronize(p->stream);
+    }
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he != hipSuccess) return fail(hip_fail(he, "stream pool call", __LINE__));
+    {
+        const auto t_done = std::chrono::steady_clock::now();
+        p->last_host_us = std::chrono::duration<double, std::micro>(t_wait - t_call).count();
+        p->last_wait_us = std::chrono::duration<double, std::micro>(t_done - t_wait).count();
+    }
+    // 6. the arena into the slots' FIFOs
+    for (int32_t i = 0; i < count; ++i) {
+        const int64_t cnt = out_cnt[(size_t)i];
+        if (cnt <= 0) continue;
+        pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+        for (int ch = 0; ch < C; ++ch) {
+            const float *src = p->h_out.p + out_base[(size_t)i] + (size_t)ch * cnt;
+            sl.outq[(size_t)ch].insert(sl.outq[(size_t)ch].end(), src, src + cnt);
+        }
+    }
+    return PV_OK;
 }
 
 } // extern "C"

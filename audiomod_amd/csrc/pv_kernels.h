@@ -297,4 +297,51 @@ void launch_synth(const SynthArgs &a, hipStream_t st);
 void launch_cepstral(const CepstralArgs &a, hipStream_t st); // nc 1024 / 2048 only
 void launch_ola(const OlaArgs &a, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------------------------------
+// Stream pool (pv_pool_*): one launch of each stage serves many independent streams ("slots"), each with its own
+// schedule.  grid.y (grid.z for the propagation kernel) is the slot's entry in the launch's PoolSlot table; the
+// kernels build a slot view of the argument block -- base pointers moved to the slot's C rows, rows = C, the slot's
+// t0 / s0 / Tn and descriptors -- and call the batch kernels' device functions.  The argument blocks passed in hold
+// the pool-wide base pointers with rows = C.  Buffers whose rows are not [rows][...] are laid out per slot by the
+// pool: the accumulator images as [slot][2][C][AR].
+// ---------------------------------------------------------------------------------------------------------------
+struct PoolSlot {
+    int64_t t0;       // the slot's first slice in this launch (its own count)
+    int32_t s0, Tn;   // ring slot of t0; the slot's slices in this launch (>= 1)
+    int32_t row0;     // first row of the slot (slot index * C)
+    int32_t acc_sel;  // ChainArgs::acc_sel of the slot (its own half and "stream starts here" bit)
+    int32_t res_ntiles; // tiles of the resampling kernel
+    int32_t pad;
+    // byte offsets into the launch's descriptor block (PoolLaunch::desc)
+    int64_t pinc_off, cs_off, ro_off, wden_off, res_off, otab_off;
+    int64_t out_off;        // float offset of its first output (row 0) in PoolLaunch::out
+    int64_t out_stride_row; // floats between its rows there
+    int64_t k_base;         // output index of out_off
+};
+struct PoolLaunch {
+    const PoolSlot *slots; // [nslots]
+    const char *desc;
+    float *out;
+    int nslots;
+    int max_tn;     // largest Tn of the launch (grid size)
+    int max_tiles;  // largest res_ntiles of the launch
+};
+// input ingest: rows [row0, row0 + C) of the device ring get samples [pos, pos + n) of their stream, channel c read
+// from src[src_off + c * src_pitch + i]
+struct PoolIngest {
+    int64_t src_off, src_pitch, pos;
+    int32_t n, row0;
+};
+void launch_pool_ingest(const float *src, float *ring, int ring_len, int C, const PoolIngest *ents, int nents,
+                        int max_n, hipStream_t st);
+// Each returns false (launching nothing) when the configuration has no per-slot kernel or it does not fit;
+// launch = false: only that check (pv_pool_create asks it once).
+bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st);
+bool pool_phase_supported(int hs, int PKP);
+bool launch_pool_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, hipStream_t st);
+bool launch_pool_prop(const PropArgs &a, const PoolLaunch &p, hipStream_t st);
+bool launch_pool_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, hipStream_t st,
+                             bool launch = true);
+bool launch_pool_resample(const ResArgs &a, const PoolLaunch &p, hipStream_t st, bool launch = true);
+
 } // namespace pv

@@ -3665,4 +3665,530 @@ void launch_stream(const StreamArgs &s, hipStream_t st) {
     }
 }
 
+// --------------------------------------------------------------------------------------------
+// Stream pool (pv_kernels.h PoolSlot): the streaming path's stages for many independent streams in one launch each.
+// Every workgroup reads its slot's entry, builds a slot view of the argument block and calls the device functions the
+// batch kernels call, so a slot computes exactly what a single-stream engine computes.  Slots differ in their slice
+// counts: a workgroup past its slot's Tn (or tile count) returns at once (workgroup-uniform).
+// --------------------------------------------------------------------------------------------
+// The per-slot kernels' copies of the bodies of pv_synth_chain_kernel, pv_resample_kernel and pv_resample_fast_kernel,
+// as device functions of the row / (tile, row group): the batch kernels keep their source, and so their machine code,
+// exactly as they are.  A change to one of those kernels must be made to its copy here too.
+template <int NC, int kPlainCore, int kRes, bool kFast>
+__device__ __forceinline__ void pool_synth_chain_role(const SynthArgs &s, const ChainArgs &c, const int row, char *smem_raw) {
+    using W = WF<NC>;
+    constexpr int N = 2 * NC, hs = NC, NQ = N / 4, NP = NQ / 64;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    constexpr int run = 0; // a slot's slices of a launch are one run
+    // (entry i of the run's list is its i-th slice in order; ChainSlice::tl says which slice of the launch it is)
+    const int i_begin = c.run_off[run], i_count = c.run_off[run + 1] - i_begin;
+    cf *wlds = reinterpret_cast<cf *>(smem_raw) + wave * W::LDS_CF;
+    const ChainLds l = chain_carve(c, smem_raw + (size_t)c.waves * W::LDS_CF * sizeof(cf));
+    chain_prologue(c, l, row, run == 0);
+    const float *__restrict__ w = s.tb.window;
+    const bool upper = (row % c.C) > 0;
+    const int lane0 = lane;
+    for (int i = wave; i < i_count; i += c.waves) {
+        // the lane id, made opaque once per iteration: everything derived from it is recomputed per slice instead of
+        // being hoisted out of the loop and held in registers (which spilled ~100 VGPRs)
+        int lane = lane0;
+        asm volatile("" : "+v"(lane));
+        const ChainSlice sl = c.slices[i_begin + i];
+        const int tl = sl.tl;
+        const bool skip = (sl.flags & 1) && upper; // wave-uniform
+        float4 A[NP];
+        if (!skip) {
+            if (!PV_CHAIN_DIAG(c, 8)) synth_wave_role<NC, kPlainCore, 1, kFast>(s, row, tl, wlds, lane);
+            // ifftshift + synthesis window (phasevocoderimpl.h:183-198): four consecutive samples per lane and piece
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                const int i = 4 * (lane + 64 * j);
+                const int e = ((i + hs) & (N - 1)) >> 1;
+                const cf z0 = wlds[W::pad(e)], z1 = wlds[W::pad(e) + 1];
+                const float4 ww = *reinterpret_cast<const float4 *>(w + i);
+                A[j] = make_float4(z0.x * ww.x, z0.y * ww.y, z1.x * ww.z, z1.y * ww.w);
+            }
+        }
+        const int r = sl.acc_pos & 3; // wave-uniform
+        if (r == 0) chain_slice_tail<0, NP, kRes, kFast>(c, l, sl, A, skip, row, i, lane);
+        else if (r == 1) chain_slice_tail<1, NP, kRes, kFast>(c, l, sl, A, skip, row, i, lane);
+        else if (r == 2) chain_slice_tail<2, NP, kRes, kFast>(c, l, sl, A, skip, row, i, lane);
+        else chain_slice_tail<3, NP, kRes, kFast>(c, l, sl, A, skip, row, i, lane);
+    }
+    chain_epilogue(c, l, row, true);
+}
+
+template <int kRes> // 1 = direct sinc table, 2 = cubic-interpolated table
+__device__ __forceinline__ void pool_resample_role(const ResArgs &a, const unsigned tile_i, const unsigned grp, char *smem_raw) {
+    constexpr int NR = kResRows;
+    float4 *tab4 = reinterpret_cast<float4 *>(smem_raw);
+    float *stab = reinterpret_cast<float *>(smem_raw);
+    float *xs = reinterpret_cast<float *>(smem_raw + a.tab_bytes); // [NR][lds_floats]
+    const int nt = blockDim.x, tid = threadIdx.x;
+    const ResTile tile = a.tiles[tile_i];
+    const int row0 = grp * NR, NF = a.filt_len;
+    const int nr = a.rows - row0 < NR ? a.rows - row0 : NR;
+    uint2 oe = make_uint2(0u, 0u);
+    if (tid < tile.kcnt) oe = a.otab[(int64_t)tile_i * kTileOut + tid];
+    // the tile's stream samples of every row, all loads in flight before the first LDS write (a tile needs at most
+    // two samples per thread and row at the ratios that resample: n_cnt <= 256 * num/den + filt_len)
+    float xv[NR][2];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const float *__restrict__ st = a.stream + (int64_t)(r < nr ? row0 + r : row0) * ((int64_t)a.smask + 1);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = tid + h * kTileOut;
+            const int64_t n = tile.n_lo + i; // the stream is zero before its first sample (skip_zeros, :1225)
+            xv[r][h] = (i < tile.n_cnt && n >= 0) ? st[(uint32_t)n & (uint32_t)a.smask] : 0.f;
+        }
+    }
+    if (kRes == 2) {
+        const int cnt = a.oversample * (NF + 1);
+        for (int i = tid; i < cnt; i += nt) tab4[i] = a.tab4[i];
+    } else {
+        for (int i = tid; i < a.sinc_len; i += nt) stab[i] = a.sinc[i];
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = tid + h * kTileOut;
+            if (i < tile.n_cnt) xs[r * a.lds_floats + i] = xv[r][h];
+        }
+    }
+    // (longer tiles -- strong down-sampling, more than two samples per thread -- take the rest in a loop)
+    for (int i = tid + 2 * kTileOut; i < tile.n_cnt; i += nt)
+        for (int r = 0; r < nr; ++r) {
+            const int64_t n = tile.n_lo + i;
+            const float *__restrict__ st = a.stream + (int64_t)(row0 + r) * ((int64_t)a.smask + 1);
+            xs[r * a.lds_floats + i] = n >= 0 ? st[(uint32_t)n & (uint32_t)a.smask] : 0.f;
+        }
+    __syncthreads();
+    if (tid >= tile.kcnt) return;
+    float *__restrict__ out = a.out + (int64_t)row0 * a.out_stride_row + (tile.k0 - a.k_base) + tid;
+    const float *x = xs + (int)(oe.x & 0xffffu); // tap j = 0
+    if (kRes == 2) {
+        const float frac = __uint_as_float(oe.y);
+        const float4 *__restrict__ T = tab4 + (int)(oe.x >> 16) * (NF + 1);
+        v2f a01[NR], a23[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) a01[r] = v2f{0.f, 0.f}, a23[r] = v2f{0.f, 0.f};
+#pragma unroll 4
+        for (int j = 0; j < NF; ++j) { // NF is a multiple of 4 (resample.c:687)
+            const float4 c = T[j];
+            const v2f c01 = {c.x, c.y}, c23 = {c.z, c.w};
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const float xr = x[r * a.lds_floats + j]; // a missing row holds zeros: computed, never stored
+                const v2f xx = {xr, xr};
+                a01[r] += xx * c01;
+                a23[r] += xx * c23;
+            }
+        }
+        // cubic_coef (resample.c:339-351)
+        const float c0 = -0.16667f * frac + 0.16667f * frac * frac * frac;
+        const float c1 = frac + 0.5f * frac * frac - 0.5f * frac * frac * frac;
+        const float c3 = -0.33333f * frac + 0.5f * frac * frac - 0.16667f * frac * frac * frac;
+        const float c2 = (float)(1. - c0 - c1 - c3);
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            if (r < nr)
+                out[(int64_t)r * a.out_stride_row] = (c0 * a01[r].x) + (c1 * a01[r].y) + (c2 * a23[r].x) + (c3 * a23[r].y);
+    } else {
+        const float *t = stab + (oe.x >> 16) * (uint32_t)NF;
+        for (int r = 0; r < nr; ++r) {
+            float sum = 0.f;
+            for (int j = 0; j < NF; ++j) sum += x[r * a.lds_floats + j] * t[j];
+            out[(int64_t)r * a.out_stride_row] = sum;
+        }
+    }
+}
+
+template <int kRes, int NR> // 1 = direct sinc table, 2 = cubic-interpolated table
+__device__ __forceinline__ void pool_resample_fast_role(const ResArgs &a, const unsigned tile_i, const unsigned grp, char *smem_raw) {
+    float4 *tab4 = reinterpret_cast<float4 *>(smem_raw);
+    float *stab = reinterpret_cast<float *>(smem_raw);
+    float *xs = reinterpret_cast<float *>(smem_raw + a.tab_bytes); // [NR][lds_floats]
+    const int nt = blockDim.x, tid = threadIdx.x;
+    const ResTile tile = a.tiles[tile_i];
+    const int row0 = grp * NR, NF = a.filt_len;
+    const int nr = a.rows - row0 < NR ? a.rows - row0 : NR;
+    uint2 oe = make_uint2(0u, 0u);
+    if (tid < tile.kcnt) oe = a.otab[(int64_t)tile_i * kTileOut + tid];
+    // the tile's stream samples of every row (a missing row re-reads the group's first: computed, never stored)
+    for (int i = tid; i < tile.n_cnt; i += nt) {
+        const int64_t n = tile.n_lo + i; // the stream is zero before its first sample (skip_zeros, :1225)
+        float xv[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const float *__restrict__ st = a.stream + (int64_t)(r < nr ? row0 + r : row0) * ((int64_t)a.smask + 1);
+            xv[r] = n >= 0 ? st[(uint32_t)n & (uint32_t)a.smask] : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r) xs[r * a.lds_floats + i] = xv[r];
+    }
+    if (kRes == 2) {
+        const int cnt = a.oversample * (NF + 1);
+        for (int i = tid; i < cnt; i += nt) tab4[i] = a.tab4[i];
+    } else {
+        for (int i = tid; i < a.sinc_len; i += nt) stab[i] = a.sinc[i];
+    }
+    __syncthreads();
+    if (tid >= tile.kcnt) return;
+    float *__restrict__ out = a.out + (int64_t)row0 * a.out_stride_row + (tile.k0 - a.k_base) + tid;
+    const float *x = xs + (int)(oe.x & 0xffffu); // tap j = 0
+    float acc[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = 0.f;
+    if (kRes == 2) {
+        const float frac = __uint_as_float(oe.y);
+        // cubic_coef (resample.c:339-351)
+        const float c0 = -0.16667f * frac + 0.16667f * frac * frac * frac;
+        const float c1 = frac + 0.5f * frac * frac - 0.5f * frac * frac * frac;
+        const float c3 = -0.33333f * frac + 0.5f * frac * frac - 0.16667f * frac * frac * frac;
+        const float c2 = (float)(1. - c0 - c1 - c3);
+        const float4 *__restrict__ T = tab4 + (int)(oe.x >> 16) * (NF + 1);
+#pragma unroll 4
+        for (int j = 0; j < NF; ++j) { // NF is a multiple of 4 (resample.c:687)
+            // (PV_EXP_RES: elimination builds for timing only -- bit 0 no sample reads, bit 1 no coefficient reads)
+#if defined(PV_EXP_RES) && (PV_EXP_RES & 2)
+            const float4 c = make_float4(frac, c0, c1, (float)j);
+#else
+            const float4 c = T[j];
+#endif
+            const float h = __builtin_fmaf(c3, c.w, __builtin_fmaf(c2, c.z, __builtin_fmaf(c1, c.y, c0 * c.x)));
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+#if defined(PV_EXP_RES) && (PV_EXP_RES & 1)
+                acc[r] = __builtin_fmaf(frac + (float)r, h, acc[r]);
+#else
+                acc[r] = __builtin_fmaf(x[r * a.lds_floats + j], h, acc[r]);
+#endif
+            }
+        }
+    } else {
+        const float *t = stab + (oe.x >> 16) * (uint32_t)NF;
+#pragma unroll 4
+        for (int j = 0; j < NF; ++j) {
+            const float h = t[j];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) acc[r] = __builtin_fmaf(x[r * a.lds_floats + j], h, acc[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+        if (r < nr) out[(int64_t)r * a.out_stride_row] = acc[r];
+}
+
+__global__ __launch_bounds__(256) void pv_pool_ingest_kernel(const float *__restrict__ src, float *__restrict__ ring,
+                                                             const int ring_len, const PoolIngest *__restrict__ ents) {
+    const PoolIngest e = ents[blockIdx.z];
+    const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    if (i >= e.n) return;
+    ring[(int64_t)(e.row0 + c) * ring_len + ((e.pos + i) & (int64_t)(ring_len - 1))] = src[e.src_off + c * e.src_pitch + i];
+}
+
+void launch_pool_ingest(const float *src, float *ring, int ring_len, int C, const PoolIngest *ents, int nents,
+                        int max_n, hipStream_t st) {
+    if (nents <= 0 || max_n <= 0) return;
+    hipLaunchKernelGGL(pv_pool_ingest_kernel, dim3((max_n + 255) / 256, C, nents), dim3(256), 0, st, src, ring,
+                       ring_len, ents);
+}
+
+__device__ __forceinline__ AnalyzeArgs pool_view(const AnalyzeArgs &a, const PoolSlot &ps) {
+    AnalyzeArgs v = a;
+    const int64_t r = ps.row0;
+    v.t0 = ps.t0, v.s0 = ps.s0, v.Tn = ps.Tn;
+    v.ia.in += r * a.ia.stride_c;
+    v.mag += r * a.TR * a.tb.HP;
+    v.phase += r * a.TR * a.tb.HP;
+    if (a.find_peaks) {
+        v.peaks += r * a.TR * a.PKP;
+        v.npk += r * a.TR;
+    }
+    return v;
+}
+
+// analysis, one wave per frame: workgroup x = tl * C + c
+template <int NC> __global__ __launch_bounds__(64) void pv_pool_analyze_wave_kernel(const AnalyzeArgs a, const PoolLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int tl = __builtin_amdgcn_readfirstlane((int)blockIdx.x / a.rows), row = blockIdx.x - tl * a.rows;
+    if (tl >= ps.Tn) return;
+    analyze_wave_role<NC, WF<NC>::LDS_CF * sizeof(cf)>(pool_view(a, ps), row, tl, reinterpret_cast<cf *>(smem_raw));
+}
+__global__ __launch_bounds__(128) void pv_pool_analyze_split_kernel(const AnalyzeArgs a, const PoolLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int tl = __builtin_amdgcn_readfirstlane((int)blockIdx.x / a.rows), row = blockIdx.x - tl * a.rows;
+    if (tl >= ps.Tn) return;
+    analyze_split_role<WF2048S, WF2048S::LDS_CF * sizeof(cf)>(pool_view(a, ps), row, tl, reinterpret_cast<cf *>(smem_raw));
+}
+
+bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st) {
+    const dim3 grid(a.rows * p.max_tn, p.nslots);
+    const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
+    switch (a.tb.nc) {
+    case 256:
+        hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<256>, grid, dim3(64), WF<256>::LDS_CF * sizeof(cf) + atab, st, a, p);
+        return true;
+    case 512:
+        hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<512>, grid, dim3(64), WF<512>::LDS_CF * sizeof(cf) + atab, st, a, p);
+        return true;
+    case 1024:
+        hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<1024>, grid, dim3(64), WF<1024>::LDS_CF * sizeof(cf) + atab, st, a, p);
+        return true;
+    case 2048:
+        if (a.split) {
+            hipLaunchKernelGGL(pv_pool_analyze_split_kernel, grid, dim3(WF2048S::LANES),
+                               WF2048S::LDS_CF * sizeof(cf) + atab + 64, st, a, p);
+        } else {
+            static unsigned long long big = 0;
+            allow_big_lds_dev(pv_pool_analyze_wave_kernel<2048>, big);
+            hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<2048>, grid, dim3(64), WF<2048>::LDS_CF * sizeof(cf) + atab,
+                               st, a, p);
+        }
+        return true;
+    default: return false;
+    }
+}
+
+// phase-locked mode: match + rotation chain of a slot's rows (pv_phase_kernel), one workgroup per (channel, slot)
+constexpr int kPoolSeqDepth = 8;
+template <int D> __global__ __launch_bounds__(1024) void pv_pool_phase_kernel(const MatchArgs m, const SeqArgs a, const PoolLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int64_t r = ps.row0;
+    const int32_t *pinc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    MatchArgs mv = m;
+    mv.t0 = ps.t0, mv.s0 = ps.s0, mv.Tn = ps.Tn, mv.phase_inc = pinc;
+    mv.phase += r * m.TR * m.HP;
+    mv.peaks += r * m.TR * m.PKP;
+    mv.npk += r * m.TR;
+    mv.recs += r * m.TR * m.PKP;
+    mv.modes += r * m.TR;
+    SeqArgs av = a;
+    av.t0 = ps.t0, av.s0 = ps.s0, av.Tn = ps.Tn, av.phase_inc = pinc;
+    av.phase = mv.phase, av.peaks = mv.peaks, av.npk = mv.npk, av.recs = mv.recs, av.modes = mv.modes;
+    av.rot += r * a.TR * a.PKP;
+    av.outphase += r * a.TR * a.HP;
+    av.st_kind += r;
+    av.st_rot += r * a.PKP;
+    av.st_po += r * a.hs;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    for (int tl = wave; tl < mv.Tn; tl += nw)
+        match_wave_role(mv, blockIdx.x, tl, smem_raw + (size_t)wave * match_wave_lds(mv.hs, mv.PKP));
+    __threadfence(); // the records go through global memory: the chain's loads must see them
+    __syncthreads();
+    if (av.high_prio) __builtin_amdgcn_s_setprio(3);
+    seq_role_ring<D>(av, blockIdx.x, smem_raw);
+}
+
+static size_t pool_phase_lds(int hs, int PKP) {
+    SeqArgs q{};
+    q.hs = hs, q.PKP = PKP;
+    const int nt = seq_threads(PKP);
+    const size_t seq_l = ((seq_lds_bytes(q) + 15) & ~(size_t)15) + (size_t)kPoolSeqDepth * nt * sizeof(PeakRec);
+    const size_t match_l = (size_t)(nt / 64) * match_wave_lds(hs, PKP);
+    return seq_l > match_l ? seq_l : match_l;
+}
+bool pool_phase_supported(int hs, int PKP) { return PKP <= seq_threads(PKP) && pool_phase_lds(hs, PKP) <= 160 * 1024 - 512; }
+
+bool launch_pool_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, hipStream_t st) {
+    if (!pool_phase_supported(a.hs, a.PKP)) return false;
+    static unsigned long long big = 0;
+    allow_big_lds_dev(pv_pool_phase_kernel<kPoolSeqDepth>, big);
+    hipLaunchKernelGGL(pv_pool_phase_kernel<kPoolSeqDepth>, dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
+                       pool_phase_lds(a.hs, a.PKP), st, m, a, p);
+    return true;
+}
+
+// coremode 0: the per-bin recurrence; grid (bins / 256, C, slots)
+__global__ __launch_bounds__(kPropThreads) void pv_pool_prop_kernel(const PropArgs a, const PoolLaunch p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const PoolSlot ps = p.slots[blockIdx.z];
+    const int64_t r = ps.row0;
+    PropArgs v = a;
+    v.t0 = ps.t0, v.s0 = ps.s0, v.Tn = ps.Tn;
+    v.phase_inc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    v.phase += r * a.TR * a.HP;
+    v.outphase += r * a.TR * a.HP;
+    v.st_pp += r * a.hs;
+    v.st_po += r * a.hs;
+    if (i < a.hs) prop_role(v, blockIdx.y, i);
+}
+
+bool launch_pool_prop(const PropArgs &a, const PoolLaunch &p, hipStream_t st) {
+    hipLaunchKernelGGL(pv_pool_prop_kernel, dim3((a.hs + kPropThreads - 1) / kPropThreads, a.rows, p.nslots),
+                       dim3(kPropThreads), 0, st, a, p);
+    return true;
+}
+
+// fused synthesis + overlap-add: one workgroup per (channel, slot), one run (the slot's few slices)
+// At most twelve waves per workgroup (the batch kernel's sixteen at fft 512 ... 2048): the slot view costs registers,
+// and with 128 VGPRs per lane the fft 2048 variants spilled.  A slot's launch has at most kStreamChunk slices, and the
+// number of waves does not change what the kernel computes (frames are added in slice order whatever the wave count).
+constexpr int pool_chain_max_threads(int NC, int kPlainCore, bool kFast) {
+    return chain_kernel_max_threads(NC, kPlainCore, kFast) < 768 ? chain_kernel_max_threads(NC, kPlainCore, kFast) : 768;
+}
+template <int NC, int kPlainCore, int kRes, bool kFast>
+__global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void pv_pool_synth_chain_kernel(
+    const SynthArgs s, const ChainArgs c, const PoolLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int64_t r = ps.row0;
+    SynthArgs sv = s;
+    sv.t0 = ps.t0, sv.s0 = ps.s0, sv.Tn = ps.Tn;
+    sv.phase_inc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    const int64_t plane = r * s.TR * s.tb.HP;
+    sv.mag += plane;
+    sv.phase += plane;
+    if (sv.outphase) sv.outphase += plane;
+    if (sv.peaks) sv.peaks += r * s.TR * s.PKP;
+    if (sv.npk) sv.npk += r * s.TR;
+    if (sv.modes) sv.modes += r * s.TR;
+    if (sv.rot) sv.rot += r * s.TR * s.PKP;
+    ChainArgs cv = c;
+    cv.Tn = ps.Tn;
+    cv.t0 = ps.t0;
+    cv.slices = reinterpret_cast<const ChainSlice *>(p.desc + ps.cs_off);
+    cv.run_off = reinterpret_cast<const int32_t *>(p.desc + ps.ro_off);
+    cv.wden = reinterpret_cast<const float *>(p.desc + ps.wden_off);
+    cv.wden_hi = cv.wden;
+    cv.st_acc += 2 * r * c.AR; // [slot][2][C][AR]
+    cv.acc_sel = ps.acc_sel;
+    if (kRes) cv.stream += r * ((int64_t)c.smask + 1);
+    cv.out = p.out + ps.out_off;
+    cv.out_stride_row = ps.out_stride_row;
+    pool_synth_chain_role<NC, kPlainCore, kRes, kFast>(sv, cv, blockIdx.x, smem_raw);
+}
+
+template <int NC, int kPlainCore>
+static bool launch_pool_synth_chain_res(const SynthArgs &s, const ChainArgs &c_in, const PoolLaunch &p, hipStream_t st,
+                                        bool launch) {
+    const bool use_fast = kPlainCore >= 0 && c_in.fast;
+    const int kMaxThreads = use_fast ? pool_chain_max_threads(NC, kPlainCore, true) : pool_chain_max_threads(NC, kPlainCore, false);
+    ChainArgs c = c_in;
+    if (64 * c.waves > kMaxThreads) c.waves = kMaxThreads / 64;
+    if (c.waves < 1) return false;
+    const size_t lds = chain_lds_bytes(c, NC);
+    if (!launch) return true;
+    const dim3 grid(c.rows, p.nslots), block(64 * c.waves);
+    static unsigned long long m0 = 0, m1 = 0, f0 = 0, f1 = 0;
+    if constexpr (kPlainCore >= 0) {
+        if (c.fast) {
+            if (!c.resample) {
+                allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 0, true>, f0);
+                hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 0, true>), grid, block, lds, st, s, c, p);
+            } else {
+                allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 1, true>, f1);
+                hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 1, true>), grid, block, lds, st, s, c, p);
+            }
+            return true;
+        }
+    }
+    if (!c.resample) {
+        allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 0, false>, m0);
+        hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 0, false>), grid, block, lds, st, s, c, p);
+    } else {
+        allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 1, false>, m1);
+        hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 1, false>), grid, block, lds, st, s, c, p);
+    }
+    return true;
+}
+
+// the same choice of specialisation as launch_synth_chain
+bool launch_pool_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, hipStream_t st, bool launch) {
+    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
+    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                           !synth_generic_only() && s.coremode == 1;
+    if (s.tb.nc == 256) {
+        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<256, 1>(s, c, p, st, launch);
+        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<256, 0>(s, c, p, st, launch);
+        if (plain) return launch_pool_synth_chain_res<256, 2>(s, c, p, st, launch);
+        return launch_pool_synth_chain_res<256, -1>(s, c, p, st, launch);
+    }
+    if (s.tb.nc == 512) {
+        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<512, 1>(s, c, p, st, launch);
+        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<512, 0>(s, c, p, st, launch);
+        if (plain) return launch_pool_synth_chain_res<512, 2>(s, c, p, st, launch);
+        return launch_pool_synth_chain_res<512, -1>(s, c, p, st, launch);
+    }
+    if (s.tb.nc == 1024) {
+        if (fc_locked) return launch_pool_synth_chain_res<1024, 3>(s, c, p, st, launch);
+        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<1024, 1>(s, c, p, st, launch);
+        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<1024, 0>(s, c, p, st, launch);
+        if (plain) return launch_pool_synth_chain_res<1024, 2>(s, c, p, st, launch);
+        return launch_pool_synth_chain_res<1024, -1>(s, c, p, st, launch);
+    }
+    if (s.tb.nc == 2048) {
+        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<2048, 1>(s, c, p, st, launch);
+        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<2048, 0>(s, c, p, st, launch);
+        if (plain) return launch_pool_synth_chain_res<2048, 2>(s, c, p, st, launch);
+        return launch_pool_synth_chain_res<2048, -1>(s, c, p, st, launch);
+    }
+    return false;
+}
+
+// resampling: grid (tiles, row groups, slots)
+__device__ __forceinline__ bool pool_res_view(const ResArgs &a, const PoolLaunch &p, ResArgs &v) {
+    const PoolSlot ps = p.slots[blockIdx.z];
+    if ((int)blockIdx.x >= ps.res_ntiles) return false;
+    v = a;
+    v.ntiles = ps.res_ntiles;
+    v.stream += (int64_t)ps.row0 * ((int64_t)a.smask + 1);
+    v.tiles = reinterpret_cast<const ResTile *>(p.desc + ps.res_off);
+    v.otab = reinterpret_cast<const uint2 *>(p.desc + ps.otab_off);
+    v.out = p.out + ps.out_off;
+    v.out_stride_row = ps.out_stride_row;
+    v.k_base = ps.k_base;
+    return true;
+}
+template <int kRes> __global__ __launch_bounds__(kTileOut) void pv_pool_resample_kernel(const ResArgs a, const PoolLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    ResArgs v;
+    if (!pool_res_view(a, p, v)) return;
+    pool_resample_role<kRes>(v, blockIdx.x, blockIdx.y, smem_raw);
+}
+constexpr int kPoolResFastRows = 8;
+template <int kRes> __global__ __launch_bounds__(kTileOut) void pv_pool_resample_fast_kernel(const ResArgs a, const PoolLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    ResArgs v;
+    if (!pool_res_view(a, p, v)) return;
+    pool_resample_fast_role<kRes, kPoolResFastRows>(v, blockIdx.x, blockIdx.y, smem_raw);
+}
+
+bool launch_pool_resample(const ResArgs &a, const PoolLaunch &p, hipStream_t st, bool launch) {
+    const int NR = a.fast ? kPoolResFastRows : kResRows;
+    const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
+    if (lds > 160 * 1024 - 512) return false;
+    if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
+    const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
+    static unsigned long long m1 = 0, m2 = 0, f1 = 0, f2 = 0;
+    if (a.fast) {
+        if (a.interp) {
+            allow_big_lds_dev(pv_pool_resample_fast_kernel<2>, f2);
+            hipLaunchKernelGGL(pv_pool_resample_fast_kernel<2>, grid, dim3(kTileOut), lds, st, a, p);
+        } else {
+            allow_big_lds_dev(pv_pool_resample_fast_kernel<1>, f1);
+            hipLaunchKernelGGL(pv_pool_resample_fast_kernel<1>, grid, dim3(kTileOut), lds, st, a, p);
+        }
+    } else if (a.interp) {
+        allow_big_lds_dev(pv_pool_resample_kernel<2>, m2);
+        hipLaunchKernelGGL(pv_pool_resample_kernel<2>, grid, dim3(kTileOut), lds, st, a, p);
+    } else {
+        allow_big_lds_dev(pv_pool_resample_kernel<1>, m1);
+        hipLaunchKernelGGL(pv_pool_resample_kernel<1>, grid, dim3(kTileOut), lds, st, a, p);
+    }
+    return true;
+}
+
 } // namespace pv

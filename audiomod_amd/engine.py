@@ -7,7 +7,8 @@ package: if the library is missing or no MI355X is visible, construction fails l
 `PhaseVocoder` keeps the method names and call semantics of audiomod::phasevocoder
 (reference include/dafx/phasevocoder.h:42-117, src/phasevocoder/phasevocoder.cc:87-183) so the
 parity tests read like drives of the reference class.  `Batch` is the device-resident throughput
-path (many independent streams), used by bench.py.
+path (many independent streams), used by bench.py.  `StreamPool` serves many live streams, each with the
+semantics of a `PhaseVocoder`, with one launch sequence per call for all of them.
 """
 import ctypes as C
 import os
@@ -116,6 +117,19 @@ def lib():
     L.pv_host_alloc.argtypes = [C.c_size_t]
     L.pv_host_alloc.restype = C.c_void_p
     L.pv_host_free.argtypes = [C.c_void_p]
+    L.pv_pool_create.argtypes = [C.POINTER(Config), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]
+    L.pv_pool_destroy.argtypes = [C.c_void_p]
+    L.pv_pool_capacity.argtypes = [C.c_void_p]
+    L.pv_pool_capacity.restype = C.c_int32
+    L.pv_pool_open.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.pv_pool_close.argtypes = [C.c_void_p, C.c_int32]
+    L.pv_pool_feed.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, fpp, C.c_void_p]
+    L.pv_pool_available.argtypes = [C.c_void_p, C.c_int32]
+    L.pv_pool_available.restype = C.c_int32
+    L.pv_pool_retrieve.argtypes = [C.c_void_p, C.c_int32, fpp, C.c_int32]
+    L.pv_pool_retrieve.restype = C.c_int32
+    L.pv_pool_get_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Info)]
+    L.pv_pool_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -414,3 +428,70 @@ class HostIO:
 
     def __del__(self):
         self.close()
+
+
+class StreamPool:
+    """Up to `capacity` independent live streams of one configuration (include/audiomod_pv.h pv_pool_*).  A slot
+    behaves bit for bit like a PhaseVocoder / pv_engine of the same configuration fed the same blocks; one feed()
+    serves any subset of the open slots with one launch sequence.  One host thread per pool."""
+
+    def __init__(self, capacity, channels=2, device=0, **config):
+        self.L = lib()
+        self.cfg = make_config(channels, **config)
+        self.channels = channels
+        self.h = C.c_void_p()
+        _check(self.L.pv_pool_create(C.byref(self.cfg), int(capacity), device, C.byref(self.h)), "pv_pool_create")
+        self.capacity = self.L.pv_pool_capacity(self.h)
+
+    def close_pool(self):
+        if getattr(self, "h", None):
+            self.L.pv_pool_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close_pool()
+
+    def open(self):
+        """A fresh stream in the lowest free slot; returns the slot."""
+        s = C.c_int32(-1)
+        _check(self.L.pv_pool_open(self.h, C.byref(s)), "pv_pool_open")
+        return s.value
+
+    def close(self, slot):
+        """Frees the slot; its pending output is discarded."""
+        _check(self.L.pv_pool_close(self.h, int(slot)), "pv_pool_close")
+
+    def feed(self, blocks):
+        """blocks: {slot: float32 array [channels, n]} (n may differ per slot, and be 0)."""
+        slots = np.array(list(blocks.keys()), np.int32)
+        arrs = [np.ascontiguousarray(blocks[int(s)], dtype=np.float32) for s in slots]
+        for a in arrs:
+            assert a.ndim == 2 and a.shape[0] == self.channels
+        n = np.array([a.shape[1] for a in arrs], np.int32)
+        rows = [a[c] for a in arrs for c in range(self.channels)]
+        _check(self.L.pv_pool_feed(self.h, len(slots), slots.ctypes.data, _pp(rows) if rows else None,
+                                   n.ctypes.data), "pv_pool_feed")
+
+    def available(self, slot):
+        return self.L.pv_pool_available(self.h, int(slot))
+
+    def retrieve(self, slot, n):
+        """Up to n frames of the slot's output, float32 [channels, got]."""
+        out = np.zeros((self.channels, max(int(n), 1)), np.float32)
+        got = 0
+        if n > 0:
+            got = self.L.pv_pool_retrieve(self.h, int(slot), _pp([out[c] for c in range(self.channels)]), int(n))
+            if got < 0:
+                raise PvError(f"pv_pool_retrieve: slot {slot} is not open")
+        return out[:, :got]
+
+    def info(self, slot):
+        i = Info()
+        _check(self.L.pv_pool_get_info(self.h, int(slot), C.byref(i)), "pv_pool_get_info")
+        return i.as_dict()
+
+    def last_timing(self):
+        """(host_us, wait_us) of the last feed(): host work up to the wait for the device, and that wait."""
+        h, w = C.c_double(), C.c_double()
+        _check(self.L.pv_pool_last_timing(self.h, C.byref(h), C.byref(w)), "pv_pool_last_timing")
+        return h.value, w.value

@@ -147,6 +147,36 @@ int32_t pv_retrieve(pv_engine *e, float *const *out, int32_t n);
 int pv_get_info(const pv_engine *e, pv_info *info);
 
 /* ----------------------------------------------------------------------------------------------
+ * Stream pool: up to `capacity` independent LIVE streams of one configuration on one device, each
+ * with the semantics of a pv_engine (same cfg, same pv_set_arithmetic setting when the pool is
+ * created): fed the same blocks and retrieved between calls, a slot returns bit for bit what that
+ * engine returns -- every available / retrieve value, every sample, the reference's slice dropping
+ * when output piles up included.  One pv_pool_feed serves many slots with ONE launch sequence.
+ *   pv_pool_open   : a fresh stream in the lowest free slot (PV_ERR_INVALID_ARG when all are open)
+ *   pv_pool_close  : discards the slot's pending output; the slot becomes free
+ *   pv_pool_feed   : slots[i] (distinct open slots) gets n[i] >= 0 frames; in[i*C + c] holds channel
+ *                    c of slots[i].  Synchronous.  All or nothing: a call that any slot's planner
+ *                    refuses changes no slot (pv_last_error() names the slot).
+ * Scope: modes NORMAL_SHIFT, GENDER_CHANGE, FORMANT_PRESERVE, NORMAL_STRETCH, ROBOTIC; coremodes
+ * 0-2; fftsize 512 ... 4096.  Anything else returns PV_ERR_UNSUPPORTED from pv_pool_create;
+ * capacity < 1 or capacity x channels > 65535 returns PV_ERR_INVALID_ARG (both checked before any
+ * device call).  One host thread per pool.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct pv_pool pv_pool;
+int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool **out);
+void pv_pool_destroy(pv_pool *p);
+int32_t pv_pool_capacity(const pv_pool *p);
+int pv_pool_open(pv_pool *p, int32_t *slot);
+int pv_pool_close(pv_pool *p, int32_t slot);
+int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *const *in, const int32_t *n);
+int32_t pv_pool_available(const pv_pool *p, int32_t slot);   /* -1: not an open slot */
+int32_t pv_pool_retrieve(pv_pool *p, int32_t slot, float *const *out, int32_t n); /* frames copied, -1: bad slot */
+int pv_pool_get_info(const pv_pool *p, int32_t slot, pv_info *info);
+/* Diagnostics: wall-clock time of the last pv_pool_feed, split into the host's share up to the wait (planning,
+ * descriptors, staging, enqueueing the launches) and the wait for the device. */
+int pv_pool_last_timing(const pv_pool *p, double *host_us, double *wait_us);
+
+/* ----------------------------------------------------------------------------------------------
  * Batch engine: `nstreams` independent streams of identical configuration and length, input and
  * output resident in device memory (HBM).  Equivalent, per stream, to driving the reference CLI
  * loop (main/main.cc:471-510) with `block`-frame calls: flush != 0 -> feed zeros until `frames`
