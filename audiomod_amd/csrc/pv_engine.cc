@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <deque>
@@ -347,15 +348,17 @@ struct Core {
     // ... whatever the path: with PV_ARITH_FAST such a configuration ALWAYS takes the fused path (init), so that what
     // an engine computes does not depend on how many rows it was created for -- a batch, its host-staged groups and
     // the single-stream engine run the same kernels and agree bit for bit, as they do under PV_ARITH_EXACT
-    bool fast_capable() const {
-        if (!(fast_arith && wave_fft())) return false;
+    bool fast_capable() const { return fast_capable_of(d, fast_arith); }
+    // ... for any derived constants (the stream pool asks it per slot)
+    static bool fast_capable_of(const Derived &d, bool fast_arith) {
+        if (!(fast_arith && (d.fft.nc == 256 || d.fft.nc == 512 || d.fft.nc == 1024 || d.fft.nc == 2048))) return false;
         SynthArgs sa{};
         sa.tb.nc = d.fft.nc;
         sa.do_freq_comp = d.do_freq_comp ? 1 : 0;
         sa.voc_band_len = d.vocoder ? d.voc_band_len : -1;
         sa.robotic = d.robotic ? 1 : 0;
         sa.passthru = d.constant ? 1 : 0;
-        sa.whisper = d.whisper ? reinterpret_cast<const float *>(this) : nullptr; // (only tested against null)
+        sa.whisper = d.whisper ? reinterpret_cast<const float *>(&d) : nullptr; // (only tested against null)
         const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
         sa.coremode = bypass ? 0 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
         return synth_chain_has_fast(sa);
@@ -776,7 +779,12 @@ int Core::build_tiles(const std::vector<SliceRec> &slices, int64_t t_base, int64
     return PV_OK;
 }
 
+// (the stream pool calls it with each slot's own constants)
+static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab);
 void Core::build_res_tiles(int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab) const {
+    build_res_tiles_of(d, ka, kb, tiles, otab);
+}
+static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab) {
     for (int64_t k0 = ka; k0 < kb; k0 += kTileOut) {
         ResTile tl{};
         tl.k0 = k0;
@@ -1299,8 +1307,31 @@ struct pv_pool {
         int acc_half = 0; // which accumulator half the slot's next launch reads
         std::vector<std::vector<float>> outq; // per channel FIFO
         size_t outq_head = 0;
+        // the slot's derived constants: the pool's (core.d) in a uniform pool, its own in a mixed one (own_d, which
+        // planner and chain reference); fast: the slot's engine would take the PV_ARITH_FAST kernels
+        const Derived *d = nullptr;
+        std::unique_ptr<Derived> own_d;
+        bool fast = false;
+        int tab = -1;              // mixed pool, resampling slot: its entry of the table arena
+        int lds_floats = 0, tab_bytes = 0; // ... and its resampling kernel's LDS layout
     };
     std::vector<Slot> slots;
+    // Mixed pool (pv_pool_create_mixed): the range a slot's pitch / time ratio may take, and what the buffers were sized
+    // for (checked again for every slot at open)
+    bool mixed = false;
+    pv_pool_range range{};
+    int max_hop = 0, max_res_lds_floats = 0, max_res_tab_bytes = 0, max_sinc = 0, max_tab4 = 0;
+    DevBuf<float> mix_stream; // the overlap-add stream rings when cfg itself does not resample
+    // Table arena: entry i holds one resampling ratio's Speex table (max_sinc floats) and expanded interpolation rows
+    // (max_tab4 float4), uploaded at the open that first needs the ratio and shared by every open slot with that ratio
+    struct Tab {
+        uint32_t num = 0, den = 0;
+        int refs = 0;
+    };
+    std::vector<Tab> tabs;
+    DevBuf<float4> d_tabs; // [capacity][tab_stride]
+    size_t tab_stride = 0; // float4 per entry
+    int last_launches = 0; // kernels launched by the last pv_pool_feed
     DevBuf<float> d_in, d_stage; // device input rings [capacity * C][ring]; a call's packed new samples
     PinBuf<float> h_stage;
     const float *stage_src = nullptr; // what the ingest kernel reads: d_stage (or h_stage mapped, PV_POOL_MAPPED_INGEST)
@@ -2152,7 +2183,89 @@ static bool pool_slot_ok(const pv_pool *p, int32_t slot) {
 
 static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true);
 
-int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool **out) {
+// the chain kernel's largest overlap-add advance for one set of derived constants (as Core::init computes it)
+static int pool_max_adv(const Derived &d) {
+    const bool fixed_shift = d.robotic || d.whisper || d.constant || d.vocoder;
+    const double m = fixed_shift ? (double)d.hop : (d.int_ratio ? (double)d.hop * d.hs_ratio : 2.0 * d.hop * d.hs_ratio + 1);
+    return (int)(m < d.N ? m + 1 : d.N);
+}
+// LDS layout of the resampling kernel for one set of derived constants (as Core::init and pool_launch_group lay it out)
+static int pool_res_lds_floats(const Derived &d) {
+    const double step = (double)d.res_num / (double)d.res_den;
+    const int tile_span = (int)(kTileOut * step) + d.filt_len + 4;
+    return (tile_span + 4 + 3) & ~3;
+}
+static int pool_res_tab_bytes(const Derived &d) {
+    return d.interp ? d.oversample * (d.filt_len + 1) * 16 : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
+}
+static bool pool_in_range(const pv_pool_range &r, float time_ratio, float semis) {
+    return semis >= r.min_semitones && semis <= r.max_semitones && time_ratio >= r.min_time_ratio &&
+           time_ratio <= r.max_time_ratio; // (false for a NaN)
+}
+
+// What a mixed pool's buffers must hold: the largest hop, overlap-add advance and resampler set-up any slot of the
+// range can have.  The hops are not monotonic (derive: input hop N/4.5 or N/6 below hs_ratio 1, N/4 at 1, N/8/hs_ratio
+// above), and resampling stops at 0 st, so the constants are taken at both ends of each parameter, at 0 st, at
+// hs_ratio 1, and on both sides of those breakpoints; within a side of a breakpoint each is monotonic.  The resampler's
+// table sizes grow with its input step, which is largest at the highest pitch; they get a margin (the Speex rate pair only
+// approximates the ratio), and pv_pool_open_with checks every slot against all of them again.
+struct PoolSizing {
+    int max_hop = 0, max_adv = 0;
+    bool any_resample = false;
+    int res_lds_floats = 0, res_tab_bytes = 0, sinc = 0, tab4 = 0;
+};
+static void pool_size_range(const pv_config &cfg, const pv_pool_range &r, PoolSizing &z) {
+    std::vector<float> ts = {r.min_time_ratio, r.max_time_ratio, cfg.time_ratio};
+    std::vector<float> ss = {r.min_semitones, r.max_semitones, cfg.pitch_semitones};
+    if (r.min_semitones <= 0 && 0 <= r.max_semitones)
+        ss.insert(ss.end(), {0.f, std::nextafter(0.f, -1.f), std::nextafter(0.f, 1.f), -1e-3f, 1e-3f});
+    if (r.min_time_ratio <= 1 && 1 <= r.max_time_ratio) ts.push_back(1.f);
+    std::vector<std::pair<float, float>> pts;
+    for (float t : ts)
+        for (float s : ss) pts.emplace_back(t, s);
+    for (float t : ts) // hs_ratio 1 and either side of it, along each time ratio
+        if (t > 0) {
+            const float s1 = (float)(-12.0 * std::log2((double)t));
+            for (float s : {s1, std::nextafter(s1, -1e9f), std::nextafter(s1, 1e9f), s1 - 1e-3f, s1 + 1e-3f}) pts.emplace_back(t, s);
+        }
+    for (float s : ss) { // ... and along each pitch
+        const float t1 = (float)std::pow(2.0, -s / 12.0);
+        for (float t : {t1, std::nextafter(t1, 0.f), std::nextafter(t1, 1e9f), t1 * 0.999f, t1 * 1.001f}) pts.emplace_back(t, s);
+    }
+    double step_max = 0;
+    for (const auto &pt : pts) {
+        Derived d;
+        pv_config c = cfg;
+        // (points just outside the range only ever bound it from above: the constants are monotonic between breakpoints)
+        c.time_ratio = pt.first, c.pitch_semitones = pt.second;
+        if (derive(c, d) != PV_OK) continue;
+        if (d.hop > z.max_hop) z.max_hop = d.hop;
+        int adv = pool_max_adv(d);
+        // below hs_ratio 1 the input hop is constant and the advance grows towards hs_ratio 1: bound it there
+        if (d.hs_ratio < 1 && !(d.robotic || d.whisper || d.constant || d.vocoder)) {
+            const int up = (int)(2.0 * d.hop + 2 < d.N ? 2.0 * d.hop + 2 : d.N);
+            if (up > adv) adv = up;
+        }
+        if (adv > z.max_adv) z.max_adv = adv;
+        if (d.resample) {
+            z.any_resample = true;
+            const double step = (double)d.res_num / (double)d.res_den;
+            if (step > step_max) step_max = step;
+            if (pool_res_lds_floats(d) > z.res_lds_floats) z.res_lds_floats = pool_res_lds_floats(d);
+            if (pool_res_tab_bytes(d) > z.res_tab_bytes) z.res_tab_bytes = pool_res_tab_bytes(d);
+        }
+    }
+    if (z.any_resample) {
+        const double step = step_max * 1.001;
+        const int fl = std::max(64, (int)std::ceil(64 * step) + 4); // Speex taps (resample.c:687), with margin
+        z.sinc = 8 * fl + 8;                                        // oversample <= 8: direct den * taps, or ov * taps + 8
+        z.tab4 = 8 * (fl + 1);
+        z.res_tab_bytes = std::max(z.res_tab_bytes, 16 * z.tab4);
+        z.res_lds_floats = std::max(z.res_lds_floats, (((int)(kTileOut * step) + fl + 4 + 4 + 3) & ~3) + 4);
+    }
+}
+
+static int pool_create(const pv_config *cfg, const pv_pool_range *range, int32_t capacity, int device, pv_pool **out) {
     g_last_error.clear();
     plan_reason_clear();
     if (!cfg || !out) return PV_ERR_INVALID_ARG;
@@ -2161,8 +2274,22 @@ int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool *
         g_last_error = "stream pool: capacity must be at least 1";
         return PV_ERR_INVALID_ARG;
     }
-    // the configuration is checked before any device call (as Core::init does)
+    PoolSizing z;
+    // the configuration (and a mixed pool's range) is checked before any device call (as Core::init does)
     {
+        if (range) {
+            const float v[4] = {range->min_semitones, range->max_semitones, range->min_time_ratio, range->max_time_ratio};
+            const char *bad = nullptr;
+            for (float x : v)
+                if (!std::isfinite(x)) bad = "a bound is not a finite number";
+            if (!bad && (v[0] > v[1] || v[2] > v[3])) bad = "a minimum is above its maximum";
+            if (!bad && !pool_in_range(*range, cfg->time_ratio, cfg->pitch_semitones))
+                bad = "the configuration's own pitch / time ratio lies outside the range";
+            if (bad) {
+                g_last_error = std::string("stream pool range: ") + bad;
+                return PV_ERR_INVALID_ARG;
+            }
+        }
         Derived d;
         const int st = derive(*cfg, d);
         if (st != PV_OK) return st;
@@ -2174,11 +2301,39 @@ int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool *
             g_last_error = why;
             return PV_ERR_UNSUPPORTED;
         }
+        if (range) {
+            // the range's worst case against every per-slot kernel's limits
+            pool_size_range(*cfg, *range, z);
+            const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
+            const int PKP = ((d.hs / 3 + 2) + 7) & ~7; // (as Core::init)
+            if (!bypass && cfg->coremode == 1 && !pool_phase_supported(d.hs, PKP)) {
+                g_last_error = "stream pool range: the per-slot phase kernel (match + rotation chain) does not fit one workgroup";
+                return PV_ERR_UNSUPPORTED;
+            }
+            ChainArgs probe{};
+            probe.AR = d.N + 4;
+            probe.waves = 1;
+            if (chain_lds_bytes(probe, d.fft.nc) > 160 * 1024 - 512) {
+                g_last_error = "stream pool range: the per-slot synthesis + overlap-add kernel does not fit the LDS";
+                return PV_ERR_UNSUPPORTED;
+            }
+            const int NR = g_arith == PV_ARITH_FAST ? 8 : 4; // rows per workgroup of the resampling kernels
+            if (z.any_resample && (size_t)z.res_tab_bytes + sizeof(float) * (size_t)z.res_lds_floats * NR > 160 * 1024 - 512) {
+                g_last_error = "stream pool range: the per-slot resampling kernel's filter table and tile do not fit the "
+                               "LDS at the range's highest pitch";
+                return PV_ERR_UNSUPPORTED;
+            }
+            if (z.max_hop < 1 || z.max_adv < 1) {
+                g_last_error = "stream pool range: no value of the range is a valid configuration";
+                return PV_ERR_INVALID_ARG;
+            }
+        }
     }
     std::unique_ptr<pv_pool> p(new pv_pool());
     Core &c = p->core;
     c.chain_required = true;
     c.fast_arith = g_arith == PV_ARITH_FAST;
+    if (range) c.chain_max_adv = z.max_adv; // (sizes the stream ring for every slot)
     int st = c.init(*cfg, device, capacity, kStreamChunk);
     if (st != PV_OK) return st;
     const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
@@ -2196,7 +2351,8 @@ int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool *
         if ((st = pool_launch_group(p.get(), probe, false)) != PV_OK) return st; // (launches nothing)
     }
     HIPC(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    p->ring = next_pow2_i(3 * c.d.N + kStreamChunk * c.d.hop + 16); // (as pv_create)
+    p->max_hop = range ? std::max(z.max_hop, c.d.hop) : c.d.hop;
+    p->ring = next_pow2_i(3 * c.d.N + kStreamChunk * p->max_hop + 16); // (as pv_create)
     if ((st = p->d_in.alloc((size_t)c.rows * p->ring)) != PV_OK) return st;
     HIPC(hipMemset(p->d_in.p, 0, p->d_in.n * sizeof(float)));
     if ((st = p->h_flag.alloc(16)) != PV_OK) return st;
@@ -2210,9 +2366,39 @@ int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool *
         HIPC(hipHostGetDevicePointer(&fp, p->h_flag.p, 0));
         p->flag_dev = static_cast<uint32_t *>(fp);
     }
+    if (range) {
+        p->mixed = true;
+        p->range = *range;
+        if (z.any_resample) {
+            p->max_res_lds_floats = z.res_lds_floats;
+            p->max_res_tab_bytes = z.res_tab_bytes;
+            p->max_sinc = z.sinc;
+            p->max_tab4 = z.tab4;
+            p->tab_stride = (size_t)(z.sinc + 3) / 4 + (size_t)z.tab4;
+            if ((st = p->d_tabs.alloc((size_t)capacity * p->tab_stride)) != PV_OK) return st;
+            p->tabs.assign((size_t)capacity, pv_pool::Tab());
+            if (!c.stream.p)
+                if ((st = p->mix_stream.alloc((size_t)c.rows * ((size_t)c.chain_smask + 1))) != PV_OK) return st;
+        }
+    } else {
+        p->range = pv_pool_range{cfg->pitch_semitones, cfg->pitch_semitones, cfg->time_ratio, cfg->time_ratio};
+    }
     p->slots.resize((size_t)capacity);
     *out = p.release();
     return PV_OK;
+}
+
+int pv_pool_create(const pv_config *cfg, int32_t capacity, int device, pv_pool **out) {
+    return pool_create(cfg, nullptr, capacity, device, out);
+}
+
+int pv_pool_create_mixed(const pv_config *cfg, const pv_pool_range *range, int32_t capacity, int device, pv_pool **out) {
+    if (!range) {
+        g_last_error = "stream pool: no range";
+        if (out) *out = nullptr;
+        return PV_ERR_INVALID_ARG;
+    }
+    return pool_create(cfg, range, capacity, device, out);
 }
 
 void pv_pool_destroy(pv_pool *p) { delete p; }
@@ -2224,15 +2410,31 @@ int pv_pool_last_timing(const pv_pool *p, double *host_us, double *wait_us) {
     return PV_OK;
 }
 
+int pv_pool_last_launches(const pv_pool *p, int32_t *launches) {
+    if (!p || !launches) return PV_ERR_INVALID_ARG;
+    *launches = p->last_launches;
+    return PV_OK;
+}
+
 int32_t pv_pool_capacity(const pv_pool *p) { return p ? p->cap : -1; }
 
-int pv_pool_open(pv_pool *p, int32_t *slot) {
+static void pool_release_tab(pv_pool *p, pv_pool::Slot &sl) {
+    if (sl.tab >= 0) --p->tabs[(size_t)sl.tab].refs;
+    sl.tab = -1;
+}
+
+static int pool_open_at(pv_pool *p, float time_ratio, float semis, int32_t *slot) {
     g_last_error.clear();
     plan_reason_clear();
     if (!p || !slot) return PV_ERR_INVALID_ARG;
     if (p->poisoned) {
         g_last_error = "pool unusable after an earlier failure: " + p->poison_reason;
         return p->poisoned;
+    }
+    if (!pool_in_range(p->range, time_ratio, semis)) {
+        g_last_error = p->mixed ? "stream pool: pitch / time ratio outside the pool's range"
+                                : "stream pool: a pool from pv_pool_create takes only its configuration's pitch / time ratio";
+        return PV_ERR_INVALID_ARG;
     }
     int32_t s = 0;
     while (s < p->cap && p->slots[(size_t)s].open) ++s;
@@ -2241,6 +2443,53 @@ int pv_pool_open(pv_pool *p, int32_t *slot) {
         return PV_ERR_INVALID_ARG;
     }
     Core &c = p->core;
+    // a mixed pool's slot: its own constants, checked against what the pool was sized for (nothing changes on refusal)
+    std::unique_ptr<Derived> own;
+    int tab = -1;
+    if (p->mixed) {
+        own.reset(new Derived());
+        pv_config cs = c.d.cfg;
+        cs.time_ratio = time_ratio;
+        cs.pitch_semitones = semis;
+        const int st = derive(cs, *own);
+        if (st != PV_OK) {
+            if (g_last_error.empty()) g_last_error = "stream pool: the engine refuses this pitch / time ratio";
+            return st;
+        }
+        const Derived &d = *own;
+        const char *big = d.hop > p->max_hop ? "input hop" : pool_max_adv(d) > c.chain_max_adv ? "overlap-add advance" : nullptr;
+        if (!big && d.resample &&
+            (pool_res_lds_floats(d) > p->max_res_lds_floats || pool_res_tab_bytes(d) > p->max_res_tab_bytes ||
+             (int)d.sinc.size() > p->max_sinc || (d.interp && d.oversample * (d.filt_len + 1) > p->max_tab4)))
+            big = "resampler set-up";
+        if (big) {
+            g_last_error = std::string("stream pool: this pitch / time ratio's ") + big + " exceeds what the pool was sized for";
+            return PV_ERR_UNSUPPORTED;
+        }
+        if (d.resample) { // the ratio's tables: shared with an open slot of the same ratio, or uploaded into a free entry
+            for (size_t i = 0; i < p->tabs.size() && tab < 0; ++i)
+                if (p->tabs[i].refs > 0 && p->tabs[i].num == d.res_num && p->tabs[i].den == d.res_den) tab = (int)i;
+            if (tab < 0) {
+                for (size_t i = 0; i < p->tabs.size() && tab < 0; ++i)
+                    if (p->tabs[i].refs == 0) tab = (int)i;
+                // (at most one entry per open slot: a free one exists)
+                std::vector<float4> img(p->tab_stride, make_float4(0, 0, 0, 0));
+                memcpy(img.data(), d.sinc.data(), d.sinc.size() * sizeof(float));
+                float4 *t4 = img.data() + (size_t)(p->max_sinc + 3) / 4;
+                if (d.interp) // (as Core::init expands them)
+                    for (int off = 0; off < d.oversample; ++off)
+                        for (int j = 0; j < d.filt_len; ++j) {
+                            const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
+                            t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+                        }
+                HIPC(hipSetDevice(c.device));
+                HIPC(hipMemcpy(p->d_tabs.p + (size_t)tab * p->tab_stride, img.data(), img.size() * sizeof(float4),
+                               hipMemcpyHostToDevice));
+                p->tabs[(size_t)tab].num = d.res_num;
+                p->tabs[(size_t)tab].den = d.res_den;
+            }
+        }
+    }
     HIPC(hipSetDevice(c.device));
     // a fresh stream: what pv_create and Core::reset_state zero, for the slot's rows only (stream-ordered before its
     // first launch)
@@ -2262,8 +2511,15 @@ int pv_pool_open(pv_pool *p, int32_t *slot) {
         return st;
     }
     pv_pool::Slot &sl = p->slots[(size_t)s];
-    sl.planner.reset(new Planner(c.d));
-    sl.chain.reset(new ChainBuilder(c.d, c.chain_AR, c.chain_smask));
+    sl.own_d = std::move(own);
+    sl.d = sl.own_d ? sl.own_d.get() : &c.d;
+    sl.fast = Core::fast_capable_of(*sl.d, c.fast_arith);
+    sl.tab = tab;
+    if (tab >= 0) ++p->tabs[(size_t)tab].refs;
+    sl.lds_floats = sl.d->resample ? pool_res_lds_floats(*sl.d) : 0;
+    sl.tab_bytes = sl.d->resample ? pool_res_tab_bytes(*sl.d) : 0;
+    sl.planner.reset(new Planner(*sl.d));
+    sl.chain.reset(new ChainBuilder(*sl.d, c.chain_AR, c.chain_smask));
     sl.fed = sl.uploaded = sl.slices = 0;
     sl.acc_half = 0;
     sl.outq.assign((size_t)c.C, std::vector<float>());
@@ -2271,6 +2527,15 @@ int pv_pool_open(pv_pool *p, int32_t *slot) {
     sl.open = true;
     *slot = s;
     return PV_OK;
+}
+
+int pv_pool_open(pv_pool *p, int32_t *slot) {
+    if (!p) return PV_ERR_INVALID_ARG;
+    return pool_open_at(p, p->core.d.cfg.time_ratio, p->core.d.cfg.pitch_semitones, slot);
+}
+
+int pv_pool_open_with(pv_pool *p, float time_ratio, float pitch_semitones, int32_t *slot) {
+    return pool_open_at(p, time_ratio, pitch_semitones, slot);
 }
 
 int pv_pool_close(pv_pool *p, int32_t slot) {
@@ -2283,6 +2548,9 @@ int pv_pool_close(pv_pool *p, int32_t slot) {
     sl.open = false;
     sl.planner.reset();
     sl.chain.reset();
+    pool_release_tab(p, sl);
+    sl.own_d.reset();
+    sl.d = nullptr;
     sl.outq.clear();
     sl.outq_head = 0;
     return PV_OK;
@@ -2294,7 +2562,7 @@ int32_t pv_pool_available(const pv_pool *p, int32_t slot) {
 
 int pv_pool_get_info(const pv_pool *p, int32_t slot, pv_info *info) {
     if (!pool_slot_ok(p, slot) || !info) return PV_ERR_INVALID_ARG;
-    fill_info(p->core.d, p->slots[(size_t)slot].planner->slices(), info);
+    fill_info(*p->slots[(size_t)slot].d, p->slots[(size_t)slot].planner->slices(), info);
     return PV_OK;
 }
 
@@ -2426,6 +2694,138 @@ static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch
     return PV_OK;
 }
 
+// A mixed pool's launch group: the slots of the table are ordered by kernel variant (VariantRun: contiguous entries of
+// one variant).  Analysis and the phase stage serve every slot in one launch each; the fused synthesis + overlap-add
+// is launched once per (frequency compensation, resampling, fast) present, the resampling once per (fast, interp)
+// present within it.  Returns the number of kernels launched in *nlaunch.
+struct VariantRun {
+    int first, count;
+    int dfc, res, fast, interp;
+    int max_tiles, lds_floats, tab_bytes;
+};
+static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const PoolParams *q,
+                                 const std::vector<VariantRun> &runs, int *nlaunch) {
+    const Core &c = p->core;
+    const Derived &d = c.d; // (only what every slot shares: sizes, mode, coremode)
+    hipStream_t st = p->stream;
+    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
+    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    auto refused = [](const char *what) {
+        g_last_error = std::string("stream pool: no per-slot ") + what + " kernel for this configuration";
+        return PV_ERR_UNSUPPORTED;
+    };
+    auto launched = [nlaunch](const char *what) -> int {
+        ++*nlaunch;
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
+    };
+    int rc;
+    AnalyzeArgs aa{};
+    aa.tb = c.tb;
+    aa.ia.in = p->d_in.p;
+    aa.ia.stride_c = p->ring;
+    aa.ia.stride_s = (int64_t)p->ring * c.C;
+    aa.ia.mask = (uint64_t)(p->ring - 1);
+    aa.ia.len = INT64_MAX;
+    aa.hop = d.hop; // (per slot: PoolParams)
+    aa.TR = c.TR;
+    aa.rows = c.C;
+    aa.PKP = c.PKP;
+    aa.find_peaks = cm == 1 ? 1 : 0;
+    aa.split = c.split_analysis ? 1 : 0;
+    aa.mag = c.mag.p;
+    aa.phase = c.phase.p;
+    aa.peaks = c.peaks.p;
+    aa.npk = c.npk.p;
+    if (!launch_pmix_analyze(aa, pl, q, st)) return refused("analysis");
+    if ((rc = launched("pool analysis launch")) != PV_OK) return rc;
+    if (cm == 1) {
+        MatchArgs ma{};
+        ma.N = d.N, ma.hs = d.hs, ma.HP = c.HP, ma.PKP = c.PKP, ma.C = c.C, ma.hop = d.hop, ma.TR = c.TR, ma.rows = c.C;
+        ma.two_pi_hop = d.two_pi_hop;
+        ma.phase = c.phase.p, ma.peaks = c.peaks.p, ma.npk = c.npk.p, ma.recs = c.recs.p, ma.modes = c.modes.p;
+        SeqArgs qa{};
+        qa.N = d.N, qa.hs = d.hs, qa.HP = c.HP, qa.PKP = c.PKP, qa.C = c.C, qa.hop = d.hop, qa.TR = c.TR, qa.rows = c.C;
+        qa.two_pi_hop = d.two_pi_hop;
+        qa.phase = c.phase.p, qa.peaks = c.peaks.p, qa.npk = c.npk.p, qa.recs = c.recs.p, qa.modes = c.modes.p;
+        qa.rot = c.rot.p, qa.outphase = c.outphase.p;
+        qa.st_kind = c.st_kind.p, qa.st_rot = c.st_rot.p, qa.st_po = c.st_po.p;
+        qa.high_prio = 1;
+        if (!launch_pmix_phase(ma, qa, pl, q, st)) return refused("phase");
+        if ((rc = launched("pool phase launch")) != PV_OK) return rc;
+    } else if (cm == 0) {
+        PropArgs pa{};
+        pa.N = d.N, pa.hs = d.hs, pa.HP = c.HP, pa.C = c.C, pa.hop = d.hop, pa.TR = c.TR, pa.rows = c.C;
+        pa.two_pi_hop = d.two_pi_hop;
+        pa.phase = c.phase.p, pa.outphase = c.outphase.p, pa.st_pp = c.st_pp.p, pa.st_po = c.st_po.p;
+        if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
+        if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
+    }
+    float *stream = c.stream.p ? c.stream.p : p->mix_stream.p;
+    for (size_t a = 0; a < runs.size();) {
+        // the synthesis variant's runs: consecutive, they differ in interp only
+        size_t b = a + 1;
+        while (b < runs.size() && runs[b].dfc == runs[a].dfc && runs[b].res == runs[a].res && runs[b].fast == runs[a].fast) ++b;
+        const VariantRun &ra0 = runs[a];
+        PoolLaunch sub = pl;
+        sub.slots = pl.slots + ra0.first;
+        sub.nslots = runs[b - 1].first + runs[b - 1].count - ra0.first;
+        SynthArgs sa{};
+        sa.tb = c.tb;
+        sa.hop = d.hop;
+        sa.C = c.C;
+        sa.two_pi_hop = d.two_pi_hop;
+        sa.do_freq_comp = ra0.dfc;
+        sa.freq_comp = 1;
+        sa.fixed_gain = 1;
+        sa.inv_n = d.inv_n;
+        sa.robotic = d.robotic ? 1 : 0;
+        sa.voc_band_len = -1;
+        sa.coremode = cm < 0 ? 0 : cm;
+        sa.TR = c.TR;
+        sa.rows = c.C;
+        sa.PKP = c.PKP;
+        sa.mag = c.mag.p, sa.phase = c.phase.p, sa.outphase = c.outphase.p, sa.peaks = c.peaks.p, sa.npk = c.npk.p;
+        sa.modes = c.modes.p, sa.rot = c.rot.p, sa.frames = c.frames.p, sa.FR = c.FR;
+        ChainArgs ca{};
+        ca.N = d.N;
+        ca.rows = c.C;
+        ca.C = c.C;
+        ca.AR = c.chain_AR;
+        ca.smask = c.chain_smask;
+        ca.waves = c.chain_waves;
+        ca.runs = 1;
+        ca.st_acc = c.st_acc.p;
+        ca.stream = stream;
+        ca.resample = ra0.res;
+        ca.frames = c.frames.p;
+        ca.FR = c.FR;
+        ca.fast = ra0.fast;
+        if (!launch_pmix_synth_chain(sa, ca, sub, q + ra0.first, st)) return refused("synthesis + overlap-add");
+        if ((rc = launched("pool synthesis + overlap-add launch")) != PV_OK) return rc;
+        for (size_t k = a; k < b && ra0.res; ++k) {
+            const VariantRun &rv = runs[k];
+            if (rv.max_tiles <= 0) continue; // (dropped slices only: no output completed)
+            PoolLaunch rs = pl;
+            rs.slots = pl.slots + rv.first;
+            rs.nslots = rv.count;
+            rs.max_tiles = rv.max_tiles;
+            ResArgs ra{};
+            ra.rows = c.C;
+            ra.smask = c.chain_smask;
+            ra.stream = stream;
+            ra.interp = rv.interp;
+            ra.lds_floats = rv.lds_floats; // (the largest of the run's slots; each slot brings its own set-up)
+            ra.tab_bytes = rv.tab_bytes;
+            ra.fast = rv.fast;
+            if (!launch_pmix_resample(ra, rs, q + rv.first, st)) return refused("resampling");
+            if ((rc = launched("pool resampling launch")) != PV_OK) return rc;
+        }
+        a = b;
+    }
+    return PV_OK;
+}
+
 int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *const *in, const int32_t *n) {
     g_last_error.clear();
     plan_reason_clear();
@@ -2454,6 +2854,7 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
             seen[(size_t)s] = 1;
         }
     }
+    p->last_launches = 0;
     if (count == 0) return PV_OK;
     const auto t_call = std::chrono::steady_clock::now();
     // 1. plan every slot; all or nothing
@@ -2542,6 +2943,11 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
     };
     std::vector<Group> grp((size_t)groups + 1); // (+ the final ingest of what the call leaves unconsumed)
     std::vector<PoolSlot> table;
+    // mixed pool: per group its PoolParams table (parallel to the PoolSlot table) and variant runs
+    std::vector<PoolParams> params;
+    std::vector<int64_t> params_off((size_t)groups, 0);
+    std::vector<std::vector<VariantRun>> vruns((size_t)groups);
+    std::vector<int> vkey;
     std::vector<PoolIngest> ingest;
     std::vector<int32_t> pinc;
     std::vector<float> wden, wden_hi;
@@ -2568,6 +2974,8 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
         g = Group{0, 0, 0, 0, 0, 0, 0};
         table.clear();
         ingest.clear();
+        params.clear();
+        vkey.clear();
         for (int32_t i = 0; i < count; ++i) {
             const std::vector<SliceRec> &f = fresh[(size_t)i];
             const int ta = gi * kStreamChunk;
@@ -2575,8 +2983,9 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
             const int tb = (int)f.size() - ta < kStreamChunk ? (int)f.size() : ta + kStreamChunk;
             const int Tn = tb - ta;
             pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+            const Derived &sd = *sl.d;
             const int64_t t0 = sl.slices + ta;
-            int64_t need = (t0 + Tn - 1) * (int64_t)c.d.hop + c.d.N;
+            int64_t need = (t0 + Tn - 1) * (int64_t)sd.hop + sd.N;
             if (need > sl.fed) need = sl.fed;
             add_ingest(i, need, g);
             PoolSlot ps{};
@@ -2599,7 +3008,7 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
             sl.chain->end_launch(1, cs, ro);
             while (wden.size() & 3) wden.push_back(1.f);
             for (int k = 0; k < 4; ++k) wden.push_back(1.f);
-            if (c.fast_chain())
+            if (sl.fast)
                 for (float &v : wden) v = 1.0f / v;
             ps.cs_off = put(cs.data(), cs.size() * sizeof(ChainSlice));
             const int32_t ro4[4] = {0, (int32_t)cs.size(), 0, 0};
@@ -2607,7 +3016,7 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
             ps.wden_off = put(wden.data(), wden.size() * sizeof(float));
             res_tiles.clear();
             res_otab.clear();
-            if (c.d.resample && kb > ka) c.build_res_tiles(ka, kb, res_tiles, res_otab);
+            if (sd.resample && kb > ka) build_res_tiles_of(sd, ka, kb, res_tiles, res_otab);
             ps.res_ntiles = (int32_t)res_tiles.size();
             ps.res_off = put(res_tiles.data(), res_tiles.size() * sizeof(ResTile));
             ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
@@ -2617,6 +3026,52 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
             table.push_back(ps);
             if (Tn > g.max_tn) g.max_tn = Tn;
             if (ps.res_ntiles > g.max_tiles) g.max_tiles = ps.res_ntiles;
+            if (p->mixed) {
+                PoolParams q{};
+                q.two_pi_hop = sd.two_pi_hop;
+                q.hop = sd.hop;
+                q.do_freq_comp = sd.do_freq_comp ? 1 : 0;
+                q.freq_comp = sd.freq_comp;
+                q.fixed_gain = sd.fixed_gain;
+                if (sd.resample) {
+                    q.filt_len = sd.filt_len;
+                    q.oversample = sd.oversample;
+                    q.sinc_len = (int32_t)sd.sinc.size();
+                    q.tab_bytes = sl.tab_bytes;
+                    q.lds_floats = sl.lds_floats;
+                    const float4 *e = p->d_tabs.p + (size_t)sl.tab * p->tab_stride;
+                    q.sinc = reinterpret_cast<const float *>(e);
+                    q.tab4 = e + (size_t)(p->max_sinc + 3) / 4;
+                }
+                params.push_back(q);
+                // the variant: frequency compensation, resampling, fast kernels, interpolated table (sort order)
+                vkey.push_back(((sd.do_freq_comp ? 1 : 0) << 3) | ((sd.resample ? 1 : 0) << 2) | ((sl.fast ? 1 : 0) << 1) |
+                               ((sd.resample && sd.interp) ? 1 : 0));
+            }
+        }
+        if (p->mixed && !table.empty()) {
+            // slots of one variant contiguous (stable: the same order as the call lists them otherwise)
+            std::vector<int> ord(table.size());
+            for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
+            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return vkey[(size_t)x] < vkey[(size_t)y]; });
+            std::vector<PoolSlot> t2(table.size());
+            std::vector<PoolParams> q2(table.size());
+            std::vector<VariantRun> &vr = vruns[(size_t)gi];
+            for (size_t k = 0; k < ord.size(); ++k) {
+                t2[k] = table[(size_t)ord[k]];
+                q2[k] = params[(size_t)ord[k]];
+                const int key = vkey[(size_t)ord[k]];
+                if (k == 0 || key != vkey[(size_t)ord[k - 1]])
+                    vr.push_back(VariantRun{(int)k, 0, key >> 3 & 1, key >> 2 & 1, key >> 1 & 1, key & 1, 0, 0, 0});
+                VariantRun &r = vr.back();
+                ++r.count;
+                if (t2[k].res_ntiles > r.max_tiles) r.max_tiles = t2[k].res_ntiles;
+                if (q2[k].lds_floats > r.lds_floats) r.lds_floats = q2[k].lds_floats;
+                if (q2[k].tab_bytes > r.tab_bytes) r.tab_bytes = q2[k].tab_bytes;
+            }
+            table.swap(t2);
+            params.swap(q2);
+            params_off[(size_t)gi] = put(params.data(), params.size() * sizeof(PoolParams));
         }
         g.nslots = (int)table.size();
         g.table_off = put(table.data(), table.size() * sizeof(PoolSlot));
@@ -2647,10 +3102,14 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
 #endif
     ce = hipMemcpyAsync(p->d_desc.p, p->h_desc.p, blob.size(), hipMemcpyHostToDevice, p->stream);
     if (ce != hipSuccess) return fail(hip_fail(ce, "descriptor upload", __LINE__));
+    int nlaunch = 0;
+    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
+    const int cm = bypass ? -1 : ((c.d.cfg.coremode == 1 || c.d.cfg.coremode == 2) ? c.d.cfg.coremode : 0);
     for (int gi = 0; gi <= groups; ++gi) {
         const Group &g = grp[(size_t)gi];
         launch_pool_ingest(p->stage_src, p->d_in.p, p->ring, C, reinterpret_cast<const PoolIngest *>(p->d_desc.p + g.ingest_off),
                            g.ningest, g.max_in, p->stream);
+        if (g.ningest > 0 && g.max_in > 0) ++nlaunch;
         const hipError_t ie = hipGetLastError();
         if (ie != hipSuccess) return fail(hip_fail(ie, "input ingest", __LINE__));
         if (gi == groups || g.nslots == 0) continue;
@@ -2661,8 +3120,15 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
         pl.nslots = g.nslots;
         pl.max_tn = g.max_tn;
         pl.max_tiles = g.max_tiles;
-        if ((st = pool_launch_group(p, pl)) != PV_OK) return fail(st);
+        if (p->mixed) {
+            const PoolParams *q = reinterpret_cast<const PoolParams *>(p->d_desc.p + params_off[(size_t)gi]);
+            if ((st = pool_mix_launch_group(p, pl, q, vruns[(size_t)gi], &nlaunch)) != PV_OK) return fail(st);
+        } else {
+            if ((st = pool_launch_group(p, pl)) != PV_OK) return fail(st);
+            nlaunch += 2 + (cm == 0 || cm == 1 ? 1 : 0) + (c.d.resample && pl.max_tiles > 0 ? 1 : 0);
+        }
     }
+    p->last_launches = nlaunch;
     // 5. wait: a sequence number behind the launches, spun on with a wall-clock bound (or a stream synchronisation
     // where the device has no stream memory operations)
     hipError_t he = hipSuccess;

@@ -344,4 +344,24 @@ bool launch_pool_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolL
                              bool launch = true);
 bool launch_pool_resample(const ResArgs &a, const PoolLaunch &p, hipStream_t st, bool launch = true);
 
+// Stream pool with per-slot pitch and time ratio (pv_pool_create_mixed): the same stages, each of which also reads its
+// slot's entry of a PoolParams table parallel to PoolLaunch::slots (indexed like it) and puts the slot's hop, phase
+// advance, frequency compensation, gain and resampler set-up into the slot view.  A launch serves slots of one kernel
+// variant (the argument blocks carry the variant's flags: do_freq_comp, resample, interp, fast); the host groups them.
+struct PoolParams {
+    double two_pi_hop;
+    int32_t hop, do_freq_comp;
+    float freq_comp, fixed_gain;
+    int32_t filt_len, oversample, sinc_len, tab_bytes, lds_floats, pad;
+    const float *sinc;  // the slot's Speex table in the pool's table arena (resampling slots)
+    const float4 *tab4; // ... and its expanded interpolation rows (interpolating slots)
+};
+bool launch_pmix_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st);
+bool launch_pmix_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st);
+bool launch_pmix_prop(const PropArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st);
+bool launch_pmix_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q,
+                             hipStream_t st, bool launch = true);
+// lds_floats / tab_bytes of `a`: the largest of the launch's slots (the LDS the launch reserves)
+bool launch_pmix_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch = true);
+
 } // namespace pv

@@ -4191,4 +4191,298 @@ bool launch_pool_resample(const ResArgs &a, const PoolLaunch &p, hipStream_t st,
     return true;
 }
 
+// --------------------------------------------------------------------------------------------
+// Stream pool with per-slot parameters (pv_kernels.h PoolParams): the per-slot kernels above, whose slot view also
+// takes the slot's hop, phase advance, frequency compensation, gain and resampler set-up from its PoolParams entry.
+// They call the same device functions with the same values a single-stream engine of the slot's configuration passes
+// as launch-wide arguments, so a slot computes exactly what that engine computes.  The kernels above stay as they are.
+// --------------------------------------------------------------------------------------------
+template <int NC> __global__ __launch_bounds__(64) void pv_pmix_analyze_wave_kernel(const AnalyzeArgs a, const PoolLaunch p,
+                                                                                   const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int tl = __builtin_amdgcn_readfirstlane((int)blockIdx.x / a.rows), row = blockIdx.x - tl * a.rows;
+    if (tl >= ps.Tn) return;
+    AnalyzeArgs v = pool_view(a, ps);
+    v.hop = q[blockIdx.y].hop;
+    analyze_wave_role<NC, WF<NC>::LDS_CF * sizeof(cf)>(v, row, tl, reinterpret_cast<cf *>(smem_raw));
+}
+__global__ __launch_bounds__(128) void pv_pmix_analyze_split_kernel(const AnalyzeArgs a, const PoolLaunch p,
+                                                                     const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int tl = __builtin_amdgcn_readfirstlane((int)blockIdx.x / a.rows), row = blockIdx.x - tl * a.rows;
+    if (tl >= ps.Tn) return;
+    AnalyzeArgs v = pool_view(a, ps);
+    v.hop = q[blockIdx.y].hop;
+    analyze_split_role<WF2048S, WF2048S::LDS_CF * sizeof(cf)>(v, row, tl, reinterpret_cast<cf *>(smem_raw));
+}
+
+bool launch_pmix_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
+    const dim3 grid(a.rows * p.max_tn, p.nslots);
+    const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
+    switch (a.tb.nc) {
+    case 256:
+        hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<256>, grid, dim3(64), WF<256>::LDS_CF * sizeof(cf) + atab, st, a, p, q);
+        return true;
+    case 512:
+        hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<512>, grid, dim3(64), WF<512>::LDS_CF * sizeof(cf) + atab, st, a, p, q);
+        return true;
+    case 1024:
+        hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<1024>, grid, dim3(64), WF<1024>::LDS_CF * sizeof(cf) + atab, st, a, p, q);
+        return true;
+    case 2048:
+        if (a.split) {
+            hipLaunchKernelGGL(pv_pmix_analyze_split_kernel, grid, dim3(WF2048S::LANES),
+                               WF2048S::LDS_CF * sizeof(cf) + atab + 64, st, a, p, q);
+        } else {
+            static unsigned long long big = 0;
+            allow_big_lds_dev(pv_pmix_analyze_wave_kernel<2048>, big);
+            hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<2048>, grid, dim3(64), WF<2048>::LDS_CF * sizeof(cf) + atab,
+                               st, a, p, q);
+        }
+        return true;
+    default: return false;
+    }
+}
+
+// phase-locked mode: match + rotation chain, one workgroup per (channel, slot)
+template <int D>
+__global__ __launch_bounds__(1024) void pv_pmix_phase_kernel(const MatchArgs m, const SeqArgs a, const PoolLaunch p,
+                                                             const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int hop = q[blockIdx.y].hop;
+    const double two_pi_hop = q[blockIdx.y].two_pi_hop;
+    const int64_t r = ps.row0;
+    const int32_t *pinc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    MatchArgs mv = m;
+    mv.hop = hop, mv.two_pi_hop = two_pi_hop;
+    mv.t0 = ps.t0, mv.s0 = ps.s0, mv.Tn = ps.Tn, mv.phase_inc = pinc;
+    mv.phase += r * m.TR * m.HP;
+    mv.peaks += r * m.TR * m.PKP;
+    mv.npk += r * m.TR;
+    mv.recs += r * m.TR * m.PKP;
+    mv.modes += r * m.TR;
+    SeqArgs av = a;
+    av.hop = hop, av.two_pi_hop = two_pi_hop;
+    av.t0 = ps.t0, av.s0 = ps.s0, av.Tn = ps.Tn, av.phase_inc = pinc;
+    av.phase = mv.phase, av.peaks = mv.peaks, av.npk = mv.npk, av.recs = mv.recs, av.modes = mv.modes;
+    av.rot += r * a.TR * a.PKP;
+    av.outphase += r * a.TR * a.HP;
+    av.st_kind += r;
+    av.st_rot += r * a.PKP;
+    av.st_po += r * a.hs;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    for (int tl = wave; tl < mv.Tn; tl += nw)
+        match_wave_role(mv, blockIdx.x, tl, smem_raw + (size_t)wave * match_wave_lds(mv.hs, mv.PKP));
+    __threadfence(); // the records go through global memory: the chain's loads must see them
+    __syncthreads();
+    if (av.high_prio) __builtin_amdgcn_s_setprio(3);
+    seq_role_ring<D>(av, blockIdx.x, smem_raw);
+}
+
+bool launch_pmix_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
+    if (!pool_phase_supported(a.hs, a.PKP)) return false;
+    static unsigned long long big = 0;
+    allow_big_lds_dev(pv_pmix_phase_kernel<kPoolSeqDepth>, big);
+    hipLaunchKernelGGL(pv_pmix_phase_kernel<kPoolSeqDepth>, dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
+                       pool_phase_lds(a.hs, a.PKP), st, m, a, p, q);
+    return true;
+}
+
+// coremode 0: the per-bin recurrence; grid (bins / 256, C, slots)
+__global__ __launch_bounds__(kPropThreads) void pv_pmix_prop_kernel(const PropArgs a, const PoolLaunch p,
+                                                                    const PoolParams *__restrict__ q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const PoolSlot ps = p.slots[blockIdx.z];
+    const int64_t r = ps.row0;
+    PropArgs v = a;
+    v.hop = q[blockIdx.z].hop;
+    v.two_pi_hop = q[blockIdx.z].two_pi_hop;
+    v.t0 = ps.t0, v.s0 = ps.s0, v.Tn = ps.Tn;
+    v.phase_inc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    v.phase += r * a.TR * a.HP;
+    v.outphase += r * a.TR * a.HP;
+    v.st_pp += r * a.hs;
+    v.st_po += r * a.hs;
+    if (i < a.hs) prop_role(v, blockIdx.y, i);
+}
+
+bool launch_pmix_prop(const PropArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
+    hipLaunchKernelGGL(pv_pmix_prop_kernel, dim3((a.hs + kPropThreads - 1) / kPropThreads, a.rows, p.nslots),
+                       dim3(kPropThreads), 0, st, a, p, q);
+    return true;
+}
+
+// fused synthesis + overlap-add: one workgroup per (channel, slot); the launch's slots share do_freq_comp, resample and
+// fast (the variant), each brings its own hop, phase advance, frequency compensation and gain
+template <int NC, int kPlainCore, int kRes, bool kFast>
+__global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void pv_pmix_synth_chain_kernel(
+    const SynthArgs s, const ChainArgs c, const PoolLaunch p, const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const PoolParams *__restrict__ qs = q + blockIdx.y;
+    const int64_t r = ps.row0;
+    SynthArgs sv = s;
+    sv.hop = qs->hop;
+    sv.two_pi_hop = qs->two_pi_hop;
+    sv.do_freq_comp = qs->do_freq_comp;
+    sv.freq_comp = qs->freq_comp;
+    sv.fixed_gain = qs->fixed_gain;
+    sv.t0 = ps.t0, sv.s0 = ps.s0, sv.Tn = ps.Tn;
+    sv.phase_inc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    const int64_t plane = r * s.TR * s.tb.HP;
+    sv.mag += plane;
+    sv.phase += plane;
+    if (sv.outphase) sv.outphase += plane;
+    if (sv.peaks) sv.peaks += r * s.TR * s.PKP;
+    if (sv.npk) sv.npk += r * s.TR;
+    if (sv.modes) sv.modes += r * s.TR;
+    if (sv.rot) sv.rot += r * s.TR * s.PKP;
+    ChainArgs cv = c;
+    cv.Tn = ps.Tn;
+    cv.t0 = ps.t0;
+    cv.slices = reinterpret_cast<const ChainSlice *>(p.desc + ps.cs_off);
+    cv.run_off = reinterpret_cast<const int32_t *>(p.desc + ps.ro_off);
+    cv.wden = reinterpret_cast<const float *>(p.desc + ps.wden_off);
+    cv.wden_hi = cv.wden;
+    cv.st_acc += 2 * r * c.AR; // [slot][2][C][AR]
+    cv.acc_sel = ps.acc_sel;
+    if (kRes) cv.stream += r * ((int64_t)c.smask + 1);
+    cv.out = p.out + ps.out_off;
+    cv.out_stride_row = ps.out_stride_row;
+    pool_synth_chain_role<NC, kPlainCore, kRes, kFast>(sv, cv, blockIdx.x, smem_raw);
+}
+
+template <int NC, int kPlainCore>
+static bool launch_pmix_synth_chain_res(const SynthArgs &s, const ChainArgs &c_in, const PoolLaunch &p,
+                                        const PoolParams *q, hipStream_t st, bool launch) {
+    const bool use_fast = kPlainCore >= 0 && c_in.fast;
+    const int kMaxThreads = use_fast ? pool_chain_max_threads(NC, kPlainCore, true) : pool_chain_max_threads(NC, kPlainCore, false);
+    ChainArgs c = c_in;
+    if (64 * c.waves > kMaxThreads) c.waves = kMaxThreads / 64;
+    if (c.waves < 1) return false;
+    const size_t lds = chain_lds_bytes(c, NC);
+    if (!launch) return true;
+    const dim3 grid(c.rows, p.nslots), block(64 * c.waves);
+    static unsigned long long m0 = 0, m1 = 0, f0 = 0, f1 = 0;
+    if constexpr (kPlainCore >= 0) {
+        if (c.fast) {
+            if (!c.resample) {
+                allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, true>, f0);
+                hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, true>), grid, block, lds, st, s, c, p, q);
+            } else {
+                allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, true>, f1);
+                hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, true>), grid, block, lds, st, s, c, p, q);
+            }
+            return true;
+        }
+    }
+    if (!c.resample) {
+        allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, false>, m0);
+        hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, false>), grid, block, lds, st, s, c, p, q);
+    } else {
+        allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, false>, m1);
+        hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, false>), grid, block, lds, st, s, c, p, q);
+    }
+    return true;
+}
+
+// the same choice of specialisation as launch_pool_synth_chain (s.do_freq_comp: the launch's variant)
+bool launch_pmix_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q,
+                             hipStream_t st, bool launch) {
+    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
+    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                           !synth_generic_only() && s.coremode == 1;
+    if (s.tb.nc == 256) {
+        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<256, 1>(s, c, p, q, st, launch);
+        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<256, 0>(s, c, p, q, st, launch);
+        if (plain) return launch_pmix_synth_chain_res<256, 2>(s, c, p, q, st, launch);
+        return launch_pmix_synth_chain_res<256, -1>(s, c, p, q, st, launch);
+    }
+    if (s.tb.nc == 512) {
+        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<512, 1>(s, c, p, q, st, launch);
+        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<512, 0>(s, c, p, q, st, launch);
+        if (plain) return launch_pmix_synth_chain_res<512, 2>(s, c, p, q, st, launch);
+        return launch_pmix_synth_chain_res<512, -1>(s, c, p, q, st, launch);
+    }
+    if (s.tb.nc == 1024) {
+        if (fc_locked) return launch_pmix_synth_chain_res<1024, 3>(s, c, p, q, st, launch);
+        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<1024, 1>(s, c, p, q, st, launch);
+        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<1024, 0>(s, c, p, q, st, launch);
+        if (plain) return launch_pmix_synth_chain_res<1024, 2>(s, c, p, q, st, launch);
+        return launch_pmix_synth_chain_res<1024, -1>(s, c, p, q, st, launch);
+    }
+    if (s.tb.nc == 2048) {
+        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<2048, 1>(s, c, p, q, st, launch);
+        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<2048, 0>(s, c, p, q, st, launch);
+        if (plain) return launch_pmix_synth_chain_res<2048, 2>(s, c, p, q, st, launch);
+        return launch_pmix_synth_chain_res<2048, -1>(s, c, p, q, st, launch);
+    }
+    return false;
+}
+
+// resampling: grid (tiles, row groups, slots); the launch's slots share interp and fast
+__device__ __forceinline__ bool pmix_res_view(const ResArgs &a, const PoolLaunch &p, const PoolParams *__restrict__ q,
+                                              ResArgs &v) {
+    if (!pool_res_view(a, p, v)) return false;
+    const PoolParams *__restrict__ qs = q + blockIdx.z;
+    v.filt_len = qs->filt_len;
+    v.oversample = qs->oversample;
+    v.sinc = qs->sinc;
+    v.sinc_len = qs->sinc_len;
+    v.tab4 = qs->tab4;
+    v.tab_bytes = qs->tab_bytes;
+    v.lds_floats = qs->lds_floats;
+    return true;
+}
+template <int kRes>
+__global__ __launch_bounds__(kTileOut) void pv_pmix_resample_kernel(const ResArgs a, const PoolLaunch p, const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    ResArgs v;
+    if (!pmix_res_view(a, p, q, v)) return;
+    pool_resample_role<kRes>(v, blockIdx.x, blockIdx.y, smem_raw);
+}
+template <int kRes>
+__global__ __launch_bounds__(kTileOut) void pv_pmix_resample_fast_kernel(const ResArgs a, const PoolLaunch p,
+                                                                         const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    ResArgs v;
+    if (!pmix_res_view(a, p, q, v)) return;
+    pool_resample_fast_role<kRes, kPoolResFastRows>(v, blockIdx.x, blockIdx.y, smem_raw);
+}
+
+bool launch_pmix_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch) {
+    const int NR = a.fast ? kPoolResFastRows : kResRows;
+    const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
+    if (lds > 160 * 1024 - 512) return false;
+    if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
+    const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
+    static unsigned long long m1 = 0, m2 = 0, f1 = 0, f2 = 0;
+    if (a.fast) {
+        if (a.interp) {
+            allow_big_lds_dev(pv_pmix_resample_fast_kernel<2>, f2);
+            hipLaunchKernelGGL(pv_pmix_resample_fast_kernel<2>, grid, dim3(kTileOut), lds, st, a, p, q);
+        } else {
+            allow_big_lds_dev(pv_pmix_resample_fast_kernel<1>, f1);
+            hipLaunchKernelGGL(pv_pmix_resample_fast_kernel<1>, grid, dim3(kTileOut), lds, st, a, p, q);
+        }
+    } else if (a.interp) {
+        allow_big_lds_dev(pv_pmix_resample_kernel<2>, m2);
+        hipLaunchKernelGGL(pv_pmix_resample_kernel<2>, grid, dim3(kTileOut), lds, st, a, p, q);
+    } else {
+        allow_big_lds_dev(pv_pmix_resample_kernel<1>, m1);
+        hipLaunchKernelGGL(pv_pmix_resample_kernel<1>, grid, dim3(kTileOut), lds, st, a, p, q);
+    }
+    return true;
+}
+
 } // namespace pv

@@ -51,6 +51,11 @@ class Info(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PoolRange(C.Structure):
+    _fields_ = [("min_semitones", C.c_float), ("max_semitones", C.c_float), ("min_time_ratio", C.c_float),
+                ("max_time_ratio", C.c_float)]
+
+
 _lib = None
 
 
@@ -130,6 +135,9 @@ def lib():
     L.pv_pool_retrieve.restype = C.c_int32
     L.pv_pool_get_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Info)]
     L.pv_pool_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pv_pool_last_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.pv_pool_create_mixed.argtypes = [C.POINTER(Config), C.POINTER(PoolRange), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]
+    L.pv_pool_open_with.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_int32)]
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -433,14 +441,25 @@ class HostIO:
 class StreamPool:
     """Up to `capacity` independent live streams of one configuration (include/audiomod_pv.h pv_pool_*).  A slot
     behaves bit for bit like a PhaseVocoder / pv_engine of the same configuration fed the same blocks; one feed()
-    serves any subset of the open slots with one launch sequence.  One host thread per pool."""
+    serves any subset of the open slots with one launch sequence.  One host thread per pool.
 
-    def __init__(self, capacity, channels=2, device=0, **config):
+    pitch_range=(lo, hi) and / or ratio_range=(lo, hi) make a mixed pool (pv_pool_create_mixed): each slot then takes
+    its own pitch / time ratio within them at open(semitones=..., time_ratio=...), and behaves like a PhaseVocoder
+    created with those values.  A range not given is the configuration's own value."""
+
+    def __init__(self, capacity, channels=2, device=0, pitch_range=None, ratio_range=None, **config):
         self.L = lib()
         self.cfg = make_config(channels, **config)
         self.channels = channels
         self.h = C.c_void_p()
-        _check(self.L.pv_pool_create(C.byref(self.cfg), int(capacity), device, C.byref(self.h)), "pv_pool_create")
+        if pitch_range is None and ratio_range is None:
+            _check(self.L.pv_pool_create(C.byref(self.cfg), int(capacity), device, C.byref(self.h)), "pv_pool_create")
+        else:
+            lo, hi = pitch_range if pitch_range is not None else (self.cfg.pitch_semitones,) * 2
+            rlo, rhi = ratio_range if ratio_range is not None else (self.cfg.time_ratio,) * 2
+            rng = PoolRange(lo, hi, rlo, rhi)
+            _check(self.L.pv_pool_create_mixed(C.byref(self.cfg), C.byref(rng), int(capacity), device, C.byref(self.h)),
+                   "pv_pool_create_mixed")
         self.capacity = self.L.pv_pool_capacity(self.h)
 
     def close_pool(self):
@@ -451,10 +470,16 @@ class StreamPool:
     def __del__(self):
         self.close_pool()
 
-    def open(self):
-        """A fresh stream in the lowest free slot; returns the slot."""
+    def open(self, semitones=None, time_ratio=None):
+        """A fresh stream in the lowest free slot, at the given pitch / time ratio (default: the configuration's);
+        returns the slot."""
         s = C.c_int32(-1)
-        _check(self.L.pv_pool_open(self.h, C.byref(s)), "pv_pool_open")
+        if semitones is None and time_ratio is None:
+            _check(self.L.pv_pool_open(self.h, C.byref(s)), "pv_pool_open")
+        else:
+            st = self.cfg.pitch_semitones if semitones is None else semitones
+            tr = self.cfg.time_ratio if time_ratio is None else time_ratio
+            _check(self.L.pv_pool_open_with(self.h, float(tr), float(st), C.byref(s)), "pv_pool_open_with")
         return s.value
 
     def close(self, slot):
@@ -495,3 +520,9 @@ class StreamPool:
         h, w = C.c_double(), C.c_double()
         _check(self.L.pv_pool_last_timing(self.h, C.byref(h), C.byref(w)), "pv_pool_last_timing")
         return h.value, w.value
+
+    def last_launches(self):
+        """Kernels launched by the last feed()."""
+        n = C.c_int32(0)
+        _check(self.L.pv_pool_last_launches(self.h, C.byref(n)), "pv_pool_last_launches")
+        return n.value

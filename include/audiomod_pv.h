@@ -158,7 +158,7 @@ int pv_get_info(const pv_engine *e, pv_info *info);
  *                    c of slots[i].  Synchronous.  All or nothing: a call that any slot's planner
  *                    refuses changes no slot (pv_last_error() names the slot).
  * Scope: modes NORMAL_SHIFT, GENDER_CHANGE, FORMANT_PRESERVE, NORMAL_STRETCH, ROBOTIC; coremodes
- * 0-2; fftsize 512 ... 4096.  Anything else returns PV_ERR_UNSUPPORTED from pv_pool_create;
+ * 0-2; fftsize 512 ... 4096 (a mixed pool's, below, too).  Anything else returns PV_ERR_UNSUPPORTED from pv_pool_create;
  * capacity < 1 or capacity x channels > 65535 returns PV_ERR_INVALID_ARG (both checked before any
  * device call).  One host thread per pool.
  * -------------------------------------------------------------------------------------------- */
@@ -175,6 +175,27 @@ int pv_pool_get_info(const pv_pool *p, int32_t slot, pv_info *info);
 /* Diagnostics: wall-clock time of the last pv_pool_feed, split into the host's share up to the wait (planning,
  * descriptors, staging, enqueueing the launches) and the wait for the device. */
 int pv_pool_last_timing(const pv_pool *p, double *host_us, double *wait_us);
+/* Kernels launched by the last pv_pool_feed (the input scatter included). */
+int pv_pool_last_launches(const pv_pool *p, int32_t *launches);
+
+/* Mixed pool: slots of one pool at different pitches and time ratios.  cfg fixes sample_rate, channels, mode, coremode,
+ * fftsize and hopsize for every slot; a slot opened with pv_pool_open_with(time_ratio, pitch_semitones) is a fresh
+ * stream with the semantics of a pv_engine created from cfg with those two values (same pv_set_arithmetic setting as
+ * when the pool was created).  pv_pool_open opens a slot at cfg's own values.  Buffers are sized once, at creation,
+ * for the whole range.  One feed groups its slots by the kernel variant their engines would run (frequency
+ * compensation or not, resampling or not, direct or interpolated table, PV_ARITH_FAST kernels or not) and launches
+ * each stage once per variant present, whatever the number of distinct pitches.
+ *   pv_pool_create_mixed : range min > max, a NaN, or a range without cfg's values: PV_ERR_INVALID_ARG; out of the pool's
+ *                          scope, or a range whose worst case does not fit a per-slot kernel: PV_ERR_UNSUPPORTED
+ *                          (pv_last_error() names the kernel).  All checked before any device call.
+ *   pv_pool_open_with    : a value outside the pool's range (a pool from pv_pool_create: anything but cfg's values),
+ *                          or one the engine itself would refuse, returns an error and changes nothing. */
+typedef struct pv_pool_range {
+    float min_semitones, max_semitones;   /* pitch_semitones a slot may take */
+    float min_time_ratio, max_time_ratio; /* time_ratio a slot may take */
+} pv_pool_range;
+int pv_pool_create_mixed(const pv_config *cfg, const pv_pool_range *range, int32_t capacity, int device, pv_pool **out);
+int pv_pool_open_with(pv_pool *p, float time_ratio, float pitch_semitones, int32_t *slot);
 
 /* ----------------------------------------------------------------------------------------------
  * Batch engine: `nstreams` independent streams of identical configuration and length, input and
