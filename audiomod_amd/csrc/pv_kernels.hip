@@ -3445,6 +3445,68 @@ __global__ __launch_bounds__(kTileOut) void pv_resample_kernel(const ResArgs a) 
 // --------------------------------------------------------------------------------------------
 constexpr int kResFastRows = 16; // (8 where the batch has fewer rows or the tile does not fit 64 KB of LDS)
 
+// cubic_coef (resample.c:339-351)
+__device__ __forceinline__ float4 res_cubic_coef(const float frac) {
+    const float c0 = -0.16667f * frac + 0.16667f * frac * frac * frac;
+    const float c1 = frac + 0.5f * frac * frac - 0.5f * frac * frac * frac;
+    const float c3 = -0.33333f * frac + 0.5f * frac * frac - 0.16667f * frac * frac * frac;
+    const float c2 = (float)(1. - c0 - c1 - c3);
+    return make_float4(c0, c1, c2, c3);
+}
+// the filter tap j of an output whose cubic weights are c, from the four interpolation-table values T[j]
+__device__ __forceinline__ float res_cubic_tap(const float4 c, const float4 t) {
+    return __builtin_fmaf(c.w, t.w, __builtin_fmaf(c.z, t.z, __builtin_fmaf(c.y, t.y, c.x * t.x)));
+}
+
+// One output of NR rows on the vector ALU: the thread's output oe, its group's staged samples xs (row r at r * xstride;
+// rows at or past nrl are not staged and read row 0 instead: computed, never stored) and the tables in LDS, stored to
+// the first nr rows at out (the output in the group's first row).  pv_resample_fast_kernel's body, and the matrix-core
+// kernel's for a workgroup whose samples are not all finite.
+template <int kRes, int NR>
+__device__ __forceinline__ void res_fast_valu(const ResArgs &a, const uint2 oe, const float *xs, const int xstride,
+                                              const int nrl, const float4 *tab4, const float *stab,
+                                              float *__restrict__ out, const int nr) {
+    const int NF = a.filt_len;
+    const float *x = xs + (int)(oe.x & 0xffffu); // tap j = 0
+    float acc[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = 0.f;
+    if (kRes == 2) {
+        const float frac = __uint_as_float(oe.y);
+        const float4 cw = res_cubic_coef(frac);
+        const float4 *__restrict__ T = tab4 + (int)(oe.x >> 16) * (NF + 1);
+#pragma unroll 4
+        for (int j = 0; j < NF; ++j) { // NF is a multiple of 4 (resample.c:687)
+            // (PV_EXP_RES: elimination builds for timing only -- bit 0 no sample reads, bit 1 no coefficient reads)
+#if defined(PV_EXP_RES) && (PV_EXP_RES & 2)
+            const float4 c = make_float4(frac, cw.x, cw.y, (float)j);
+#else
+            const float4 c = T[j];
+#endif
+            const float h = res_cubic_tap(cw, c);
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+#if defined(PV_EXP_RES) && (PV_EXP_RES & 1)
+                acc[r] = __builtin_fmaf(frac + (float)r, h, acc[r]);
+#else
+                acc[r] = __builtin_fmaf(x[(r < nrl ? r : 0) * xstride + j], h, acc[r]);
+#endif
+            }
+        }
+    } else {
+        const float *t = stab + (oe.x >> 16) * (uint32_t)NF;
+#pragma unroll 4
+        for (int j = 0; j < NF; ++j) {
+            const float h = t[j];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) acc[r] = __builtin_fmaf(x[(r < nrl ? r : 0) * xstride + j], h, acc[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+        if (r < nr) out[(int64_t)r * a.out_stride_row] = acc[r];
+}
+
 template <int kRes, int NR> // 1 = direct sinc table, 2 = cubic-interpolated table
 __global__ __launch_bounds__(kTileOut) void pv_resample_fast_kernel(const ResArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -3479,48 +3541,165 @@ __global__ __launch_bounds__(kTileOut) void pv_resample_fast_kernel(const ResArg
     __syncthreads();
     if (tid >= tile.kcnt) return;
     float *__restrict__ out = a.out + (int64_t)row0 * a.out_stride_row + (tile.k0 - a.k_base) + tid;
-    const float *x = xs + (int)(oe.x & 0xffffu); // tap j = 0
-    float acc[NR];
+    res_fast_valu<kRes, NR>(a, oe, xs, a.lds_floats, NR, tab4, stab, out, nr);
+}
+
+// --------------------------------------------------------------------------------------------
+// The same outputs on the f32 matrix cores (the default; AUDIOMOD_PV_RES_MFMA=0 selects pv_resample_fast_kernel).
+// All rows follow one schedule, so 16 consecutive outputs n0 .. n0+15 of a tile and the 16 rows of a workgroup are a
+// small banded product
+//     Out[r][n] = sum_t X[r][t] B[t][n],   B[t][n] = h_n(t - off_n) for 0 <= t - off_n < NF, else 0,
+// t running from off_n0 over ceil((off_n15 - off_n0 + NF) / 4) K-steps of v_mfma_f32_16x16x4_f32: lane l holds the
+// sample X[row l&15][t + (l>>4)] (one ds_read_b32) and the tap B[t + (l>>4)][n0 + (l&15)], interpolated exactly as
+// res_fast_valu does.  That instruction is bit for bit a k-ordered chain of f32 fma, so every output sees its taps
+// j = 0 .. NF-1 in order, as in the vector loop; the products outside the band are fma(x, 0, acc) = acc for finite x
+// (before the band acc is +0, as the loop starts).  So the outputs are the vector kernel's, bit for bit; the samples
+// stay in registers for all 16 outputs instead of being re-read from LDS for every tap.
+// - Each wave takes four 16-output blocks of its tile, all at once: four independent accumulators (the instruction's
+//   dependent latency is 40 cycles against a 32-cycle issue; two blocks at a time measured 0.147 against 0.132 ms per
+//   launch).  They run the largest K-step count of the four; a shorter block's extra steps have zero taps and read
+//   clamped sample positions.  Capped at 128 registers: four waves per SIMD, what the LDS allows anyway.
+// - The K-span is rounded up to a multiple of 4: the staging writes zeros to the four positions past the tile's samples.
+// - Row stride xstride = 2 mod 4 floats: the 16 rows x 4 t of an A read fall on distinct banks.  With the flag words it
+//   stays within the 16 rows x lds_floats of the vector kernel (the engines size lds_floats >= n_cnt + 7).
+// - inf or NaN among the samples would leak into outputs whose band does not cover it (inf * 0 = NaN), so the staging
+//   ORs a not-finite flag over them, and a workgroup that sees one runs res_fast_valu instead.
+// --------------------------------------------------------------------------------------------
+constexpr int kResMfmaRows = 16; // the M of v_mfma_f32_16x16x4_f32: one row group per workgroup
+constexpr int kResMfmaBlocks = 4; // 16-output blocks in flight per wave (all four of its blocks)
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+__host__ __device__ constexpr int res_mfma_xstride(const int lds_floats) { return ((lds_floats - 2) & ~3) + 2; }
+
+template <int kRes> // 1 = direct sinc table, 2 = cubic-interpolated table
+__global__ __launch_bounds__(kTileOut) __attribute__((amdgpu_waves_per_eu(4))) void pv_resample_mfma_kernel(const ResArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    constexpr int NR = kResMfmaRows, NW = kTileOut / 64, NB = kResMfmaBlocks, NBW = kTileOut / 16 / NW;
+    const float4 *tab4 = reinterpret_cast<const float4 *>(smem_raw);
+    const float *stab = reinterpret_cast<const float *>(smem_raw);
+    float *xs = reinterpret_cast<float *>(smem_raw + a.tab_bytes); // [nrl][xstride], then NW flag words
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const ResTile tile = a.tiles[blockIdx.x];
+    const int row0 = blockIdx.y * NR, NF = a.filt_len, ncnt = tile.n_cnt, kcnt = tile.kcnt;
+    const int nr = a.rows - row0 < NR ? a.rows - row0 : NR;
+    const int nrl = a.rows < NR ? a.rows : NR; // rows the launch's LDS holds
+    // (a tile too long for the padded layout -- no engine makes one -- stages at lds_floats and takes the vector loop)
+    const bool fits = ncnt + 4 <= res_mfma_xstride(a.lds_floats);
+    const int xstride = fits ? res_mfma_xstride(a.lds_floats) : a.lds_floats;
+    const int nstage = fits ? ncnt + 4 : ncnt;
+    const uint2 *__restrict__ ot = a.otab + (int64_t)blockIdx.x * kTileOut;
+    const int q = lane >> 4, c = lane & 15;
+    uint2 eo[NBW]; // the lane's output of each of its wave's blocks, loaded before the staging (blocks interleaved over
+                   // the waves: a short tile stays balanced)
 #pragma unroll
-    for (int r = 0; r < NR; ++r) acc[r] = 0.f;
+    for (int k = 0; k < NBW; ++k) {
+        const int n = 16 * (w + NW * k) + c;
+        eo[k] = n < kcnt ? ot[n] : make_uint2(0u, 0u);
+    }
+    bool bad = false;
+    for (int i = tid; i < nstage; i += kTileOut) {
+        const int64_t n = tile.n_lo + i; // the stream is zero before its first sample (skip_zeros, :1225)
+        float xv[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const float *__restrict__ st = a.stream + (int64_t)(row0 + r) * ((int64_t)a.smask + 1);
+            xv[r] = (r < nr && i < ncnt && n >= 0) ? st[(uint32_t)n & (uint32_t)a.smask] : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            if (r < nr) {
+                xs[r * xstride + i] = xv[r];
+                bad |= (__float_as_uint(xv[r]) & 0x7f800000u) == 0x7f800000u;
+            }
+    }
     if (kRes == 2) {
-        const float frac = __uint_as_float(oe.y);
-        // cubic_coef (resample.c:339-351)
-        const float c0 = -0.16667f * frac + 0.16667f * frac * frac * frac;
-        const float c1 = frac + 0.5f * frac * frac - 0.5f * frac * frac * frac;
-        const float c3 = -0.33333f * frac + 0.5f * frac * frac - 0.16667f * frac * frac * frac;
-        const float c2 = (float)(1. - c0 - c1 - c3);
-        const float4 *__restrict__ T = tab4 + (int)(oe.x >> 16) * (NF + 1);
-#pragma unroll 4
-        for (int j = 0; j < NF; ++j) { // NF is a multiple of 4 (resample.c:687)
-            // (PV_EXP_RES: elimination builds for timing only -- bit 0 no sample reads, bit 1 no coefficient reads)
-#if defined(PV_EXP_RES) && (PV_EXP_RES & 2)
-            const float4 c = make_float4(frac, c0, c1, (float)j);
-#else
-            const float4 c = T[j];
-#endif
-            const float h = __builtin_fmaf(c3, c.w, __builtin_fmaf(c2, c.z, __builtin_fmaf(c1, c.y, c0 * c.x)));
+        const int cnt = a.oversample * (NF + 1);
+        for (int i = tid; i < cnt; i += kTileOut) reinterpret_cast<float4 *>(smem_raw)[i] = a.tab4[i];
+    } else {
+        for (int i = tid; i < a.sinc_len; i += kTileOut) reinterpret_cast<float *>(smem_raw)[i] = a.sinc[i];
+    }
+    int *flag = reinterpret_cast<int *>(xs + nrl * xstride);
+    const bool wave_bad = __any(bad);
+    if (fits && lane == 0) flag[w] = wave_bad ? 1 : 0;
+    __syncthreads();
+    bool vec = !fits;
+    if (fits) {
 #pragma unroll
-            for (int r = 0; r < NR; ++r) {
-#if defined(PV_EXP_RES) && (PV_EXP_RES & 1)
-                acc[r] = __builtin_fmaf(frac + (float)r, h, acc[r]);
-#else
-                acc[r] = __builtin_fmaf(x[r * a.lds_floats + j], h, acc[r]);
-#endif
+        for (int i = 0; i < NW; ++i) vec |= flag[i] != 0;
+    }
+    float *__restrict__ out = a.out + (int64_t)row0 * a.out_stride_row + (tile.k0 - a.k_base);
+    if (vec) {
+        if (tid < kcnt) res_fast_valu<kRes, NR>(a, ot[tid], xs, xstride, nr, tab4, stab, out + tid, nr);
+        return;
+    }
+    const float *xa = xs + (c < nr ? c : 0) * xstride + q; // A: X[row c][t + q] (a missing row reads row 0)
+#pragma unroll 1
+    for (int p = 0; p < NBW / NB; ++p) {
+        int base[NB], jb[NB], nk[NB], nb[NB];
+        float4 cw[NB];
+        const float4 *T[NB];
+        const float *S[NB];
+        int ks = 0;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int n0 = 16 * (w + NW * (p * NB + b));
+            const int n = n0 + c;
+            const uint2 e = eo[p * NB + b];
+            const int off = (int)(e.x & 0xffffu);
+            const int last = (kcnt - 1 - n0 < 15 ? kcnt - 1 - n0 : 15); // uniform; < 0: an empty block
+            base[b] = __builtin_amdgcn_readfirstlane(off);
+            nk[b] = last < 0 ? 0 : (__builtin_amdgcn_readlane(off, last < 0 ? 0 : last) - base[b] + NF + 3) >> 2;
+            ks = nk[b] > ks ? nk[b] : ks;
+            // tap index of the lane's (t, n) at K-step s: j = jb + 4 s; outputs past kcnt never enter the band
+            jb[b] = n < kcnt ? q - (off - base[b]) : -(1 << 29);
+            nb[b] = n0;
+            if constexpr (kRes == 2) {
+                cw[b] = res_cubic_coef(__uint_as_float(e.y));
+                T[b] = tab4 + (int)(e.x >> 16) * (NF + 1);
+            } else {
+                S[b] = stab + (e.x >> 16) * (uint32_t)NF;
             }
         }
-    } else {
-        const float *t = stab + (oe.x >> 16) * (uint32_t)NF;
-#pragma unroll 4
-        for (int j = 0; j < NF; ++j) {
-            const float h = t[j];
+        ks = __builtin_amdgcn_readfirstlane(ks);
+        if (ks == 0) break; // (these blocks and every later one are past kcnt)
+        v4f acc[NB];
 #pragma unroll
-            for (int r = 0; r < NR; ++r) acc[r] = __builtin_fmaf(x[r * a.lds_floats + j], h, acc[r]);
+        for (int b = 0; b < NB; ++b) acc[b] = v4f{0.f, 0.f, 0.f, 0.f};
+        auto step = [&](const int s) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                // (every lane reads a tap -- out of band a clamped one, then zeroed: no branch in the loop; a step past
+                // the block's own span has zero taps, and its sample positions stop at the zero padding)
+                const uint32_t j = (uint32_t)(jb[b] + 4 * s), jc = j < (uint32_t)(NF - 1) ? j : (uint32_t)(NF - 1);
+                float h;
+                if constexpr (kRes == 2) h = res_cubic_tap(cw[b], T[b][jc]);
+                else h = S[b][jc];
+                h = j < (uint32_t)NF ? h : 0.f;
+                const int t = base[b] + 4 * s < ncnt ? base[b] + 4 * s : ncnt;
+                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[t], h, acc[b], 0, 0, 0);
+            }
+        };
+        int s = 0; // (four steps per trip: the compiler does not unroll a loop of run-time length here)
+#if defined(PV_EXP_RES) && (PV_EXP_RES & 4)
+        s = ks; // (elimination build, timing only: bit 2 no K-steps -- staging, table copy, set-up and stores remain)
+#endif
+#pragma unroll 1
+        for (; s + 4 <= ks; s += 4) step(s), step(s + 1), step(s + 2), step(s + 3);
+#pragma unroll 1
+        for (; s < ks; ++s) step(s);
+        // D: lane l holds Out[row 4 (l>>4) + i][n0 + (l&15)] in element i
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int n = nb[b] + c;
+            if (n < kcnt) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (4 * q + i < nr) out[(int64_t)(4 * q + i) * a.out_stride_row + n] = acc[b][i];
+            }
         }
     }
-#pragma unroll
-    for (int r = 0; r < NR; ++r)
-        if (r < nr) out[(int64_t)r * a.out_stride_row] = acc[r];
 }
 
 // (Measured and left out, round 3: NO = 4 consecutive outputs per thread walking the samples of their common span once
@@ -3545,6 +3724,28 @@ static void launch_resample_fast(const ResArgs &a, hipStream_t st) {
         const char *e = getenv("AUDIOMOD_PV_RES_ROWS");
         return e ? atoi(e) : 0;
     }();
+    static const bool mfma = [] { // AUDIOMOD_PV_RES_MFMA=0: the vector kernel (for comparison; same bits)
+        const char *e = getenv("AUDIOMOD_PV_RES_MFMA");
+        return !(e && atoi(e) == 0);
+    }();
+    const size_t fl = sizeof(float);
+    if (mfma && (size_t)a.tab_bytes + fl * (size_t)a.lds_floats * kResMfmaRows <= 64 * 1024) {
+        // LDS: the tables, then the staged rows -- at the padded stride plus the flag words, or at lds_floats for a
+        // tile that does not fit it -- never more than the vector kernel's 16 rows x lds_floats for two rows or more
+        const size_t nrl = a.rows < kResMfmaRows ? a.rows : kResMfmaRows;
+        const size_t padded = fl * (nrl * res_mfma_xstride(a.lds_floats) + kTileOut / 64);
+        const size_t lds = (size_t)a.tab_bytes + std::max(fl * nrl * (size_t)a.lds_floats, padded);
+        const dim3 grid(a.ntiles, (a.rows + kResMfmaRows - 1) / kResMfmaRows);
+        static unsigned long long m1 = 0, m2 = 0;
+        if (a.interp) {
+            allow_big_lds_dev(pv_resample_mfma_kernel<2>, m2);
+            hipLaunchKernelGGL(pv_resample_mfma_kernel<2>, grid, dim3(kTileOut), lds, st, a);
+        } else {
+            allow_big_lds_dev(pv_resample_mfma_kernel<1>, m1);
+            hipLaunchKernelGGL(pv_resample_mfma_kernel<1>, grid, dim3(kTileOut), lds, st, a);
+        }
+        return;
+    }
     const int want = rows_env ? rows_env : kResFastRows; // (8 -> 16 rows per thread: 0.265 -> 0.255 ms per launch alone, cfg4 -7 st +3 %)
     if (want >= 16 && a.rows >= 16 && (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * 16 <= 64 * 1024)
         launch_resample_fast_rows<16>(a, st);
