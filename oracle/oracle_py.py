@@ -56,6 +56,8 @@ def lib():
         L.pvo_available.argtypes = [C.c_void_p]
         L.pvo_retrieve.argtypes = [C.c_void_p, fpp, C.c_int]
         L.pvo_get_info.argtypes = [C.c_void_p, C.POINTER(Info)]
+        L.pvo_set_synth_trig_nudge.argtypes = [C.c_void_p, C.c_float, C.c_uint]
+        L.pvo_set_synth_trig_nudge.restype = None
         L.pvo_get_increments.restype = C.c_long
         L.pvo_get_increments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
         L.pvo_hann.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
@@ -86,12 +88,17 @@ class Oracle:
     """Streaming handle mirroring audiomod::phasevocoder's offline + real-time drive."""
 
     def __init__(self, channels, mode="normal_pitchshift", semitones=0.0, time_ratio=1.0, coremode=1,
-                 fftsize=2048, sample_rate=48000, hopsize=0):
+                 fftsize=2048, sample_rate=48000, hopsize=0, trig_nudge=0.0, nudge_seed=1):
+        """trig_nudge (test model, pv_oracle.h pvo_set_synth_trig_nudge): every synthesis sine / cosine off by
+        +-trig_nudge, signs from a generator seeded with nudge_seed; 0.0 is the reference, bit for bit.  run_offline /
+        run_realtime pass both through."""
         self.L = lib()
         m = MODES[mode] if isinstance(mode, str) else int(mode)
         self.cfg = Config(sample_rate, channels, time_ratio, semitones, m, coremode, fftsize, hopsize)
         self.h = self.L.pvo_create(C.byref(self.cfg))
         self.channels = channels
+        if trig_nudge:
+            self.L.pvo_set_synth_trig_nudge(self.h, float(trig_nudge), int(nudge_seed))
 
     def close(self):
         if self.h:

@@ -187,6 +187,9 @@ typedef struct {
     cfft *fwd, *inv;
     cpx *st_fwd, *st_inv; /* "super twiddles" */
     cpx *tmp, *packed;
+    /* test-only error model of the synthesis sine / cosine (pvo_set_synth_trig_nudge); 0 = off */
+    float nudge;
+    unsigned long long nudge_state;
 } rfft;
 
 static rfft *rfft_new(int n) {
@@ -270,8 +273,33 @@ static void rfft_forward_polar(rfft *p, const float *in, float *mag, float *phas
     for (int i = 0; i <= hs; ++i) phase[i] = atan2f(p->packed[i].i, p->packed[i].r);
 }
 
+/* xorshift64* (Vigna 2016): one sign per call, from the top bit */
+static float nudge_sign(rfft *p) {
+    unsigned long long x = p->nudge_state;
+    x ^= x >> 12;
+    x ^= x << 25;
+    x ^= x >> 27;
+    p->nudge_state = x;
+    return ((x * 0x2545F4914F6CDD1DULL) >> 63) ? -1.f : 1.f;
+}
+
 static void rfft_inverse_polar(rfft *p, const float *mag, const float *phase, float *out) {
     const int hs = p->n / 2;
+    if (p->nudge != 0.f) {
+        /* the parity tests' noise floor: every sine / cosine off by +-nudge, the size of the error a device
+         * implementation is allowed.  A zero argument stays exact, as it is in every implementation (ROBOTIC). */
+        for (int i = 0; i <= hs; ++i) {
+            float c = cosf(phase[i]), s = sinf(phase[i]);
+            if (phase[i] != 0.f) {
+                c += p->nudge * nudge_sign(p);
+                s += p->nudge * nudge_sign(p);
+            }
+            p->packed[i].r = mag[i] * c;
+            p->packed[i].i = mag[i] * s;
+        }
+        rfft_inverse(p, p->packed, out);
+        return;
+    }
     for (int i = 0; i <= hs; ++i) {
         p->packed[i].r = mag[i] * cosf(phase[i]);
         p->packed[i].i = mag[i] * sinf(phase[i]);
@@ -754,6 +782,24 @@ pvo *pvo_create(const pvo_config *cfg) {
     h->peak = (int *)xcalloc(H, sizeof(int));
     h->prev_peak = (int *)xcalloc(H, sizeof(int));
     return h;
+}
+
+/* splitmix64: spreads (seed, channel) over the generator's state; never zero */
+static unsigned long long nudge_seed(unsigned long long z) {
+    z += 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    z ^= z >> 31;
+    return z ? z : 1;
+}
+
+void pvo_set_synth_trig_nudge(pvo *h, float delta, unsigned seed) {
+    for (int c = 0; c < h->cfg.channels; ++c) {
+        h->ch[c].fft->nudge = delta;
+        h->ch[c].fft->nudge_state = nudge_seed(((unsigned long long)seed << 16) + 2 * c);
+        h->car[c].fft->nudge = delta;
+        h->car[c].fft->nudge_state = nudge_seed(((unsigned long long)seed << 16) + 2 * c + 1);
+    }
 }
 
 void pvo_destroy(pvo *h) {

@@ -59,6 +59,11 @@ int pvo_available(const pvo *h);
 /* == Impl::retrieve (phasevocoderprocess.cc:1266-1284); returns frames read per channel */
 int pvo_retrieve(pvo *h, float *const *out, int n);
 void pvo_get_info(const pvo *h, pvo_info *info);
+/* TEST MODEL, off by default (delta = 0: bit-identical to the reference).  Adds +delta or -delta, the sign drawn from a
+ * generator seeded by (seed, channel), to every cosf / sinf result of the resynthesis (rfft_inverse_polar) whose
+ * argument is not exactly zero: the one place where the engine may differ from the reference in value.  The parity
+ * tests take the difference between a nudged and a plain run as the noise floor of a configuration. */
+void pvo_set_synth_trig_nudge(pvo *h, float delta, unsigned seed);
 /* per-slice shift increments recorded so far (for pinning the host planner); returns count copied */
 long pvo_get_increments(const pvo *h, int *shift, int *phase, long max);
 

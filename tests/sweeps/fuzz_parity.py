@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on the GPU: random configurations (mode, pitch, ratio, core mode, FFT size, hop, rate,
-channels, length, call size, signal) through the streaming and the batch API against the oracle.  Prints one line
-per case and a summary; exit code 1 if any case fails.  usage: tests/sweeps/fuzz_parity.py [cases] [seed] [seconds]"""
+channels, length, call size, signal) through the streaming and the batch API against the oracle: equal counts, RMS <=
+1e-4 and the error-shape bar of tests/helpers.py (max abs and worst 256-sample window within 8 noise floors + 4 ulp of
+the peak; the two ratios to the floor are printed per case).  Prints one line per case and a summary; exit code 1 if
+any case fails.  usage: tests/sweeps/fuzz_parity.py [cases] [seed] [seconds]"""
 import os
 import sys
 import time
@@ -13,8 +15,19 @@ sys.path.insert(0, ROOT)
 from audiomod_amd import engine as E  # noqa: E402
 from audiomod_amd import signals  # noqa: E402
 from oracle import oracle_py as O  # noqa: E402
+from tests.helpers import oracle_floor, shape_report  # noqa: E402
 
 RMS_TOL = 1e-4
+
+
+def shape(got, want, run, x, arith, **kw):
+    """(within the error-shape bar?, max abs / floor, worst window / floor): tests/helpers.py shape_report against the
+    oracle's own noise floor for this case (`want` serves as its un-nudged run: one extra oracle run per case)."""
+    floor = oracle_floor(run, x, arith, want=want, **kw)
+    ok, text, ratios = shape_report(got, want, floor)
+    if not ok:
+        print("   error shape:", text, flush=True)
+    return ok, ratios["max_abs"], ratios["win_rms"]
 
 
 def rms(a, b):
@@ -74,6 +87,7 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     budget = float(sys.argv[3]) if len(sys.argv) > 3 else 600.0
     rng = np.random.default_rng(seed)
+    arith = E.get_arithmetic()
     t0 = time.time()
     bad, unsupported, done = [], [], 0
     for i in range(cases):
@@ -105,12 +119,18 @@ def main():
             print("   counts/shape differ:", got.shape, want.shape, list(gc)[:12], list(wc)[:12], flush=True)
         r = rms(got, want) if ok else float("nan")
         ok = ok and r <= RMS_TOL
+        ra = rw = float("nan")
+        if ok:
+            oks, ra, rw = shape(got, want, O.run_offline, x, arith, block=block, flush=flush, **kw)
+            ok = ok and oks
         # the processBlock / outputReady loop (main/main.cc:561-572) on every third case
         if ok and i % 3 == 1:
             try:
                 wr, wrc = O.run_realtime(x, block=block, **kw)
                 gr, grc = E.run_realtime(x, block=block, **kw)
                 okr = list(grc) == list(wrc) and gr.shape == wr.shape and rms(gr, wr) <= RMS_TOL
+                if okr and kw["mode"] != "time_stretch":
+                    okr = shape(gr, wr, O.run_realtime, x, arith, block=block, **kw)[0]
                 if kw["mode"] == "time_stretch":  # pass-through in the reference: bit for bit
                     okr = okr and np.array_equal(gr.view(np.uint32), x.view(np.uint32))
                 if not okr:
@@ -139,14 +159,20 @@ def main():
                 rb = float("nan")
                 if okb:
                     rb = rms(out[0], want)
+                    oksb = rb <= RMS_TOL and shape(out[0], want, O.run_offline, x, arith, block=block, flush=flush, **kw)[0]
                     for k in range(1, ns):
                         wk, _, _ = O.run_offline(xs[k], block=block, flush=flush, **kw)
-                        rb = max(rb, rms(out[k], wk))
+                        rk = rms(out[k], wk)
+                        rb = max(rb, rk)
+                        oksb = oksb and rk <= RMS_TOL and shape(out[k], wk, O.run_offline, xs[k], arith, block=block,
+                                                                flush=flush, **kw)[0]
+                    okb = okb and oksb
                 okb = okb and rb <= RMS_TOL
             except E.PvError as ex:
                 unsupported.append(tag + f" [batch] -> {ex}")
                 print(tag, "BATCH UNSUPPORTED", ex, flush=True)
-        print(tag, f"rms={r:.2e} batch={rb:.2e}", "ok" if ok and okb else "FAIL", flush=True)
+        print(tag, f"rms={r:.2e} batch={rb:.2e} max/floor={ra:.2f} win/floor={rw:.2f}", "ok" if ok and okb else "FAIL",
+              flush=True)
         if not (ok and okb):
             bad.append(tag)
     print(f"{done} cases compared, {len(bad)} failed, {len(unsupported)} unsupported, {time.time() - t0:.0f} s")

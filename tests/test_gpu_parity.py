@@ -12,7 +12,7 @@ import pytest
 from audiomod_amd import engine as E
 from audiomod_amd import signals
 from oracle import oracle_py as O
-from tests.helpers import bits_equal, e2e_cases, load_e2e
+from tests.helpers import assert_shape, bits_equal, e2e_cases, load_e2e, oracle_floor
 
 pytestmark = pytest.mark.gpu
 
@@ -206,6 +206,11 @@ def test_full_size_single_stream_vs_oracle():
     y = out.cpu().numpy()[0]
     assert y.shape == want.shape
     assert rms(y, want) <= RMS_TOL
+    # ... and per sample and per 256-sample window (chunk seams at scale), sized by the oracle's own noise floor for
+    # this input (tests/test_parity_shape_gpu.py)
+    arith = E.get_arithmetic()
+    floor = oracle_floor(O.run_offline, x, arith, want=want, semitones=4.0)
+    assert_shape("full-size cfg2 60 s stereo +4 st", y, want, floor, arith)
 
 
 @pytest.mark.parametrize("frames", [1, 100, 479, 2047, 2048, 2049, 5000])

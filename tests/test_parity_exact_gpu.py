@@ -1,0 +1,265 @@
+"""Bit-exact tier: ROBOTIC mode WITH a pitch, under PV_ARITH_EXACT, against the oracle.
+
+ROBOTIC sets every synthesis phase to zero (cos 0 = 1, sin 0 = 0: no device transcendental on a non-trivial
+argument), so under PV_ARITH_EXACT the whole chain has to equal the reference bit for bit.  At
+0 semitones the reference does not resample; with a pitch it does, which puts the exact resampler (pv_resample_kernel
+<1> / <2>, the chain kernels' kRes = 1 path), the stream ring, the window-sum division and the tile / fused overlap-add
+under the same bar.  There is no tolerance anywhere in this file: equal per-call counts and bits_equal, nothing else.
+Every case first asserts from the oracle's own info() that the reference resamples and with the table class the case
+is named for."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from audiomod_amd import engine as E
+from audiomod_amd import signals
+from oracle import oracle_py as O
+from tests.helpers import bits_equal
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# name -> (configuration, interpolated table?, up-sampling?)
+PITCH = {
+    "+4_interp_down": (dict(semitones=4.0), 1, False),
+    "-7_interp_up": (dict(semitones=-7.0), 1, True),
+    "+12_direct_down": (dict(semitones=12.0), 0, False),
+    "-12_direct_up": (dict(semitones=-12.0), 0, True),
+    "+3.7_fractional": (dict(semitones=3.7), 1, False),
+    "-15.8_above_2x_up": (dict(fftsize=1024, sample_rate=16000, semitones=-15.8), 1, True),
+}
+
+
+@pytest.fixture(autouse=True)
+def exact_arithmetic():
+    prev = E.set_arithmetic(E.ARITH_EXACT)
+    yield
+    E.set_arithmetic(prev)
+
+
+def check_class(info, interp, up):
+    """The reference really resamples, with the table class and direction the case claims."""
+    assert info["resample"] == 1, info
+    assert info["res_interp"] == interp, info
+    assert (info["res_num"] < info["res_den"]) == up and info["res_num"] != info["res_den"], info
+    if not interp:
+        assert min(info["res_num"], info["res_den"]) == 1, info
+    assert info["res_filt_len"] >= 64, info
+
+
+def where(got, want):
+    """First differing positions, for the failure message."""
+    if got.shape != want.shape:
+        return f"shapes {got.shape} {want.shape}"
+    m = np.argwhere(np.ascontiguousarray(got).view(np.uint32) != np.ascontiguousarray(want).view(np.uint32))
+    return f"{len(m)} differ, first {m[:6].tolist()}: " + str([(float(got[tuple(i)]), float(want[tuple(i)])) for i in m[:6]])
+
+
+def stream_vs_oracle(x, interp, up, block=480, flush=True, **kw):
+    kw = dict(kw, mode="robotic")
+    want, wc, info = O.run_offline(x, block=block, flush=flush, **kw)
+    check_class(info, interp, up)
+    got, gc = E.run_offline(x, block=block, flush=flush, **kw)
+    assert list(gc) == list(wc)
+    assert want.shape[1] > 0 and float(np.abs(want).max()) > 0.01   # there is audio to compare
+    assert bits_equal(got, want), where(got, want)
+    return want
+
+
+def batch_vs_oracle(xs, interp, up, block=480, flush=True, **kw):
+    """Every stream of a batch (distinct inputs) against its own oracle run."""
+    import torch
+    kw = dict(kw, mode="robotic")
+    S, ch, frames = xs.shape
+    b = E.Batch(S, frames, channels=ch, block=block, flush=flush, **kw)
+    out = b.run(torch.from_numpy(xs).cuda(), d_out=torch.full((S, ch, b.out_frames), float("nan"), device="cuda"))
+    torch.cuda.synchronize()
+    out = out.cpu().numpy()
+    launches = b.launches
+    b.close()
+    for s in range(S):
+        want, _, info = O.run_offline(xs[s], block=block, flush=flush, **kw)
+        check_class(info, interp, up)
+        assert bits_equal(out[s], want), (s, where(out[s], want))
+    return launches
+
+
+@pytest.mark.parametrize("name", list(PITCH))
+def test_resampler_classes(name):
+    kw, interp, up = PITCH[name]
+    stream_vs_oracle(signals.voice(30000, 2, seed=77), interp, up, **kw)
+    xs = np.stack([signals.voice(30000, 2, seed=300 + s) for s in range(3)])
+    batch_vs_oracle(xs, interp, up, **kw)
+
+
+@pytest.mark.parametrize("semitones,interp,up", [(4.0, 1, False), (-7.0, 1, True), (12.0, 0, False)],
+                         ids=["+4", "-7", "+12"])
+@pytest.mark.parametrize("fftsize", [256, 512, 1024, 2048, 4096, 8192])
+def test_every_fft_size_class(fftsize, semitones, interp, up):
+    """generic LDS transforms (256, 8192), wave per frame (512 ... 4096), split analysis (4096)"""
+    stream_vs_oracle(signals.voice(30000, 2, seed=78), interp, up, fftsize=fftsize, semitones=semitones)
+    xs = np.stack([signals.voice(24000, 2, seed=310 + s) for s in range(2)])
+    batch_vs_oracle(xs, interp, up, fftsize=fftsize, semitones=semitones)
+
+
+@pytest.mark.parametrize("semitones,interp,up", [(4.0, 1, False), (-7.0, 1, True), (-12.0, 0, True)],
+                         ids=["+4", "-7", "-12"])
+@pytest.mark.parametrize("channels", [1, 2, 3, 5, 6])
+def test_partial_row_groups_streaming(channels, semitones, interp, up):
+    """the exact resampler serves four rows per group (kResRows): 1, 2, 3, 5 and 6 rows leave partial groups"""
+    stream_vs_oracle(signals.voice(20000, channels, seed=79), interp, up, semitones=semitones)
+
+
+@pytest.mark.parametrize("semitones,interp,up", [(4.0, 1, False), (-7.0, 1, True)], ids=["+4", "-7"])
+def test_batch_of_17_mono_streams(semitones, interp, up):
+    xs = np.stack([signals.voice(16000, 1, seed=400 + s) for s in range(17)])
+    assert not bits_equal(xs[0], xs[16])
+    batch_vs_oracle(xs, interp, up, semitones=semitones)
+
+
+RAGGED = [1, 0, 479, 4097, 0, 13, 9000, 480, 480, 7, 0]   # the sizes of test_ragged_and_empty_calls
+
+
+def drive_calls(pv, o, x, calls):
+    """pv: an engine with processInData / getOutSamples / getOutData; o: the oracle.  Per-call counts equal; returns
+    both outputs."""
+    pos, g_all, w_all = 0, [], []
+    for n in calls:
+        blk = x[:, pos:pos + n]
+        pos += n
+        pv.processInData(blk)
+        avail = o.process(blk)
+        assert pv.getOutSamples() == avail
+        g_all.append(pv.getOutData(avail))
+        w_all.append(o.retrieve(avail))
+    return np.concatenate(g_all, 1), np.concatenate(w_all, 1)
+
+
+@pytest.mark.parametrize("channels", [2, 3])
+@pytest.mark.parametrize("name", ["+4_interp_down", "-7_interp_up", "-12_direct_up"])
+def test_ragged_and_empty_calls(name, channels):
+    kw, interp, up = PITCH[name]
+    sizes = RAGGED + RAGGED[::-1]
+    x = signals.voice(sum(sizes), channels, seed=5)
+    pv = E.PhaseVocoder(48000, channels, 1.0, kw["semitones"], E.ROBOTIC, E.PHASE_LOCKED, 2048)
+    o = O.Oracle(channels, mode="robotic", **kw)
+    g, w = drive_calls(pv, o, x, sizes)
+    check_class(o.info(), interp, up)
+    assert g.shape[1] > 20000
+    assert bits_equal(g, w), where(g, w)
+    pv.close()
+
+
+def test_output_overrun_bit_for_bit():
+    """OVERRUN_GPU[5]: robotic 1024 at -9 st, a call so large that the reference drops slices"""
+    from tests.test_gpu_parity import OVERRUN_GPU
+    kw, ch, calls = OVERRUN_GPU[5]
+    assert kw == dict(mode="robotic", fftsize=1024, semitones=-9.0)
+    x = signals.voice(sum(calls), ch, seed=55)
+    pv = E.PhaseVocoder(48000, ch, 1.0, kw["semitones"], E.ROBOTIC, 1, kw["fftsize"])
+    o = O.Oracle(ch, **kw)
+    cap = o.info()["outbuf_capacity"] - 2 * o.info()["fftsize"]
+    pos, g_all, w_all, dropped = 0, [], [], False
+    for n in calls:
+        blk = x[:, pos:pos + n]
+        pos += n
+        pv.processInData(blk)
+        avail = o.process(blk)
+        assert pv.getOutSamples() == avail
+        dropped = dropped or avail >= cap
+        g_all.append(pv.getOutData(avail))
+        w_all.append(o.retrieve(avail))
+    assert dropped
+    check_class(o.info(), 1, True)
+    g, w = np.concatenate(g_all, 1), np.concatenate(w_all, 1)
+    assert g.shape[1] > 0 and bits_equal(g, w), where(g, w)
+    pv.close()
+
+
+def pool_vs_oracles(pool, slots, pitches, kw, classes, frames=36000, block=480):
+    xs = [signals.voice(frames, 2, seed=500 + j) for j in range(len(slots))]
+    orc = [O.Oracle(2, **dict(kw, semitones=p)) for p in pitches]
+    got, want = [[] for _ in slots], [[] for _ in slots]
+    sizes = [block] * (frames // block)
+    sizes[3], sizes[4] = 0, 2 * block   # an empty call and a double one
+    pos = 0
+    for n in sizes:
+        pool.feed({s: xs[j][:, pos:pos + n] for j, s in enumerate(slots)})
+        for j, s in enumerate(slots):
+            avail = orc[j].process(xs[j][:, pos:pos + n])
+            assert pool.available(s) == avail, (j, pos)
+            got[j].append(pool.retrieve(s, avail))
+            want[j].append(orc[j].retrieve(avail))
+        pos += n
+    for j in range(len(slots)):
+        check_class(orc[j].info(), *classes[j])
+        a, b = np.concatenate(got[j], axis=1), np.concatenate(want[j], axis=1)
+        assert b.shape[1] > 12000   # (+12 st halves the length)
+        assert bits_equal(a, b), (j, where(a, b))
+
+
+def test_uniform_pool_slot():
+    kw = dict(mode="robotic", semitones=4.0)
+    pool = E.StreamPool(3, channels=2, **kw)
+    slots = [pool.open() for _ in range(3)]
+    pool_vs_oracles(pool, slots[1:], [4.0, 4.0], kw, [(1, False)] * 2)
+    pool.close_pool()
+
+
+def test_mixed_pool_slots_at_different_pitches():
+    kw = dict(mode="robotic", semitones=0.0)
+    pool = E.StreamPool(3, channels=2, pitch_range=(-12, 12), **kw)
+    pitches = [-7.0, 4.0, 12.0]
+    slots = [pool.open(semitones=p) for p in pitches]
+    pool_vs_oracles(pool, slots, pitches, kw, [(1, True), (1, False), (0, False)])
+    pool.close_pool()
+
+
+# ---- variants chosen by environment variables that the library reads once per process or engine: child processes
+CHILD_CASES = ["+4_interp_down", "-7_interp_up", "+12_direct_down", "-15.8_above_2x_up"]
+
+
+def child_main():
+    """Runs in a child process (the environment selects the path): streaming engine, three channels in ragged calls,
+    and a batch of three distinct streams long enough for many launches, all bit for bit against the oracle."""
+    E.set_arithmetic(E.ARITH_EXACT)
+    min_launches = int(sys.argv[1])
+    n = 0
+    for name in CHILD_CASES:
+        kw, interp, up = PITCH[name]
+        stream_vs_oracle(signals.voice(30000, 2, seed=81), interp, up, **kw)
+        stream_vs_oracle(signals.voice(20000, 3, seed=82), interp, up, block=777, **kw)
+        xs = np.stack([signals.voice(60000, 2, seed=70 + s) for s in range(3)])
+        launches = batch_vs_oracle(xs, interp, up, **kw)
+        assert launches >= min_launches, (name, launches)
+        n += 1
+    for fftsize in (512, 4096, 8192):
+        stream_vs_oracle(signals.voice(30000, 2, seed=83), 1, True, fftsize=fftsize, semitones=-7.0)
+        n += 1
+    print("exact-child ok", n)
+
+
+VARIANTS = {
+    "tile_path": (dict(AUDIOMOD_PV_FUSED="0"), 1),
+    "fused_path": (dict(AUDIOMOD_PV_FUSED="2"), 1),
+    "single_launch_streaming": (dict(AUDIOMOD_PV_STREAM_LAUNCHES="single"), 1),
+    # eight slices per launch and row: the batch is split over many launches (chunk seams in the stream ring); with the
+    # two-chunks-in-flight pipeline allowed and switched off (ROBOTIC has no rotation chain to overlap, so the switch
+    # must not matter)
+    "many_launches_pipeline_on": (dict(AUDIOMOD_PV_CHUNK_SLICES="8", AUDIOMOD_PV_PIPELINE="1"), 10),
+    "many_launches_pipeline_off": (dict(AUDIOMOD_PV_CHUNK_SLICES="8", AUDIOMOD_PV_PIPELINE="0"), 10),
+    "many_launches_tile_path": (dict(AUDIOMOD_PV_CHUNK_SLICES="8", AUDIOMOD_PV_FUSED="0"), 10),
+}
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_path_variants(variant):
+    env, min_launches = VARIANTS[variant]
+    code = "import sys; sys.path.insert(0, %r); from tests import test_parity_exact_gpu as T; T.child_main()" % (ROOT,)
+    r = subprocess.run([sys.executable, "-c", code, str(min_launches)], capture_output=True, text=True,
+                       env=dict(os.environ, **env), timeout=600)
+    assert r.returncode == 0 and "exact-child ok 7" in r.stdout, (r.stdout + r.stderr)[-3000:]
