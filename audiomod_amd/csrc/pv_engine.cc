@@ -3177,4 +3177,583 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
     return PV_OK;
 }
 
+// ---------------------------------------------------------------- mixed batch
+// Streams of different length, pitch and time ratio on the batch path (audiomod_pv.h "Mixed batch").  One Core holds
+// the planes, state and rings of every stream (stream i owns rows [i*C, (i+1)*C), as a pool slot does); every stream
+// has its own Derived, plan_batch() plan and ChainBuilder output, all built and uploaded once, at creation.  A launch
+// group covers slices [g*Tc, (g+1)*Tc) of every stream that still has slices there; its PoolSlot / PoolParams / MbSlot
+// tables are sorted by kernel variant like a mixed pool's feed.
+struct MbVariant { // contiguous table entries of one kernel variant (the sort order of the group's tables)
+    int first, count;
+    int dfc, res, fast, interp;
+    int max_tiles, lds_floats, tab_bytes, max_runs;
+};
+} // extern "C"
+
+struct pv_mbatch {
+    Core core;
+    struct Stream {
+        Derived d;
+        BatchPlan plan;
+        int64_t frames = 0, in_off = 0, out_off = 0;
+        bool fast = false;
+        int tab = -1, lds_floats = 0, tab_bytes = 0;
+    };
+    std::vector<Stream> s; // (sized once: the plans' builders keep references into it)
+    int64_t in_floats = 0, out_floats = 0;
+    struct Group {
+        int64_t table_off = 0, params_off = 0, mb_off = 0;
+        int nslots = 0, max_tn = 0;
+        std::vector<MbVariant> vr;
+    };
+    std::vector<Group> groups;
+    int kernel_launches = 0; // kernels per run
+    size_t max_sinc = 0, tab_stride = 0;
+    DevBuf<char> d_desc;
+    DevBuf<float4> d_tabs;     // the sinc-table arena: one entry per distinct Speex num / den
+    DevBuf<float> mix_stream;  // the overlap-add stream rings when stream 0 itself does not resample
+};
+
+static const char *mb_scope(const pv_config &cfg) {
+    switch (cfg.mode) {
+    case PV_MODE_NORMAL_SHIFT: case PV_MODE_GENDER_CHANGE: case PV_MODE_FORMANT_PRESERVE: case PV_MODE_NORMAL_STRETCH:
+    case PV_MODE_ROBOTIC: break;
+    case PV_MODE_VOCODER_ROSENBERG: case PV_MODE_VOCODER_CHORD:
+        return "mixed batch: the vocoder modes are not supported (their carrier planes are shared by all rows)";
+    case PV_MODE_WHISPER: return "mixed batch: WHISPER is not supported (its phases come from one process-wide random stream)";
+    case PV_MODE_CONSTANT: return "mixed batch: CONSTANT is not supported (its overrun flag is per stream)";
+    case PV_MODE_FORMANT_CEPSTRAL: return "mixed batch: FORMANT_CEPSTRAL is not supported";
+    default: return "mixed batch: unknown mode";
+    }
+    if (cfg.coremode < 0 || cfg.coremode > 2) return "mixed batch: coremodes 0-2 only";
+    const int N = cfg.fftsize > 0 && cfg.fftsize <= 16384 ? next_pow2_i(cfg.fftsize) : 0;
+    if (N < 512 || N > 4096)
+        return "mixed batch: fftsize 512 ... 4096 only (the sizes of the fused synthesis + overlap-add kernel)";
+    return nullptr;
+}
+
+// Everything that can be decided without a device: arguments, scope, every stream's constants and plan, the packing.
+static int mb_plan(const pv_config *cfg, const pv_mbatch_stream *s, int32_t n, int32_t block, int32_t flush,
+                   std::vector<pv_mbatch::Stream> &out) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!cfg || !s) {
+        g_last_error = "mixed batch: null configuration or stream list";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (n < 1 || block < 1) {
+        g_last_error = "mixed batch: nstreams and block must be at least 1";
+        return PV_ERR_INVALID_ARG;
+    }
+    for (int32_t i = 0; i < n; ++i)
+        if (s[i].frames < 1 || !std::isfinite(s[i].time_ratio) || !std::isfinite(s[i].pitch_semitones)) {
+            g_last_error = "mixed batch: stream " + std::to_string(i) +
+                           (s[i].frames < 1 ? ": frames must be at least 1" : ": pitch / time ratio is not a finite number");
+            return PV_ERR_INVALID_ARG;
+        }
+    if (const char *why = mb_scope(*cfg)) {
+        g_last_error = why;
+        return PV_ERR_UNSUPPORTED;
+    }
+    if ((int64_t)n * cfg->channels > 65535) {
+        g_last_error = "mixed batch: nstreams x channels above 65535 (the kernels put the slots on the grid's y / z)";
+        return PV_ERR_UNSUPPORTED;
+    }
+    out.clear();
+    out.resize((size_t)n);
+    const int NR = g_arith == PV_ARITH_FAST ? (cfg->channels <= 2 ? 2 : cfg->channels <= 4 ? 4 : 8) : 4; // launch_mb_resample
+    int64_t in_off = 0, out_off = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        pv_mbatch::Stream &t = out[(size_t)i];
+        pv_config ci = *cfg;
+        ci.time_ratio = s[i].time_ratio;
+        ci.pitch_semitones = s[i].pitch_semitones;
+        int st = derive(ci, t.d);
+        if (st == PV_OK) st = plan_batch(t.d, s[i].frames, block, flush != 0, t.plan);
+        if (st != PV_OK) {
+            const std::string why = g_last_error.empty() ? std::string(plan_reason()) : g_last_error;
+            g_last_error = "mixed batch: stream " + std::to_string(i) + ": the engine refuses this configuration" +
+                           (why.empty() ? std::string() : " (" + why + ")");
+            return st;
+        }
+        const int nc = t.d.fft.nc;
+        if (!(nc == 256 || nc == 512 || nc == 1024 || nc == 2048)) {
+            g_last_error = "mixed batch: fftsize 512 ... 4096 only (the sizes of the fused synthesis + overlap-add kernel)";
+            return PV_ERR_UNSUPPORTED;
+        }
+        if (t.d.resample) {
+            t.lds_floats = pool_res_lds_floats(t.d);
+            t.tab_bytes = pool_res_tab_bytes(t.d);
+            if ((size_t)t.tab_bytes + sizeof(float) * (size_t)t.lds_floats * NR > 160 * 1024 - 512) {
+                g_last_error = "mixed batch: stream " + std::to_string(i) +
+                               ": the resampling kernel's filter table and tile do not fit the LDS at this pitch";
+                return PV_ERR_UNSUPPORTED;
+            }
+        }
+        t.frames = s[i].frames;
+        t.in_off = in_off;
+        t.out_off = out_off;
+        in_off += (int64_t)cfg->channels * t.frames;
+        out_off += (int64_t)cfg->channels * t.plan.out_frames;
+    }
+    return PV_OK;
+}
+
+// kernels one launch group enqueues (mb_launch_group)
+static int mb_group_kernels(const pv_mbatch::Group &g, int cm) {
+    int k = 1 + (cm == 1 ? 2 : cm == 0 ? 1 : 0);
+    for (size_t a = 0; a < g.vr.size(); ++a) {
+        const bool first_of_synth = a == 0 || g.vr[a].dfc != g.vr[a - 1].dfc || g.vr[a].res != g.vr[a - 1].res ||
+                                    g.vr[a].fast != g.vr[a - 1].fast;
+        k += (first_of_synth ? 1 : 0) + (g.vr[a].res && g.vr[a].max_tiles > 0 ? 1 : 0);
+    }
+    return k;
+}
+
+// the stages of one launch group (the fields as Core::launch_chunk sets them, rows = C); launch = false: launch nothing,
+// only ask the launchers whether this configuration fits them (pv_mbatch_create)
+static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const float *d_in, float *d_out, hipStream_t st,
+                           bool launch = true) {
+    const Core &c = b->core;
+    const Derived &d = c.d; // (only what every stream shares: sizes, mode, coremode)
+    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
+    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    auto refused = [](const char *what) {
+        g_last_error = std::string("mixed batch: no ") + what + " kernel for this configuration";
+        return PV_ERR_UNSUPPORTED;
+    };
+    auto launched = [launch](const char *what) -> int {
+        if (!launch) return PV_OK;
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
+    };
+    int rc;
+    PoolLaunch pl{};
+    pl.slots = reinterpret_cast<const PoolSlot *>(b->d_desc.p + g.table_off);
+    pl.desc = b->d_desc.p;
+    pl.out = d_out;
+    pl.nslots = g.nslots;
+    pl.max_tn = g.max_tn;
+    const PoolParams *q = reinterpret_cast<const PoolParams *>(b->d_desc.p + g.params_off);
+    const MbSlot *ms = reinterpret_cast<const MbSlot *>(b->d_desc.p + g.mb_off);
+    if (launch) {
+        AnalyzeArgs aa{};
+        aa.tb = c.tb;
+        aa.ia.in = d_in; // (per slot: MbSlot)
+        aa.ia.mask = ~0ull;
+        aa.hop = d.hop; // (per slot: PoolParams)
+        aa.TR = c.TR;
+        aa.rows = c.C;
+        aa.PKP = c.PKP;
+        aa.find_peaks = cm == 1 ? 1 : 0;
+        aa.split = c.split_analysis ? 1 : 0;
+        aa.mag = c.mag.p;
+        aa.phase = c.phase.p;
+        aa.peaks = c.peaks.p;
+        aa.npk = c.npk.p;
+        if (!launch_mb_analyze(aa, pl, q, ms, st)) return refused("analysis");
+        if ((rc = launched("mixed batch analysis launch")) != PV_OK) return rc;
+    }
+    if (cm == 1) {
+        MatchArgs ma{};
+        ma.N = d.N, ma.hs = d.hs, ma.HP = c.HP, ma.PKP = c.PKP, ma.C = c.C, ma.hop = d.hop, ma.TR = c.TR, ma.rows = c.C;
+        ma.two_pi_hop = d.two_pi_hop;
+        ma.phase = c.phase.p, ma.peaks = c.peaks.p, ma.npk = c.npk.p, ma.recs = c.recs.p, ma.modes = c.modes.p;
+        SeqArgs qa{};
+        qa.N = d.N, qa.hs = d.hs, qa.HP = c.HP, qa.PKP = c.PKP, qa.C = c.C, qa.hop = d.hop, qa.TR = c.TR, qa.rows = c.C;
+        qa.two_pi_hop = d.two_pi_hop;
+        qa.phase = c.phase.p, qa.peaks = c.peaks.p, qa.npk = c.npk.p, qa.recs = c.recs.p, qa.modes = c.modes.p;
+        qa.rot = c.rot.p, qa.outphase = c.outphase.p;
+        qa.st_kind = c.st_kind.p, qa.st_rot = c.st_rot.p, qa.st_po = c.st_po.p;
+        qa.high_prio = 1;
+        if (launch) {
+            launch_mb_match(ma, pl, q, st);
+            if ((rc = launched("mixed batch match launch")) != PV_OK) return rc;
+            if (!launch_mb_seq(qa, pl, q, st)) return refused("rotation chain");
+            if ((rc = launched("mixed batch rotation chain launch")) != PV_OK) return rc;
+        } else if (!pool_phase_supported(d.hs, c.PKP)) { // (the pool's bound: a deeper ring than launch_mb_seq's)
+            return refused("rotation chain");
+        }
+    } else if (cm == 0 && launch) {
+        PropArgs pa{};
+        pa.N = d.N, pa.hs = d.hs, pa.HP = c.HP, pa.C = c.C, pa.hop = d.hop, pa.TR = c.TR, pa.rows = c.C;
+        pa.two_pi_hop = d.two_pi_hop;
+        pa.phase = c.phase.p, pa.outphase = c.outphase.p, pa.st_pp = c.st_pp.p, pa.st_po = c.st_po.p;
+        if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
+        if ((rc = launched("mixed batch propagation launch")) != PV_OK) return rc;
+    }
+    float *stream = c.stream.p ? c.stream.p : b->mix_stream.p;
+    const std::vector<MbVariant> &runs = g.vr;
+    for (size_t a = 0; a < runs.size();) {
+        // the synthesis variant's entries: consecutive, they differ in interp only
+        size_t e = a + 1;
+        while (e < runs.size() && runs[e].dfc == runs[a].dfc && runs[e].res == runs[a].res && runs[e].fast == runs[a].fast) ++e;
+        const MbVariant &ra0 = runs[a];
+        PoolLaunch sub = pl;
+        sub.slots = pl.slots + ra0.first;
+        sub.nslots = runs[e - 1].first + runs[e - 1].count - ra0.first;
+        int max_runs = 1;
+        for (size_t k = a; k < e; ++k) max_runs = std::max(max_runs, runs[k].max_runs);
+        SynthArgs sa{};
+        sa.tb = c.tb;
+        sa.hop = d.hop;
+        sa.C = c.C;
+        sa.two_pi_hop = d.two_pi_hop;
+        sa.do_freq_comp = ra0.dfc;
+        sa.freq_comp = 1;
+        sa.fixed_gain = 1;
+        sa.inv_n = d.inv_n;
+        sa.robotic = d.robotic ? 1 : 0;
+        sa.voc_band_len = -1;
+        sa.coremode = cm < 0 ? 0 : cm;
+        sa.TR = c.TR;
+        sa.rows = c.C;
+        sa.PKP = c.PKP;
+        sa.mag = c.mag.p, sa.phase = c.phase.p, sa.outphase = c.outphase.p, sa.peaks = c.peaks.p, sa.npk = c.npk.p;
+        sa.modes = c.modes.p, sa.rot = c.rot.p, sa.frames = c.frames.p, sa.FR = c.FR;
+        ChainArgs ca{};
+        ca.N = d.N;
+        ca.rows = c.C;
+        ca.C = c.C;
+        ca.AR = c.chain_AR;
+        ca.smask = c.chain_smask;
+        ca.waves = c.chain_waves;
+        ca.runs = 1; // (per slot: MbSlot)
+        ca.st_acc = c.st_acc.p;
+        ca.stream = stream;
+        ca.resample = ra0.res;
+        ca.frames = c.frames.p;
+        ca.FR = c.FR;
+        ca.fast = ra0.fast;
+        if (!launch_mb_synth_chain(sa, ca, sub, q + ra0.first, ms + ra0.first, max_runs, st, launch))
+            return refused("synthesis + overlap-add");
+        if ((rc = launched("mixed batch synthesis + overlap-add launch")) != PV_OK) return rc;
+        for (size_t k = a; k < e && ra0.res; ++k) {
+            const MbVariant &rv = runs[k];
+            if (rv.max_tiles <= 0 && launch) continue; // (dropped or truncated slices only: no output completed)
+            PoolLaunch rs = pl;
+            rs.slots = pl.slots + rv.first;
+            rs.nslots = rv.count;
+            rs.max_tiles = rv.max_tiles;
+            ResArgs ra{};
+            ra.rows = c.C;
+            ra.smask = c.chain_smask;
+            ra.stream = stream;
+            ra.interp = rv.interp;
+            ra.lds_floats = rv.lds_floats; // (the largest of the entries' slots; each slot brings its own set-up)
+            ra.tab_bytes = rv.tab_bytes;
+            ra.fast = rv.fast;
+            if (!launch_mb_resample(ra, rs, q + rv.first, st, launch)) return refused("resampling");
+            if ((rc = launched("mixed batch resampling launch")) != PV_OK) return rc;
+        }
+        a = e;
+    }
+    return PV_OK;
+}
+
+extern "C" {
+
+int pv_mbatch_layout(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
+                     int64_t *out_frames, int64_t *slices, int64_t *in_off, int64_t *out_off, int64_t *in_floats,
+                     int64_t *out_floats) {
+    std::vector<pv_mbatch::Stream> v;
+    const int st = mb_plan(cfg, s, nstreams, block, flush, v);
+    if (st != PV_OK) return st;
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (out_frames) out_frames[i] = v[i].plan.out_frames;
+        if (slices) slices[i] = (int64_t)v[i].plan.slices.size();
+        if (in_off) in_off[i] = v[i].in_off;
+        if (out_off) out_off[i] = v[i].out_off;
+    }
+    if (in_floats) *in_floats = v.back().in_off + (int64_t)cfg->channels * v.back().frames;
+    if (out_floats) *out_floats = v.back().out_off + (int64_t)cfg->channels * v.back().plan.out_frames;
+    return PV_OK;
+}
+
+int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
+                     int device, pv_mbatch **out) {
+    if (out) *out = nullptr;
+    std::unique_ptr<pv_mbatch> b(new pv_mbatch());
+    int st = mb_plan(cfg, s, nstreams, block, flush, b->s);
+    if (st != PV_OK) return st;
+    if (!out) {
+        g_last_error = "mixed batch: null handle pointer";
+        return PV_ERR_INVALID_ARG;
+    }
+    const int n = nstreams, C = cfg->channels, rows = n * C;
+    b->in_floats = b->s.back().in_off + (int64_t)C * b->s.back().frames;
+    b->out_floats = b->s.back().out_off + (int64_t)C * b->s.back().plan.out_frames;
+    // slices per launch and slot: as pv_batch_create sizes its chunks (the fused path's wide ones: every stream here
+    // takes the fused path), AUDIOMOD_PV_CHUNK_SLICES included
+    int Tc = 131072 / rows;
+    if (Tc < 16) Tc = 16;
+    if (Tc > 512) Tc = 512;
+    if (const char *env = getenv("AUDIOMOD_PV_CHUNK_SLICES")) {
+        const int v = atoi(env);
+        if (v >= 4 && v <= 1024) Tc = v;
+    }
+    Core &c = b->core;
+    c.chain_required = true;
+    c.fast_arith = g_arith == PV_ARITH_FAST;
+    int64_t maxT = 0;
+    {
+        int mx = 1; // the overlap-add rings are sized from the advances the plans really contain
+        for (const pv_mbatch::Stream &t : b->s) {
+            for (const SliceRec &r : t.plan.slices) mx = r.adv > mx ? r.adv : mx;
+            maxT = std::max(maxT, (int64_t)t.plan.slices.size());
+        }
+        c.chain_max_adv = mx;
+    }
+    pv_config c0 = *cfg; // (the Core's own constants: stream 0's; only what every stream shares is read from them)
+    c0.time_ratio = s[0].time_ratio;
+    c0.pitch_semitones = s[0].pitch_semitones;
+    st = c.init(c0, device, n, Tc);
+    if (st != PV_OK) return st;
+    // (chain_waves: init takes sixteen waves for a plain stream 0 and twelve otherwise, eight at fft 4096; the per-slot
+    // fused kernels are compiled for at most twelve and their launcher clamps to that, so every variant of the corpus
+    // runs with the same wave count whichever stream comes first)
+    if (!c.use_chain || !c.wave_fft()) {
+        g_last_error = "mixed batch: needs the fused synthesis + overlap-add path (AUDIOMOD_PV_FUSED=0 turns it off)";
+        return PV_ERR_UNSUPPORTED;
+    }
+    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
+    const int cm = bypass ? -1 : ((c.d.cfg.coremode == 1 || c.d.cfg.coremode == 2) ? c.d.cfg.coremode : 0);
+    // the sinc-table arena: streams with the same Speex num / den share an entry
+    struct Tab {
+        uint32_t num, den;
+        const Derived *d;
+    };
+    std::vector<Tab> tabs;
+    size_t max_tab4 = 0;
+    bool any_res = false;
+    for (pv_mbatch::Stream &t : b->s) {
+        t.fast = Core::fast_capable_of(t.d, c.fast_arith);
+        if (!t.d.resample) continue;
+        any_res = true;
+        for (size_t k = 0; k < tabs.size() && t.tab < 0; ++k)
+            if (tabs[k].num == t.d.res_num && tabs[k].den == t.d.res_den) t.tab = (int)k;
+        if (t.tab < 0) {
+            t.tab = (int)tabs.size();
+            tabs.push_back(Tab{t.d.res_num, t.d.res_den, &t.d});
+            b->max_sinc = std::max(b->max_sinc, t.d.sinc.size());
+            if (t.d.interp) max_tab4 = std::max(max_tab4, (size_t)t.d.oversample * (t.d.filt_len + 1));
+        }
+    }
+    if (any_res) {
+        b->tab_stride = (b->max_sinc + 3) / 4 + max_tab4;
+        std::vector<float4> img(tabs.size() * b->tab_stride, make_float4(0, 0, 0, 0));
+        for (size_t k = 0; k < tabs.size(); ++k) {
+            const Derived &d = *tabs[k].d;
+            float4 *e = img.data() + k * b->tab_stride;
+            memcpy(e, d.sinc.data(), d.sinc.size() * sizeof(float));
+            float4 *t4 = e + (b->max_sinc + 3) / 4;
+            if (d.interp) // (as Core::init expands them)
+                for (int off = 0; off < d.oversample; ++off)
+                    for (int j = 0; j < d.filt_len; ++j) {
+                        const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
+                        t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+                    }
+        }
+        if ((st = b->d_tabs.upload(img)) != PV_OK) return st;
+        if (!c.stream.p)
+            if ((st = b->mix_stream.alloc((size_t)c.rows * ((size_t)c.chain_smask + 1))) != PV_OK) return st;
+    }
+    // the descriptors of every (stream, group): phase increments, run lists, run offsets, denominators, resampling
+    // tiles; then each group's tables.  Streams of equal parameters and length share their descriptors.
+    const int G = (int)((maxT + Tc - 1) / Tc);
+    std::vector<int> live((size_t)G, 0); // streams with slices in the group
+    for (const pv_mbatch::Stream &t : b->s)
+        for (int g = 0; (int64_t)g * Tc < (int64_t)t.plan.slices.size(); ++g) ++live[(size_t)g];
+    std::vector<char> blob;
+    {
+        size_t est = 1 << 20;
+        for (const pv_mbatch::Stream &t : b->s)
+            est += t.plan.slices.size() * (sizeof(ChainSlice) * 2 + 64) + (size_t)t.plan.out_frames * 14 +
+                   (t.plan.slices.empty() ? 0 : (size_t)(t.plan.slices.back().P + t.d.N) * 5);
+        blob.reserve(est);
+    }
+    auto put = [&](const void *src, size_t bytes) -> int64_t {
+        const size_t off = (blob.size() + 15) & ~(size_t)15;
+        blob.resize(off + bytes);
+        if (bytes) memcpy(blob.data() + off, src, bytes);
+        return (int64_t)off;
+    };
+    struct Entry {
+        PoolSlot ps;
+        PoolParams q;
+        MbSlot ms;
+        int key;
+    };
+    const char *runs_env = getenv("AUDIOMOD_PV_CHAIN_RUNS"); // tuning knob, as pv_batch_create reads it
+    std::vector<std::vector<Entry>> ent((size_t)G);
+    std::vector<std::vector<Entry>> per_stream((size_t)n);
+    std::vector<int32_t> pinc, ro;
+    std::vector<float> wden, wden_hi;
+    std::vector<ChainSlice> cs;
+    std::vector<ResTile> res_tiles;
+    std::vector<uint2> res_otab;
+    for (int i = 0; i < n; ++i) {
+        pv_mbatch::Stream &t = b->s[(size_t)i];
+        const Derived &sd = t.d;
+        const auto &sl = t.plan.slices;
+        const int64_t T = (int64_t)sl.size();
+        int twin = -1; // an earlier stream with the same constants and length: the same descriptors
+        for (int j = 0; j < i && twin < 0; ++j)
+            if (b->s[(size_t)j].frames == t.frames && s[j].time_ratio == s[i].time_ratio &&
+                s[j].pitch_semitones == s[i].pitch_semitones)
+                twin = j;
+        std::vector<Entry> &mine = per_stream[(size_t)i];
+        if (twin >= 0) {
+            mine = per_stream[(size_t)twin];
+        } else {
+            ChainBuilder cb(sd, c.chain_AR, c.chain_smask);
+            for (int g = 0; (int64_t)g * Tc < T; ++g) {
+                const int64_t t0 = (int64_t)g * Tc;
+                const int Tn = (int)((T - t0) < Tc ? (T - t0) : Tc);
+                const int64_t t1 = t0 + Tn;
+                Entry e{};
+                e.ps.t0 = t0;
+                e.ps.s0 = (int32_t)(t0 % c.TR);
+                e.ps.Tn = Tn;
+                // the slot's own accumulator halves: launch g reads half g & 1 (nothing at the stream's start) and
+                // writes the other
+                e.ps.acc_sel = (g & 1) | (g == 0 ? 2 : 0);
+                pinc.clear();
+                for (int64_t k = t0; k < t1; ++k) pinc.push_back(sl[(size_t)k].phase_inc);
+                e.ps.pinc_off = put(pinc.data(), pinc.size() * sizeof(int32_t));
+                wden.clear(), wden_hi.clear(), cs.clear(), ro.clear();
+                const int64_t k0 = cb.begin_launch(sl[(size_t)t0]);
+                for (int64_t k = t0; k < t1; ++k) cb.add(sl[(size_t)k], t.plan.out_frames, wden, wden_hi);
+                // one workgroup per (row, run): split the slot's slices so that the group fills the chip, by
+                // pv_batch_create's rule for the rows that are live in this group
+                const int live_rows = live[(size_t)g] * C;
+                int runs_wanted = (256 + live_rows - 1) / live_rows;
+                if (live_rows > 256) { // a partly filled last round: best product of occupancy and useful share of a run
+                    const double warm = (double)sd.N / (double)(sd.min_shift > 0 ? sd.min_shift : 1) + 1.0;
+                    double best = 0.0;
+                    for (int r = 1; r <= 8; ++r) {
+                        const double wgs = (double)live_rows * r / 256.0, len = (double)Tn / r;
+                        const double eff = wgs / std::ceil(wgs) * (r == 1 ? 1.0 : len / (len + warm));
+                        if (eff > best + 1e-9) best = eff, runs_wanted = r;
+                    }
+                }
+                if (runs_env) runs_wanted = atoi(runs_env);
+                e.ms.runs = cb.end_launch(runs_wanted > 32 ? 32 : runs_wanted, cs, ro);
+                while (wden.size() & 3) wden.push_back(1.f);
+                for (int k = 0; k < 4; ++k) wden.push_back(1.f);
+                if (t.fast)
+                    for (float &v : wden) v = 1.0f / v;
+                while (ro.size() & 3) ro.push_back(0);
+                e.ps.cs_off = put(cs.data(), cs.size() * sizeof(ChainSlice));
+                e.ps.ro_off = put(ro.data(), ro.size() * sizeof(int32_t));
+                e.ps.wden_off = put(wden.data(), wden.size() * sizeof(float));
+                int64_t ka = sl[(size_t)t0].K0, kb = sl[(size_t)(t1 - 1)].K0 + sl[(size_t)(t1 - 1)].cnt;
+                if (ka > t.plan.out_frames) ka = t.plan.out_frames;
+                if (kb > t.plan.out_frames) kb = t.plan.out_frames;
+                res_tiles.clear(), res_otab.clear();
+                if (sd.resample && kb > ka) build_res_tiles_of(sd, ka, kb, res_tiles, res_otab);
+                e.ps.res_ntiles = (int32_t)res_tiles.size();
+                e.ps.res_off = put(res_tiles.data(), res_tiles.size() * sizeof(ResTile));
+                e.ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
+                e.ps.out_off = k0; // (+ the stream's own offset, below)
+                e.ps.out_stride_row = t.plan.out_frames;
+                e.ps.k_base = k0;
+                e.q.two_pi_hop = sd.two_pi_hop;
+                e.q.hop = sd.hop;
+                e.q.do_freq_comp = sd.do_freq_comp ? 1 : 0;
+                e.q.freq_comp = sd.freq_comp;
+                e.q.fixed_gain = sd.fixed_gain;
+                if (sd.resample) {
+                    e.q.filt_len = sd.filt_len;
+                    e.q.oversample = sd.oversample;
+                    e.q.sinc_len = (int32_t)sd.sinc.size();
+                    e.q.tab_bytes = t.tab_bytes;
+                    e.q.lds_floats = t.lds_floats;
+                    const float4 *te = b->d_tabs.p + (size_t)t.tab * b->tab_stride;
+                    e.q.sinc = reinterpret_cast<const float *>(te);
+                    e.q.tab4 = te + (b->max_sinc + 3) / 4;
+                }
+                // the variant: frequency compensation, resampling, fast kernels, interpolated table (sort order)
+                e.key = ((sd.do_freq_comp ? 1 : 0) << 3) | ((sd.resample ? 1 : 0) << 2) | ((t.fast ? 1 : 0) << 1) |
+                        ((sd.resample && sd.interp) ? 1 : 0);
+                mine.push_back(e);
+            }
+        }
+        for (size_t g = 0; g < mine.size(); ++g) {
+            Entry e = mine[g];
+            e.ps.row0 = i * C;
+            e.ps.out_off += t.out_off;
+            e.ms.in_off = t.in_off;
+            e.ms.frames = t.frames;
+            ent[g].push_back(e);
+        }
+    }
+    b->groups.resize((size_t)G);
+    std::vector<PoolSlot> table;
+    std::vector<PoolParams> params;
+    std::vector<MbSlot> mbs;
+    for (int g = 0; g < G; ++g) {
+        std::vector<Entry> &ev = ent[(size_t)g];
+        // slots of one variant contiguous (stable: stream order otherwise)
+        std::stable_sort(ev.begin(), ev.end(), [](const Entry &x, const Entry &y) { return x.key < y.key; });
+        pv_mbatch::Group &gr = b->groups[(size_t)g];
+        table.clear(), params.clear(), mbs.clear();
+        for (size_t k = 0; k < ev.size(); ++k) {
+            const Entry &e = ev[k];
+            if (k == 0 || e.key != ev[k - 1].key)
+                gr.vr.push_back(MbVariant{(int)k, 0, e.key >> 3 & 1, e.key >> 2 & 1, e.key >> 1 & 1, e.key & 1, 0, 0, 0, 1});
+            MbVariant &r = gr.vr.back();
+            ++r.count;
+            r.max_tiles = std::max(r.max_tiles, (int)e.ps.res_ntiles);
+            r.lds_floats = std::max(r.lds_floats, (int)e.q.lds_floats);
+            r.tab_bytes = std::max(r.tab_bytes, (int)e.q.tab_bytes);
+            r.max_runs = std::max(r.max_runs, (int)e.ms.runs);
+            gr.max_tn = std::max(gr.max_tn, (int)e.ps.Tn);
+            table.push_back(e.ps), params.push_back(e.q), mbs.push_back(e.ms);
+        }
+        gr.nslots = (int)ev.size();
+        gr.table_off = put(table.data(), table.size() * sizeof(PoolSlot));
+        gr.params_off = put(params.data(), params.size() * sizeof(PoolParams));
+        gr.mb_off = put(mbs.data(), mbs.size() * sizeof(MbSlot));
+        b->kernel_launches += mb_group_kernels(gr, cm);
+    }
+    if ((st = b->d_desc.upload(blob)) != PV_OK) return st;
+    for (const pv_mbatch::Group &gr : b->groups) // every variant present against its launcher's limits (launches nothing)
+        if ((st = mb_launch_group(b.get(), gr, nullptr, nullptr, nullptr, false)) != PV_OK) return st;
+    *out = b.release();
+    return PV_OK;
+}
+
+void pv_mbatch_destroy(pv_mbatch *b) { delete b; }
+int32_t pv_mbatch_nstreams(const pv_mbatch *b) { return b ? (int32_t)b->s.size() : -1; }
+static bool mb_index_ok(const pv_mbatch *b, int32_t i) { return b && i >= 0 && (size_t)i < b->s.size(); }
+int64_t pv_mbatch_out_frames(const pv_mbatch *b, int32_t i) { return mb_index_ok(b, i) ? b->s[(size_t)i].plan.out_frames : -1; }
+int64_t pv_mbatch_in_offset(const pv_mbatch *b, int32_t i) { return mb_index_ok(b, i) ? b->s[(size_t)i].in_off : -1; }
+int64_t pv_mbatch_out_offset(const pv_mbatch *b, int32_t i) { return mb_index_ok(b, i) ? b->s[(size_t)i].out_off : -1; }
+int64_t pv_mbatch_in_floats(const pv_mbatch *b) { return b ? b->in_floats : -1; }
+int64_t pv_mbatch_out_floats(const pv_mbatch *b) { return b ? b->out_floats : -1; }
+int32_t pv_mbatch_launches(const pv_mbatch *b) { return b ? (int32_t)b->groups.size() : -1; }
+int32_t pv_mbatch_kernel_launches(const pv_mbatch *b) { return b ? (int32_t)b->kernel_launches : -1; }
+
+int pv_mbatch_get_info(const pv_mbatch *b, int32_t i, pv_info *info) {
+    if (!mb_index_ok(b, i) || !info) return PV_ERR_INVALID_ARG;
+    fill_info(b->s[(size_t)i].d, (int64_t)b->s[(size_t)i].plan.slices.size(), info);
+    return PV_OK;
+}
+
+int pv_mbatch_run(pv_mbatch *b, const float *d_in, float *d_out, void *hip_stream) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!b || !d_in || (!d_out && b->out_floats > 0)) return PV_ERR_INVALID_ARG; // an empty output needs no buffer
+    Core &c = b->core;
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPC(hipSetDevice(c.device));
+    int rc = c.reset_state(st); // every run starts every stream afresh (the accumulator halves restart with the plan's)
+    if (rc != PV_OK) return rc;
+    for (const pv_mbatch::Group &g : b->groups)
+        if ((rc = mb_launch_group(b, g, d_in, d_out, st)) != PV_OK) return rc;
+    HIPC(hipGetLastError());
+    return PV_OK;
+}
+
 } // extern "C"

@@ -364,4 +364,29 @@ bool launch_pmix_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolL
 // lds_floats / tab_bytes of `a`: the largest of the launch's slots (the LDS the launch reserves)
 bool launch_pmix_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch = true);
 
+// ---------------------------------------------------------------------------------------------------------------
+// Mixed batch (pv_mbatch_*): the batch path's long launches with a slot table -- streams of one launch differ in
+// length, pitch and time ratio.  A launch group's tables are PoolSlot and PoolParams as in the mixed pool (built once,
+// at creation) plus MbSlot, parallel to them.  What differs from the pool's per-slot kernels:
+//   - the analysis reads the caller's packed device buffer (slot i: [C][frames_i] at float offset in_off, zeros from
+//     frames_i on), not an ingest ring;
+//   - a slot has up to the batch path's 512 slices per launch: match and rotation chain are two launches, as there;
+//   - the fused synthesis + overlap-add runs one workgroup per (row, run) of a slot, the slot's slices of the launch
+//     split into runs by ChainBuilder::end_launch: PoolSlot::ro_off holds runs + 1 offsets into its run lists.
+// ---------------------------------------------------------------------------------------------------------------
+struct MbSlot {
+    int64_t in_off; // float offset of the slot's channel 0 in the caller's input
+    int64_t frames; // its length: the channel stride, and where the zero flush starts
+    int32_t runs;   // runs of the fused kernel's launch for this slot (>= 1)
+    int32_t pad;
+};
+bool launch_mb_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, const MbSlot *m, hipStream_t st);
+bool launch_mb_match(const MatchArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st);
+bool launch_mb_seq(const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st);
+// max_runs: the largest MbSlot::runs of the launch (grid size)
+bool launch_mb_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q,
+                           const MbSlot *m, int max_runs, hipStream_t st, bool launch = true);
+// the pool's resampling bodies with as many rows per workgroup as a slot has (a.rows = C)
+bool launch_mb_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch = true);
+
 } // namespace pv

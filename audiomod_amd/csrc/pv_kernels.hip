@@ -3876,11 +3876,12 @@ void launch_stream(const StreamArgs &s, hipStream_t st) {
 // as device functions of the row / (tile, row group): the batch kernels keep their source, and so their machine code,
 // exactly as they are.  A change to one of those kernels must be made to its copy here too.
 template <int NC, int kPlainCore, int kRes, bool kFast>
-__device__ __forceinline__ void pool_synth_chain_role(const SynthArgs &s, const ChainArgs &c, const int row, char *smem_raw) {
+__device__ __forceinline__ void pool_synth_chain_role(const SynthArgs &s, const ChainArgs &c, const int row, char *smem_raw,
+                                                      const int run = 0, const bool last_run = true) {
     using W = WF<NC>;
     constexpr int N = 2 * NC, hs = NC, NQ = N / 4, NP = NQ / 64;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    constexpr int run = 0; // a slot's slices of a launch are one run
+    // (the pools: a slot's slices of a launch are one run, run 0; the mixed batch splits them, pv_kernels.h MbSlot)
     // (entry i of the run's list is its i-th slice in order; ChainSlice::tl says which slice of the launch it is)
     const int i_begin = c.run_off[run], i_count = c.run_off[run + 1] - i_begin;
     cf *wlds = reinterpret_cast<cf *>(smem_raw) + wave * W::LDS_CF;
@@ -3916,7 +3917,7 @@ __device__ __forceinline__ void pool_synth_chain_role(const SynthArgs &s, const 
         else if (r == 2) chain_slice_tail<2, NP, kRes, kFast>(c, l, sl, A, skip, row, i, lane);
         else chain_slice_tail<3, NP, kRes, kFast>(c, l, sl, A, skip, row, i, lane);
     }
-    chain_epilogue(c, l, row, true);
+    chain_epilogue(c, l, row, last_run);
 }
 
 template <int kRes> // 1 = direct sinc table, 2 = cubic-interpolated table
@@ -4683,6 +4684,289 @@ bool launch_pmix_resample(const ResArgs &a, const PoolLaunch &p, const PoolParam
         allow_big_lds_dev(pv_pmix_resample_kernel<1>, m1);
         hipLaunchKernelGGL(pv_pmix_resample_kernel<1>, grid, dim3(kTileOut), lds, st, a, p, q);
     }
+    return true;
+}
+
+// --------------------------------------------------------------------------------------------
+// Mixed batch (pv_kernels.h MbSlot): the batch path's long launches over a slot table.  The stages are the device
+// functions the batch and pool kernels call, given the values a single-stream batch of the slot's configuration and
+// length passes as launch-wide arguments, so a slot computes exactly what that batch computes.
+// --------------------------------------------------------------------------------------------
+// analysis: the slot's rows of the caller's packed input ([C][frames] at in_off, zeros from `frames` on), its hop
+__device__ __forceinline__ AnalyzeArgs mb_view(const AnalyzeArgs &a, const PoolSlot &ps, const int hop, const MbSlot &ms) {
+    AnalyzeArgs v = a;
+    const int64_t r = ps.row0;
+    v.t0 = ps.t0, v.s0 = ps.s0, v.Tn = ps.Tn;
+    v.hop = hop;
+    v.ia.in = a.ia.in + ms.in_off;
+    v.ia.stride_c = ms.frames;
+    v.ia.stride_s = 0;
+    v.ia.mask = ~0ull;
+    v.ia.len = ms.frames;
+    v.mag += r * a.TR * a.tb.HP;
+    v.phase += r * a.TR * a.tb.HP;
+    if (a.find_peaks) {
+        v.peaks += r * a.TR * a.PKP;
+        v.npk += r * a.TR;
+    }
+    return v;
+}
+// one wave per frame: workgroup x = tl * C + c, y = slot
+template <int NC> __global__ __launch_bounds__(64) void pv_mb_analyze_wave_kernel(const AnalyzeArgs a, const PoolLaunch p,
+                                                                                 const PoolParams *__restrict__ q,
+                                                                                 const MbSlot *__restrict__ m) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int tl = __builtin_amdgcn_readfirstlane((int)blockIdx.x / a.rows), row = blockIdx.x - tl * a.rows;
+    if (tl >= ps.Tn) return;
+    analyze_wave_role<NC, WF<NC>::LDS_CF * sizeof(cf)>(mb_view(a, ps, q[blockIdx.y].hop, m[blockIdx.y]), row, tl,
+                                                       reinterpret_cast<cf *>(smem_raw));
+}
+__global__ __launch_bounds__(128) void pv_mb_analyze_split_kernel(const AnalyzeArgs a, const PoolLaunch p,
+                                                                   const PoolParams *__restrict__ q,
+                                                                   const MbSlot *__restrict__ m) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int tl = __builtin_amdgcn_readfirstlane((int)blockIdx.x / a.rows), row = blockIdx.x - tl * a.rows;
+    if (tl >= ps.Tn) return;
+    analyze_split_role<WF2048S, WF2048S::LDS_CF * sizeof(cf)>(mb_view(a, ps, q[blockIdx.y].hop, m[blockIdx.y]), row, tl,
+                                                              reinterpret_cast<cf *>(smem_raw));
+}
+
+bool launch_mb_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, const MbSlot *m, hipStream_t st) {
+    const dim3 grid(a.rows * p.max_tn, p.nslots);
+    const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
+    switch (a.tb.nc) {
+    case 256:
+        hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<256>, grid, dim3(64), WF<256>::LDS_CF * sizeof(cf) + atab, st, a, p, q, m);
+        return true;
+    case 512:
+        hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<512>, grid, dim3(64), WF<512>::LDS_CF * sizeof(cf) + atab, st, a, p, q, m);
+        return true;
+    case 1024:
+        hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<1024>, grid, dim3(64), WF<1024>::LDS_CF * sizeof(cf) + atab, st, a, p, q, m);
+        return true;
+    case 2048:
+        if (a.split) {
+            hipLaunchKernelGGL(pv_mb_analyze_split_kernel, grid, dim3(WF2048S::LANES),
+                               WF2048S::LDS_CF * sizeof(cf) + atab + 64, st, a, p, q, m);
+        } else {
+            static unsigned long long big = 0;
+            allow_big_lds_dev(pv_mb_analyze_wave_kernel<2048>, big);
+            hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<2048>, grid, dim3(64), WF<2048>::LDS_CF * sizeof(cf) + atab,
+                               st, a, p, q, m);
+        }
+        return true;
+    default: return false;
+    }
+}
+
+// phase-locked mode, parallel part: four waves, one step of the slot each; grid (steps / 4, C, slots)
+__global__ __launch_bounds__(kMatchThreads) void pv_mb_match_kernel(const MatchArgs m, const PoolLaunch p,
+                                                                    const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.z];
+    const int wave = threadIdx.x >> 6;
+    const int tl = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+    if (tl >= ps.Tn) return; // wave-uniform
+    const int64_t r = ps.row0;
+    MatchArgs mv = m;
+    mv.hop = q[blockIdx.z].hop, mv.two_pi_hop = q[blockIdx.z].two_pi_hop;
+    mv.t0 = ps.t0, mv.s0 = ps.s0, mv.Tn = ps.Tn;
+    mv.phase_inc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    mv.phase += r * m.TR * m.HP;
+    mv.peaks += r * m.TR * m.PKP;
+    mv.npk += r * m.TR;
+    mv.recs += r * m.TR * m.PKP;
+    mv.modes += r * m.TR;
+    match_wave_role(mv, blockIdx.y, tl, smem_raw + (size_t)wave * match_wave_lds(mv.hs, mv.PKP));
+}
+bool launch_mb_match(const MatchArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
+    const size_t lds = 4 * match_wave_lds(a.hs, a.PKP);
+    hipLaunchKernelGGL(pv_mb_match_kernel, dim3((p.max_tn + 3) / 4, a.rows, p.nslots), dim3(kMatchThreads), lds, st, a, p, q);
+    return true;
+}
+
+// ... and the rotation chain: one workgroup per (channel, slot) walks the slot's steps of the launch
+constexpr int kMbSeqDepth = 4; // (launch_seq: four steps ahead where the chain shares its CUs with other rows' workgroups)
+template <int D>
+__global__ __launch_bounds__(1024) void pv_mb_seq_kernel(const SeqArgs a, const PoolLaunch p, const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int64_t r = ps.row0;
+    SeqArgs av = a;
+    av.hop = q[blockIdx.y].hop, av.two_pi_hop = q[blockIdx.y].two_pi_hop;
+    av.t0 = ps.t0, av.s0 = ps.s0, av.Tn = ps.Tn;
+    av.phase_inc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    av.phase += r * a.TR * a.HP;
+    av.peaks += r * a.TR * a.PKP;
+    av.npk += r * a.TR;
+    av.recs += r * a.TR * a.PKP;
+    av.modes += r * a.TR;
+    av.rot += r * a.TR * a.PKP;
+    av.outphase += r * a.TR * a.HP;
+    av.st_kind += r;
+    av.st_rot += r * a.PKP;
+    av.st_po += r * a.hs;
+    if (av.high_prio) __builtin_amdgcn_s_setprio(3);
+    seq_role_ring<D>(av, blockIdx.x, smem_raw);
+}
+static size_t mb_seq_lds(const SeqArgs &a) {
+    return ((seq_lds_bytes(a) + 15) & ~(size_t)15) + (size_t)kMbSeqDepth * seq_threads(a.PKP) * sizeof(PeakRec);
+}
+bool launch_mb_seq(const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
+    if (a.PKP > seq_threads(a.PKP) || mb_seq_lds(a) > 160 * 1024 - 512) return false;
+    static unsigned long long big = 0;
+    allow_big_lds_dev(pv_mb_seq_kernel<kMbSeqDepth>, big);
+    hipLaunchKernelGGL(pv_mb_seq_kernel<kMbSeqDepth>, dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)), mb_seq_lds(a), st, a, p, q);
+    return true;
+}
+
+// fused synthesis + overlap-add: one workgroup per (channel, run, slot).  The launch's slots share do_freq_comp,
+// resample and fast (the variant); each brings its own hop, phase advance, frequency compensation, gain and run lists.
+// Run 0 of a slot reads the slot's carried accumulator half, its last run writes the other one (ChainArgs::acc_sel,
+// per slot: PoolSlot::acc_sel), so no run of one launch can overwrite what another run of it still has to read.
+template <int NC, int kPlainCore, int kRes, bool kFast>
+__global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void pv_mb_synth_chain_kernel(
+    const SynthArgs s, const ChainArgs c, const PoolLaunch p, const PoolParams *__restrict__ q, const MbSlot *__restrict__ m) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const int runs = m[blockIdx.z].runs, run = blockIdx.y;
+    if (run >= runs) return; // workgroup-uniform
+    const PoolSlot ps = p.slots[blockIdx.z];
+    const PoolParams *__restrict__ qs = q + blockIdx.z;
+    const int64_t r = ps.row0;
+    SynthArgs sv = s;
+    sv.hop = qs->hop;
+    sv.two_pi_hop = qs->two_pi_hop;
+    sv.do_freq_comp = qs->do_freq_comp;
+    sv.freq_comp = qs->freq_comp;
+    sv.fixed_gain = qs->fixed_gain;
+    sv.t0 = ps.t0, sv.s0 = ps.s0, sv.Tn = ps.Tn;
+    sv.phase_inc = reinterpret_cast<const int32_t *>(p.desc + ps.pinc_off);
+    const int64_t plane = r * s.TR * s.tb.HP;
+    sv.mag += plane;
+    sv.phase += plane;
+    if (sv.outphase) sv.outphase += plane;
+    if (sv.peaks) sv.peaks += r * s.TR * s.PKP;
+    if (sv.npk) sv.npk += r * s.TR;
+    if (sv.modes) sv.modes += r * s.TR;
+    if (sv.rot) sv.rot += r * s.TR * s.PKP;
+    ChainArgs cv = c;
+    cv.Tn = ps.Tn;
+    cv.t0 = ps.t0;
+    cv.runs = runs;
+    cv.slices = reinterpret_cast<const ChainSlice *>(p.desc + ps.cs_off);
+    cv.run_off = reinterpret_cast<const int32_t *>(p.desc + ps.ro_off);
+    cv.wden = reinterpret_cast<const float *>(p.desc + ps.wden_off);
+    cv.wden_hi = cv.wden;
+    cv.st_acc += 2 * r * c.AR; // [slot][2][C][AR]
+    cv.acc_sel = ps.acc_sel;
+    if (kRes) cv.stream += r * ((int64_t)c.smask + 1);
+    cv.out = p.out + ps.out_off;
+    cv.out_stride_row = ps.out_stride_row;
+    pool_synth_chain_role<NC, kPlainCore, kRes, kFast>(sv, cv, blockIdx.x, smem_raw, run, run == runs - 1);
+}
+
+template <int NC, int kPlainCore>
+static bool launch_mb_synth_chain_res(const SynthArgs &s, const ChainArgs &c_in, const PoolLaunch &p, const PoolParams *q,
+                                      const MbSlot *m, int max_runs, hipStream_t st, bool launch) {
+    const bool use_fast = kPlainCore >= 0 && c_in.fast;
+    const int kMaxThreads = use_fast ? pool_chain_max_threads(NC, kPlainCore, true) : pool_chain_max_threads(NC, kPlainCore, false);
+    ChainArgs c = c_in;
+    if (64 * c.waves > kMaxThreads) c.waves = kMaxThreads / 64;
+    if (c.waves < 1) return false;
+    const size_t lds = chain_lds_bytes(c, NC);
+    if (!launch) return true;
+    const dim3 grid(c.rows, max_runs, p.nslots), block(64 * c.waves);
+    static unsigned long long m0 = 0, m1 = 0, f0 = 0, f1 = 0;
+    if constexpr (kPlainCore >= 0) {
+        if (c.fast) {
+            if (!c.resample) {
+                allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 0, true>, f0);
+                hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 0, true>), grid, block, lds, st, s, c, p, q, m);
+            } else {
+                allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 1, true>, f1);
+                hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 1, true>), grid, block, lds, st, s, c, p, q, m);
+            }
+            return true;
+        }
+    }
+    if (!c.resample) {
+        allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 0, false>, m0);
+        hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 0, false>), grid, block, lds, st, s, c, p, q, m);
+    } else {
+        allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 1, false>, m1);
+        hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 1, false>), grid, block, lds, st, s, c, p, q, m);
+    }
+    return true;
+}
+
+template <int NC>
+static bool launch_mb_synth_chain_nc(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q,
+                                     const MbSlot *m, int max_runs, hipStream_t st, bool launch, bool plain, bool fc_locked) {
+    if constexpr (NC == 1024)
+        if (fc_locked) return launch_mb_synth_chain_res<NC, 3>(s, c, p, q, m, max_runs, st, launch);
+    if (plain && s.coremode == 1) return launch_mb_synth_chain_res<NC, 1>(s, c, p, q, m, max_runs, st, launch);
+    if (plain && s.coremode == 0) return launch_mb_synth_chain_res<NC, 0>(s, c, p, q, m, max_runs, st, launch);
+    if (plain) return launch_mb_synth_chain_res<NC, 2>(s, c, p, q, m, max_runs, st, launch);
+    return launch_mb_synth_chain_res<NC, -1>(s, c, p, q, m, max_runs, st, launch);
+}
+
+// the same choice of specialisation as launch_pmix_synth_chain (s.do_freq_comp: the launch's variant)
+bool launch_mb_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q, const MbSlot *m,
+                           int max_runs, hipStream_t st, bool launch) {
+    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
+    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                           !synth_generic_only() && s.coremode == 1;
+    if (max_runs < 1 || max_runs > 65535) return false;
+    switch (s.tb.nc) {
+    case 256: return launch_mb_synth_chain_nc<256>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
+    case 512: return launch_mb_synth_chain_nc<512>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
+    case 1024: return launch_mb_synth_chain_nc<1024>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
+    case 2048: return launch_mb_synth_chain_nc<2048>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
+    default: return false;
+    }
+}
+
+// resampling: grid (tiles, row groups, slots).  The pool's free-form kernel computes eight rows per workgroup, the
+// missing ones of a slot with fewer channels included (computed, never stored); here a slot's C rows are all a
+// workgroup ever has, so the row count is matched to them.  A row's sum does not depend on the rows beside it.
+template <int kRes, int NR>
+__global__ __launch_bounds__(kTileOut) void pv_mb_resample_fast_kernel(const ResArgs a, const PoolLaunch p,
+                                                                       const PoolParams *__restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    ResArgs v;
+    if (!pmix_res_view(a, p, q, v)) return;
+    pool_resample_fast_role<kRes, NR>(v, blockIdx.x, blockIdx.y, smem_raw);
+}
+template <int NR>
+static void launch_mb_resample_fast_rows(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
+    const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
+    const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
+    static unsigned long long f1 = 0, f2 = 0;
+    if (a.interp) {
+        allow_big_lds_dev(pv_mb_resample_fast_kernel<2, NR>, f2);
+        hipLaunchKernelGGL((pv_mb_resample_fast_kernel<2, NR>), grid, dim3(kTileOut), lds, st, a, p, q);
+    } else {
+        allow_big_lds_dev(pv_mb_resample_fast_kernel<1, NR>, f1);
+        hipLaunchKernelGGL((pv_mb_resample_fast_kernel<1, NR>), grid, dim3(kTileOut), lds, st, a, p, q);
+    }
+}
+bool launch_mb_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch) {
+    if (!a.fast) return launch_pmix_resample(a, p, q, st, launch); // the reference's order: four rows per workgroup
+    const int NR = a.rows <= 2 ? 2 : a.rows <= 4 ? 4 : kPoolResFastRows;
+    if ((size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR > 160 * 1024 - 512) return false;
+    if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
+    if (NR == 2) launch_mb_resample_fast_rows<2>(a, p, q, st);
+    else if (NR == 4) launch_mb_resample_fast_rows<4>(a, p, q, st);
+    else launch_mb_resample_fast_rows<kPoolResFastRows>(a, p, q, st);
     return true;
 }
 

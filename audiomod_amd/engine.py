@@ -7,7 +7,8 @@ package: if the library is missing or no MI355X is visible, construction fails l
 `PhaseVocoder` keeps the method names and call semantics of audiomod::phasevocoder
 (reference include/dafx/phasevocoder.h:42-117, src/phasevocoder/phasevocoder.cc:87-183) so the
 parity tests read like drives of the reference class.  `Batch` is the device-resident throughput
-path (many independent streams), used by bench.py.  `StreamPool` serves many live streams, each with the
+path (many independent streams), used by bench.py; `MixedBatch` is the same path for streams that differ in length,
+pitch and time ratio.  `StreamPool` serves many live streams, each with the
 semantics of a `PhaseVocoder`, with one launch sequence per call for all of them.
 """
 import ctypes as C
@@ -49,6 +50,10 @@ class Info(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MixedStream(C.Structure):
+    _fields_ = [("frames", C.c_int64), ("time_ratio", C.c_float), ("pitch_semitones", C.c_float)]
 
 
 class PoolRange(C.Structure):
@@ -138,6 +143,25 @@ def lib():
     L.pv_pool_last_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.pv_pool_create_mixed.argtypes = [C.POINTER(Config), C.POINTER(PoolRange), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]
     L.pv_pool_open_with.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_int32)]
+    i64p = C.POINTER(C.c_int64)
+    L.pv_mbatch_layout.argtypes = [C.POINTER(Config), C.POINTER(MixedStream), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, i64p, i64p]
+    L.pv_mbatch_create.argtypes = [C.POINTER(Config), C.POINTER(MixedStream), C.c_int32, C.c_int32, C.c_int32, C.c_int,
+                                   C.POINTER(C.c_void_p)]
+    L.pv_mbatch_destroy.argtypes = [C.c_void_p]
+    L.pv_mbatch_nstreams.argtypes = [C.c_void_p]
+    L.pv_mbatch_nstreams.restype = C.c_int32
+    for name in ("pv_mbatch_out_frames", "pv_mbatch_in_offset", "pv_mbatch_out_offset"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int32]
+        getattr(L, name).restype = C.c_int64
+    for name in ("pv_mbatch_in_floats", "pv_mbatch_out_floats"):
+        getattr(L, name).argtypes = [C.c_void_p]
+        getattr(L, name).restype = C.c_int64
+    for name in ("pv_mbatch_launches", "pv_mbatch_kernel_launches"):
+        getattr(L, name).argtypes = [C.c_void_p]
+        getattr(L, name).restype = C.c_int32
+    L.pv_mbatch_get_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Info)]
+    L.pv_mbatch_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -387,6 +411,101 @@ class Batch:
         n = (C.c_int64 * len(KERNELS))()
         _check(self.L.pv_batch_kernel_times(self.h, ms, n), "pv_batch_kernel_times")
         return {KERNELS[k]: (ms[k], n[k]) for k in range(len(KERNELS))}
+
+
+def _mixed_streams(streams):
+    """(frames, semitones, time_ratio) tuples as the C ABI's array"""
+    arr = (MixedStream * max(len(streams), 1))()
+    for i, (frames, semitones, time_ratio) in enumerate(streams):
+        arr[i] = MixedStream(int(frames), float(time_ratio), float(semitones))
+    return arr
+
+
+def mbatch_layout(streams, channels=2, block=480, flush=True, **config):
+    """Host only (works without a GPU): how MixedBatch packs `streams`, a list of (frames, semitones, time_ratio).
+    Returns a dict of out_frames, slices, in_offsets, out_offsets (one entry per stream) and in_floats, out_floats."""
+    cfg = make_config(channels, **config)
+    n = len(streams)
+    a = [np.zeros(max(n, 1), np.int64) for _ in range(4)]
+    fin, fout = C.c_int64(0), C.c_int64(0)
+    _check(lib().pv_mbatch_layout(C.byref(cfg), _mixed_streams(streams), n, block, 1 if flush else 0, a[0].ctypes.data,
+                                  a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, C.byref(fin), C.byref(fout)),
+           "pv_mbatch_layout")
+    keys = ("out_frames", "slices", "in_offsets", "out_offsets")
+    out = {k: [int(x) for x in v[:n]] for k, v in zip(keys, a)}
+    out.update(in_floats=fin.value, out_floats=fout.value)
+    return out
+
+
+class MixedBatch:
+    """Streams of different length, pitch and time ratio on the device-resident throughput path (include/audiomod_pv.h
+    pv_mbatch_*).  `streams` is a list of (frames, semitones, time_ratio); every other setting is shared.  Stream i's
+    output is bit for bit what Batch(1, frames_i, semitones=..., time_ratio=..., ...) writes.  Input and output are
+    packed 1-D float32 CUDA tensors: stream i's [channels, frames_i] at in_offsets[i] (torch.cat of the flattened
+    clips), its [channels, out_frames_i] at out_offsets[i] (split())."""
+
+    def __init__(self, streams, channels=2, block=480, flush=True, device=0, **config):
+        self.L = lib()
+        config.pop("semitones", None), config.pop("time_ratio", None)  # per stream
+        self.cfg = make_config(channels, **config)
+        self.streams = [(int(f), float(s), float(r)) for f, s, r in streams]
+        self.channels, self.device = channels, device
+        self.h = C.c_void_p()
+        _check(self.L.pv_mbatch_create(C.byref(self.cfg), _mixed_streams(self.streams), len(self.streams), block,
+                                       1 if flush else 0, device, C.byref(self.h)), "pv_mbatch_create")
+        n = self.L.pv_mbatch_nstreams(self.h)
+        self.out_frames = [self.L.pv_mbatch_out_frames(self.h, i) for i in range(n)]
+        self.in_offsets = [self.L.pv_mbatch_in_offset(self.h, i) for i in range(n)]
+        self.out_offsets = [self.L.pv_mbatch_out_offset(self.h, i) for i in range(n)]
+        self.in_floats = self.L.pv_mbatch_in_floats(self.h)
+        self.out_floats = self.L.pv_mbatch_out_floats(self.h)
+        self.launches = self.L.pv_mbatch_launches(self.h)  # launch groups per run
+        self.kernel_launches = self.L.pv_mbatch_kernel_launches(self.h)  # kernels per run
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pv_mbatch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def info(self, i):
+        inf = Info()
+        _check(self.L.pv_mbatch_get_info(self.h, int(i), C.byref(inf)), "pv_mbatch_get_info")
+        return inf.as_dict()
+
+    def alloc_out(self):
+        import torch
+        return torch.empty(max(self.out_floats, 1), dtype=torch.float32, device=f"cuda:{self.device}")[:self.out_floats]
+
+    def pack(self, clips):
+        """The packed input tensor of a list of [channels, frames_i] arrays or tensors (host or device)."""
+        import torch
+        parts = []
+        for (frames, _, _), x in zip(self.streams, clips):
+            t = x.to(torch.float32) if torch.is_tensor(x) else torch.tensor(np.asarray(x), dtype=torch.float32)
+            assert tuple(t.shape) == (self.channels, frames)
+            parts.append(t.reshape(-1).to(f"cuda:{self.device}"))
+        return torch.cat(parts)
+
+    def run(self, d_in, d_out=None, stream=None):
+        """d_in: packed 1-D float32 CUDA tensor of in_floats elements.  Asynchronous."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.is_contiguous() and d_in.dim() == 1
+        assert d_in.numel() == self.in_floats
+        if d_out is None:
+            d_out = self.alloc_out()
+        assert d_out.is_cuda and d_out.dtype == torch.float32 and d_out.is_contiguous() and d_out.dim() == 1
+        assert d_out.numel() == self.out_floats
+        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+        _check(self.L.pv_mbatch_run(self.h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out.data_ptr()),
+                                    C.c_void_p(s.cuda_stream)), "pv_mbatch_run")
+        return d_out
+
+    def split(self, d_out):
+        """[channels, out_frames_i] views of the packed output, one per stream."""
+        return [d_out[o:o + self.channels * f].view(self.channels, f) for o, f in zip(self.out_offsets, self.out_frames)]
 
 
 class HostIO:

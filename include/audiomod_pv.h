@@ -242,6 +242,67 @@ int pv_batch_kernel_times(pv_batch *b, double ms[PV_NUM_KERNELS], int64_t launch
 const char *pv_kernel_name(int k);
 
 /* ----------------------------------------------------------------------------------------------
+ * Mixed batch: the batch engine for streams that differ in LENGTH, PITCH and TIME RATIO -- an offline
+ * corpus (augmentation with a random shift and stretch per clip, a folder of files) in one object,
+ * input and output resident in device memory.  cfg fixes sample_rate, channels, mode, coremode, fftsize
+ * and hopsize for every stream; its own time_ratio and pitch_semitones are ignored.  Stream i is, bit
+ * for bit, what pv_batch_create(cfg_i, 1, s[i].frames, block, flush) produces, cfg_i being cfg with
+ * s[i]'s two values, under the pv_set_arithmetic setting at creation: the reference's slice dropping on
+ * output overrun, the flush and the truncation to `frames` apply as they do there.
+ *   Packing is tight, no padding (C = cfg->channels):
+ *   d_in  : stream i's [C][frames_i]     at float offset in_off[i]  = C * (frames_0 + ... + frames_{i-1})
+ *   d_out : stream i's [C][out_frames_i] at float offset out_off[i] = C * (out_frames_0 + ... + out_frames_{i-1})
+ * so a caller concatenates its clips and slices the results.
+ *   pv_mbatch_layout : host only, no device call: per stream the output length, slice count and the two
+ *                      offsets, and the sizes (in floats) of the two packed buffers.  Every output
+ *                      pointer may be NULL.
+ *   pv_mbatch_create : every stream's constants, plan, overlap-add descriptors and resampler tables are
+ *                      built and uploaded here, once (streams with the same Speex rate pair share a
+ *                      table; buffers are sized from the actual streams); AUDIOMOD_PV_CHUNK_SLICES and the
+ *                      tuning knob AUDIOMOD_PV_CHAIN_RUNS are read here as pv_batch_create reads them.  The
+ *                      descriptors are per stream (only streams of equal length, pitch and ratio share
+ *                      them): about 14 bytes of host and device memory per output frame and stream, and
+ *                      a creation time that grows with the corpus' total length.
+ *   pv_mbatch_run    : enqueues all work on `hip_stream` (NULL = the default stream) and returns without
+ *                      synchronising; rebuilds nothing on the host.  Every run starts every stream afresh.
+ * A run is pv_mbatch_launches() launch groups; group g covers slices [g*Tc, (g+1)*Tc) of every stream
+ * that still has slices there (a stream that has ended costs nothing afterwards), and launches each
+ * stage once per kernel variant present (frequency compensation or not, resampling or not, direct or
+ * interpolated table, PV_ARITH_FAST kernels or not) whatever the number of distinct pitches;
+ * pv_mbatch_kernel_launches() is the run's total.
+ * Scope: the stream pool's -- modes NORMAL_SHIFT, GENDER_CHANGE, FORMANT_PRESERVE, NORMAL_STRETCH,
+ * ROBOTIC; coremodes 0-2; fftsize 512 ... 4096; nstreams x channels <= 65535.
+ * Errors, all decided by pv_mbatch_layout and at the top of pv_mbatch_create, before any device call:
+ *   outside the scope                                            PV_ERR_UNSUPPORTED, pv_last_error() starts "mixed batch"
+ *   nstreams < 1, a frames < 1, block < 1, a NaN or infinite
+ *   pitch / time ratio, cfg, s or out NULL                       PV_ERR_INVALID_ARG
+ *   a stream whose cfg_i the engine itself refuses               that status; pv_last_error() names the stream index
+ * -------------------------------------------------------------------------------------------- */
+typedef struct pv_mbatch_stream {
+    int64_t frames;
+    float time_ratio;
+    float pitch_semitones;
+} pv_mbatch_stream;
+typedef struct pv_mbatch pv_mbatch;
+
+int pv_mbatch_layout(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
+                     int64_t *out_frames, int64_t *slices, int64_t *in_off, int64_t *out_off,
+                     int64_t *in_floats, int64_t *out_floats);
+int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
+                     int device, pv_mbatch **out);
+void pv_mbatch_destroy(pv_mbatch *b);
+int32_t pv_mbatch_nstreams(const pv_mbatch *b);
+int64_t pv_mbatch_out_frames(const pv_mbatch *b, int32_t i);   /* -1: bad index */
+int64_t pv_mbatch_in_offset(const pv_mbatch *b, int32_t i);    /* float offsets into d_in / d_out */
+int64_t pv_mbatch_out_offset(const pv_mbatch *b, int32_t i);
+int64_t pv_mbatch_in_floats(const pv_mbatch *b);               /* sizes of the two packed buffers */
+int64_t pv_mbatch_out_floats(const pv_mbatch *b);
+int32_t pv_mbatch_launches(const pv_mbatch *b);                /* launch groups per run */
+int32_t pv_mbatch_kernel_launches(const pv_mbatch *b);         /* kernels per run, all groups */
+int pv_mbatch_get_info(const pv_mbatch *b, int32_t i, pv_info *info);
+int pv_mbatch_run(pv_mbatch *b, const float *d_in, float *d_out, void *hip_stream); /* enqueues, does not synchronise */
+
+/* ----------------------------------------------------------------------------------------------
  * Host-staged many-stream job.  The reference's callers hold their audio in host memory (planar
  * float buffers filled from 16-bit WAV data: main/main.cc:152-162,484-491; main/wavfile.cc:733-755,
  * 1295-1306,1334-1342), so this is the batch engine with the staging included: `nstreams` streams in
