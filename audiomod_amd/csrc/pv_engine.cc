@@ -94,6 +94,10 @@ template <typename T> struct DevBuf {
 #endif
         return PV_OK;
     }
+    void swap(DevBuf &o) {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+    }
     int upload(const std::vector<T> &v) {
         int st = alloc(v.size());
         if (st != PV_OK) return st;
@@ -138,6 +142,10 @@ struct ChainBuilder {
     int64_t launch_k0 = 0; // first output of the current launch (begin_launch)
     std::vector<ChainSlice> launch_cs; // the current launch's slices, in order (end_launch turns them into run lists)
     std::vector<int64_t> launch_P;
+    // the mixed batch's redraw: add() only lays the denominators out (wden_off, wden_count floats so far in the
+    // launch); a kernel computes them (pv_kernels.hip pv_mb_build_wden_kernel)
+    bool count_only = false;
+    int64_t wden_count = 0;
 
     ChainBuilder(const Derived &dd, int ar, int mask) : d(dd), AR(ar), smask(mask) {}
 
@@ -165,19 +173,24 @@ struct ChainBuilder {
         c.adv = r.adv;
         c.flags = r.flags;
         if (r.flags & kSliceUpperChannelsSkip) any_upper_skip = true;
-        live.push_back(Live{r.P, r.flags});
-        // denominators by ring quads: entry 0 belongs to sample P - (P mod 4); entries outside [P, P + adv) are
-        // never used (1.0); every slice starts on a 16-byte boundary
-        while (wden.size() & 3) wden.push_back(1.f), wden_hi.push_back(1.f);
-        c.wden_off = (int32_t)wden.size();
         const int lead = c.acc_pos & 3;
-        for (int i = -lead; i < ((r.adv + lead + 3) & ~3) - lead; ++i) {
-            const bool in = i >= 0 && i < r.adv;
-            wden.push_back(in ? denominator(r.P + i, false) : 1.f);
-            wden_hi.push_back(in && any_upper_skip ? denominator(r.P + i, true) : wden.back());
+        if (count_only) { // the same layout, nothing computed
+            c.wden_off = (int32_t)wden_count;
+            wden_count += (r.adv + lead + 3) & ~3;
+        } else {
+            live.push_back(Live{r.P, r.flags});
+            // denominators by ring quads: entry 0 belongs to sample P - (P mod 4); entries outside [P, P + adv) are
+            // never used (1.0); every slice starts on a 16-byte boundary
+            while (wden.size() & 3) wden.push_back(1.f), wden_hi.push_back(1.f);
+            c.wden_off = (int32_t)wden.size();
+            for (int i = -lead; i < ((r.adv + lead + 3) & ~3) - lead; ++i) {
+                const bool in = i >= 0 && i < r.adv;
+                wden.push_back(in ? denominator(r.P + i, false) : 1.f);
+                wden_hi.push_back(in && any_upper_skip ? denominator(r.P + i, true) : wden.back());
+            }
+            const int64_t Pn = r.P + r.adv;
+            while (!live.empty() && live.front().P + d.N <= Pn) live.pop_front();
         }
-        const int64_t Pn = r.P + r.adv;
-        while (!live.empty() && live.front().P + d.N <= Pn) live.pop_front();
         if (!d.resample) { // the finalised samples are the outputs
             int64_t lo = r.K0, hi = r.K0 + r.cnt;
             if (hi > out_limit) hi = out_limit;
@@ -191,6 +204,7 @@ struct ChainBuilder {
     // the first output of the launch, relative to which k_off counts
     int64_t begin_launch(const SliceRec &first) {
         launch_k0 = first.K0;
+        wden_count = 0;
         launch_cs.clear();
         launch_P.clear();
         return launch_k0;
@@ -780,11 +794,14 @@ int Core::build_tiles(const std::vector<SliceRec> &slices, int64_t t_base, int64
 }
 
 // (the stream pool calls it with each slot's own constants)
-static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab);
+static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab,
+                               bool tiles_only = false);
 void Core::build_res_tiles(int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab) const {
     build_res_tiles_of(d, ka, kb, tiles, otab);
 }
-static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab) {
+// tiles_only: the tile headers alone (the mixed batch's redraw: pv_mb_build_otab_kernel writes the table)
+static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::vector<ResTile> &tiles, std::vector<uint2> &otab,
+                               bool tiles_only) {
     for (int64_t k0 = ka; k0 < kb; k0 += kTileOut) {
         ResTile tl{};
         tl.k0 = k0;
@@ -795,6 +812,7 @@ static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::ve
         tl.n_lo = pos(k0) - d.filt_len + 1;
         tl.n_cnt = (int32_t)(pos(k0 + tl.kcnt - 1) - tl.n_lo + 1);
         tiles.push_back(tl);
+        if (tiles_only) continue;
         // where each output of the tile sits in the stream: last_sample = filt_len/2 + floor(k*num/den),
         // samp_frac_num = (k*num) mod den (closed form of resample.c:548-554 from skip_zeros :1225), and from those
         // the sub-sample offset and the interpolation fraction of resampler_basic_interpolate_single (:494-500)
@@ -3191,15 +3209,33 @@ struct MbVariant { // contiguous table entries of one kernel variant (the sort o
 } // extern "C"
 
 struct pv_mbatch {
-    Core core;
+    // Everything on the device.  A redraw keeps it, growing what the new draw outgrows; only a draw whose largest
+    // overlap-add advance exceeds what the Core's rings were sized for gets a new one (pv_mbatch_redraw).
+    struct Dev {
+        Core core;
+        DevBuf<char> d_desc;       // the descriptor block (n: its capacity)
+        DevBuf<float4> d_tabs;     // the sinc-table arena: one entry per distinct Speex num / den
+        DevBuf<float> mix_stream;  // the overlap-add stream rings when the Core's own stream 0 does not resample
+        struct Tab {
+            uint32_t num, den;
+        };
+        std::vector<Tab> tabs;     // the arena's resident entries, in order
+        size_t sinc4 = 0, tab_stride = 0, tab_cap = 0; // float4s of an entry's sinc part / of an entry; entries allocated
+    };
+    std::unique_ptr<Dev> dev;
+    struct Span { // one per-sample array of one (stream, group) in the descriptor block (pv_mbatch_debug_descriptors)
+        int64_t off, bytes;
+        bool in_blob;
+    };
     struct Stream {
         Derived d;
         BatchPlan plan;
         int64_t frames = 0, in_off = 0, out_off = 0;
         bool fast = false;
         int tab = -1, lds_floats = 0, tab_bytes = 0;
+        std::vector<Span> wden, otab;
     };
-    std::vector<Stream> s; // (sized once: the plans' builders keep references into it)
+    std::vector<Stream> s; // (sized once per draw: the plans' builders keep references into it)
     int64_t in_floats = 0, out_floats = 0;
     struct Group {
         int64_t table_off = 0, params_off = 0, mb_off = 0;
@@ -3208,10 +3244,13 @@ struct pv_mbatch {
     };
     std::vector<Group> groups;
     int kernel_launches = 0; // kernels per run
-    size_t max_sinc = 0, tab_stride = 0;
-    DevBuf<char> d_desc;
-    DevBuf<float4> d_tabs;     // the sinc-table arena: one entry per distinct Speex num / den
-    DevBuf<float> mix_stream;  // the overlap-add stream rings when stream 0 itself does not resample
+    // what creation fixed (a redraw re-reads neither the arithmetic setting nor the environment)
+    pv_config cfg{};
+    int32_t block = 0, flush = 0;
+    int device = 0, arith = PV_ARITH_EXACT, Tc = 0;
+    bool has_runs_knob = false; // AUDIOMOD_PV_CHAIN_RUNS
+    int runs_knob = 0;
+    double plan_us = 0, host_us = 0, device_us = 0; // the last create or redraw (pv_mbatch_last_build_timing)
 };
 
 static const char *mb_scope(const pv_config &cfg) {
@@ -3233,8 +3272,9 @@ static const char *mb_scope(const pv_config &cfg) {
 }
 
 // Everything that can be decided without a device: arguments, scope, every stream's constants and plan, the packing.
+// arith: the pv_set_arithmetic setting the object was or is being created under
 static int mb_plan(const pv_config *cfg, const pv_mbatch_stream *s, int32_t n, int32_t block, int32_t flush,
-                   std::vector<pv_mbatch::Stream> &out) {
+                   std::vector<pv_mbatch::Stream> &out, int arith) {
     g_last_error.clear();
     plan_reason_clear();
     if (!cfg || !s) {
@@ -3261,7 +3301,7 @@ static int mb_plan(const pv_config *cfg, const pv_mbatch_stream *s, int32_t n, i
     }
     out.clear();
     out.resize((size_t)n);
-    const int NR = g_arith == PV_ARITH_FAST ? (cfg->channels <= 2 ? 2 : cfg->channels <= 4 ? 4 : 8) : 4; // launch_mb_resample
+    const int NR = arith == PV_ARITH_FAST ? (cfg->channels <= 2 ? 2 : cfg->channels <= 4 ? 4 : 8) : 4; // launch_mb_resample
     int64_t in_off = 0, out_off = 0;
     for (int32_t i = 0; i < n; ++i) {
         pv_mbatch::Stream &t = out[(size_t)i];
@@ -3314,7 +3354,8 @@ static int mb_group_kernels(const pv_mbatch::Group &g, int cm) {
 // only ask the launchers whether this configuration fits them (pv_mbatch_create)
 static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const float *d_in, float *d_out, hipStream_t st,
                            bool launch = true) {
-    const Core &c = b->core;
+    const Core &c = b->dev->core;
+    const char *desc = b->dev->d_desc.p;
     const Derived &d = c.d; // (only what every stream shares: sizes, mode, coremode)
     const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
     const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
@@ -3329,13 +3370,13 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
     };
     int rc;
     PoolLaunch pl{};
-    pl.slots = reinterpret_cast<const PoolSlot *>(b->d_desc.p + g.table_off);
-    pl.desc = b->d_desc.p;
+    pl.slots = reinterpret_cast<const PoolSlot *>(desc + g.table_off);
+    pl.desc = desc;
     pl.out = d_out;
     pl.nslots = g.nslots;
     pl.max_tn = g.max_tn;
-    const PoolParams *q = reinterpret_cast<const PoolParams *>(b->d_desc.p + g.params_off);
-    const MbSlot *ms = reinterpret_cast<const MbSlot *>(b->d_desc.p + g.mb_off);
+    const PoolParams *q = reinterpret_cast<const PoolParams *>(desc + g.params_off);
+    const MbSlot *ms = reinterpret_cast<const MbSlot *>(desc + g.mb_off);
     if (launch) {
         AnalyzeArgs aa{};
         aa.tb = c.tb;
@@ -3382,7 +3423,7 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
         if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
         if ((rc = launched("mixed batch propagation launch")) != PV_OK) return rc;
     }
-    float *stream = c.stream.p ? c.stream.p : b->mix_stream.p;
+    float *stream = c.stream.p ? c.stream.p : b->dev->mix_stream.p;
     const std::vector<MbVariant> &runs = g.vr;
     for (size_t a = 0; a < runs.size();) {
         // the synthesis variant's entries: consecutive, they differ in interp only
@@ -3451,125 +3492,108 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
     return PV_OK;
 }
 
-extern "C" {
+// What a create or redraw has prepared on the host and has yet to put on the device (mb_prepare -> mb_commit).
+struct MbStage {
+    std::vector<char> blob;     // the host-built part of the descriptor block
+    int64_t dev_bytes = 0;      // the device-built part in front of it (redraw; 0: everything is in the blob)
+    std::vector<MbWdenJob> wjobs;
+    std::vector<MbOtabJob> ojobs;
+    int wblocks = 0, oblocks = 0;
+    int64_t wjobs_off = 0, ojobs_off = 0;
+    // the sinc-table arena after this draw: its entries, geometry, the entries to upload, and a new buffer where the
+    // resident one cannot take them
+    std::vector<pv_mbatch::Dev::Tab> tabs;
+    size_t sinc4 = 0, tab_stride = 0, tab_cap = 0;
+    std::vector<std::pair<int, const Derived *>> tab_uploads;
+    DevBuf<float4> new_tabs;
+    bool replace_tabs = false, any_res = false;
+};
 
-int pv_mbatch_layout(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
-                     int64_t *out_frames, int64_t *slices, int64_t *in_off, int64_t *out_off, int64_t *in_floats,
-                     int64_t *out_floats) {
-    std::vector<pv_mbatch::Stream> v;
-    const int st = mb_plan(cfg, s, nstreams, block, flush, v);
-    if (st != PV_OK) return st;
-    for (size_t i = 0; i < v.size(); ++i) {
-        if (out_frames) out_frames[i] = v[i].plan.out_frames;
-        if (slices) slices[i] = (int64_t)v[i].plan.slices.size();
-        if (in_off) in_off[i] = v[i].in_off;
-        if (out_off) out_off[i] = v[i].out_off;
-    }
-    if (in_floats) *in_floats = v.back().in_off + (int64_t)cfg->channels * v.back().frames;
-    if (out_floats) *out_floats = v.back().out_off + (int64_t)cfg->channels * v.back().plan.out_frames;
-    return PV_OK;
-}
-
-int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
-                     int device, pv_mbatch **out) {
-    if (out) *out = nullptr;
-    std::unique_ptr<pv_mbatch> b(new pv_mbatch());
-    int st = mb_plan(cfg, s, nstreams, block, flush, b->s);
-    if (st != PV_OK) return st;
-    if (!out) {
-        g_last_error = "mixed batch: null handle pointer";
-        return PV_ERR_INVALID_ARG;
-    }
-    const int n = nstreams, C = cfg->channels, rows = n * C;
-    b->in_floats = b->s.back().in_off + (int64_t)C * b->s.back().frames;
-    b->out_floats = b->s.back().out_off + (int64_t)C * b->s.back().plan.out_frames;
-    // slices per launch and slot: as pv_batch_create sizes its chunks (the fused path's wide ones: every stream here
-    // takes the fused path), AUDIOMOD_PV_CHUNK_SLICES included
-    int Tc = 131072 / rows;
-    if (Tc < 16) Tc = 16;
-    if (Tc > 512) Tc = 512;
-    if (const char *env = getenv("AUDIOMOD_PV_CHUNK_SLICES")) {
-        const int v = atoi(env);
-        if (v >= 4 && v <= 1024) Tc = v;
-    }
-    Core &c = b->core;
-    c.chain_required = true;
-    c.fast_arith = g_arith == PV_ARITH_FAST;
-    int64_t maxT = 0;
-    {
-        int mx = 1; // the overlap-add rings are sized from the advances the plans really contain
-        for (const pv_mbatch::Stream &t : b->s) {
-            for (const SliceRec &r : t.plan.slices) mx = r.adv > mx ? r.adv : mx;
-            maxT = std::max(maxT, (int64_t)t.plan.slices.size());
-        }
-        c.chain_max_adv = mx;
-    }
-    pv_config c0 = *cfg; // (the Core's own constants: stream 0's; only what every stream shares is read from them)
-    c0.time_ratio = s[0].time_ratio;
-    c0.pitch_semitones = s[0].pitch_semitones;
-    st = c.init(c0, device, n, Tc);
-    if (st != PV_OK) return st;
-    // (chain_waves: init takes sixteen waves for a plain stream 0 and twelve otherwise, eight at fft 4096; the per-slot
-    // fused kernels are compiled for at most twelve and their launcher clamps to that, so every variant of the corpus
-    // runs with the same wave count whichever stream comes first)
-    if (!c.use_chain || !c.wave_fft()) {
-        g_last_error = "mixed batch: needs the fused synthesis + overlap-add path (AUDIOMOD_PV_FUSED=0 turns it off)";
-        return PV_ERR_UNSUPPORTED;
-    }
-    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
-    const int cm = bypass ? -1 : ((c.d.cfg.coremode == 1 || c.d.cfg.coremode == 2) ? c.d.cfg.coremode : 0);
-    // the sinc-table arena: streams with the same Speex num / den share an entry
-    struct Tab {
+// The sinc-table arena for the draw in b->s: streams with the same Speex num / den share an entry; entries already
+// resident stay where they are and only new rate pairs are uploaded.  Where a new pair does not fit (no free entry, or a
+// longer table than the entries were laid out for) the arena is laid out anew for this draw's pairs, with `slack`
+// times as many entries.
+static int mb_plan_tabs(pv_mbatch *b, bool fast_arith, int slack, MbStage &g) {
+    const pv_mbatch::Dev &dv = *b->dev;
+    struct Need {
         uint32_t num, den;
         const Derived *d;
     };
-    std::vector<Tab> tabs;
-    size_t max_tab4 = 0;
-    bool any_res = false;
+    std::vector<Need> need;
+    size_t max_sinc4 = 0, max_tab4 = 0;
     for (pv_mbatch::Stream &t : b->s) {
-        t.fast = Core::fast_capable_of(t.d, c.fast_arith);
+        t.fast = Core::fast_capable_of(t.d, fast_arith);
+        t.tab = -1;
         if (!t.d.resample) continue;
-        any_res = true;
-        for (size_t k = 0; k < tabs.size() && t.tab < 0; ++k)
-            if (tabs[k].num == t.d.res_num && tabs[k].den == t.d.res_den) t.tab = (int)k;
-        if (t.tab < 0) {
-            t.tab = (int)tabs.size();
-            tabs.push_back(Tab{t.d.res_num, t.d.res_den, &t.d});
-            b->max_sinc = std::max(b->max_sinc, t.d.sinc.size());
-            if (t.d.interp) max_tab4 = std::max(max_tab4, (size_t)t.d.oversample * (t.d.filt_len + 1));
-        }
+        g.any_res = true;
+        bool seen = false;
+        for (const Need &k : need) seen = seen || (k.num == t.d.res_num && k.den == t.d.res_den);
+        if (seen) continue;
+        need.push_back(Need{t.d.res_num, t.d.res_den, &t.d});
+        max_sinc4 = std::max(max_sinc4, (t.d.sinc.size() + 3) / 4);
+        if (t.d.interp) max_tab4 = std::max(max_tab4, (size_t)t.d.oversample * (t.d.filt_len + 1));
     }
-    if (any_res) {
-        b->tab_stride = (b->max_sinc + 3) / 4 + max_tab4;
-        std::vector<float4> img(tabs.size() * b->tab_stride, make_float4(0, 0, 0, 0));
-        for (size_t k = 0; k < tabs.size(); ++k) {
-            const Derived &d = *tabs[k].d;
-            float4 *e = img.data() + k * b->tab_stride;
-            memcpy(e, d.sinc.data(), d.sinc.size() * sizeof(float));
-            float4 *t4 = e + (b->max_sinc + 3) / 4;
-            if (d.interp) // (as Core::init expands them)
-                for (int off = 0; off < d.oversample; ++off)
-                    for (int j = 0; j < d.filt_len; ++j) {
-                        const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
-                        t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
-                    }
+    g.tabs = dv.tabs, g.sinc4 = dv.sinc4, g.tab_stride = dv.tab_stride, g.tab_cap = dv.tab_cap;
+    bool fits = max_sinc4 <= dv.sinc4 && max_tab4 <= dv.tab_stride - dv.sinc4;
+    if (fits)
+        for (const Need &k : need) {
+            bool resident = false;
+            for (const pv_mbatch::Dev::Tab &r : g.tabs) resident = resident || (r.num == k.num && r.den == k.den);
+            if (resident) continue;
+            if (g.tabs.size() >= g.tab_cap) {
+                fits = false;
+                break;
+            }
+            g.tab_uploads.push_back({(int)g.tabs.size(), k.d});
+            g.tabs.push_back(pv_mbatch::Dev::Tab{k.num, k.den});
         }
-        if ((st = b->d_tabs.upload(img)) != PV_OK) return st;
-        if (!c.stream.p)
-            if ((st = b->mix_stream.alloc((size_t)c.rows * ((size_t)c.chain_smask + 1))) != PV_OK) return st;
+    if (!fits) {
+        g.tabs.clear(), g.tab_uploads.clear();
+        for (const Need &k : need) {
+            g.tab_uploads.push_back({(int)g.tabs.size(), k.d});
+            g.tabs.push_back(pv_mbatch::Dev::Tab{k.num, k.den});
+        }
+        g.sinc4 = std::max(max_sinc4, dv.sinc4);
+        g.tab_stride = g.sinc4 + std::max(max_tab4, dv.tab_stride - dv.sinc4);
+        g.tab_cap = need.size() * (size_t)slack;
+        g.replace_tabs = true;
+        const int st = g.new_tabs.alloc(g.tab_cap * g.tab_stride);
+        if (st != PV_OK) return st;
     }
-    // the descriptors of every (stream, group): phase increments, run lists, run offsets, denominators, resampling
-    // tiles; then each group's tables.  Streams of equal parameters and length share their descriptors.
+    for (pv_mbatch::Stream &t : b->s)
+        for (size_t k = 0; k < g.tabs.size() && t.d.resample && t.tab < 0; ++k)
+            if (g.tabs[k].num == t.d.res_num && g.tabs[k].den == t.d.res_den) t.tab = (int)k;
+    return PV_OK;
+}
+
+// The descriptors of every (stream, group) -- phase increments, run lists, run offsets, denominators, resampling
+// tiles -- then each group's tables, for the draw in b->s (mb_plan's) and the Core in b->dev.  Streams of equal
+// parameters and length share their descriptors.  Host work only, apart from the allocation of a new table arena.
+// on_device = false (pv_mbatch_create): everything goes into the blob.  on_device = true (pv_mbatch_redraw): the two
+// per-sample arrays -- denominators and resampler output tables -- are only laid out, in a region in front of the
+// blob, with one job each for the kernels that fill them.
+static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, MbStage &stg) {
+    const Core &c = b->dev->core;
+    const int n = (int)b->s.size(), C = c.C, Tc = b->Tc;
+    int st = mb_plan_tabs(b, c.fast_arith, on_device ? 2 : 1, stg);
+    if (st != PV_OK) return st;
+    const float4 *tab_base = stg.replace_tabs ? stg.new_tabs.p : b->dev->d_tabs.p;
+    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
+    const int cm = bypass ? -1 : ((c.d.cfg.coremode == 1 || c.d.cfg.coremode == 2) ? c.d.cfg.coremode : 0);
+    int64_t maxT = 0;
+    for (const pv_mbatch::Stream &t : b->s) maxT = std::max(maxT, (int64_t)t.plan.slices.size());
     const int G = (int)((maxT + Tc - 1) / Tc);
     std::vector<int> live((size_t)G, 0); // streams with slices in the group
     for (const pv_mbatch::Stream &t : b->s)
         for (int g = 0; (int64_t)g * Tc < (int64_t)t.plan.slices.size(); ++g) ++live[(size_t)g];
-    std::vector<char> blob;
+    std::vector<char> &blob = stg.blob;
     {
         size_t est = 1 << 20;
         for (const pv_mbatch::Stream &t : b->s)
-            est += t.plan.slices.size() * (sizeof(ChainSlice) * 2 + 64) + (size_t)t.plan.out_frames * 14 +
-                   (t.plan.slices.empty() ? 0 : (size_t)(t.plan.slices.back().P + t.d.N) * 5);
+            est += t.plan.slices.size() * (sizeof(ChainSlice) * 2 + 64) +
+                   (on_device ? 0
+                              : (size_t)t.plan.out_frames * 14 +
+                                    (t.plan.slices.empty() ? 0 : (size_t)(t.plan.slices.back().P + t.d.N) * 5));
         blob.reserve(est);
     }
     auto put = [&](const void *src, size_t bytes) -> int64_t {
@@ -3578,16 +3602,22 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
         if (bytes) memcpy(blob.data() + off, src, bytes);
         return (int64_t)off;
     };
+    auto reserve_dev = [&](size_t bytes) -> int64_t { // room in the device-built region (no host copy of it exists)
+        const int64_t off = (stg.dev_bytes + 255) & ~(int64_t)255;
+        stg.dev_bytes = off + (int64_t)bytes;
+        return off;
+    };
     struct Entry {
         PoolSlot ps;
         PoolParams q;
         MbSlot ms;
         int key;
+        bool otab_in_blob;
     };
-    const char *runs_env = getenv("AUDIOMOD_PV_CHAIN_RUNS"); // tuning knob, as pv_batch_create reads it
     std::vector<std::vector<Entry>> ent((size_t)G);
     std::vector<std::vector<Entry>> per_stream((size_t)n);
-    std::vector<int32_t> pinc, ro;
+    std::vector<int32_t> pinc, ro, s_adv, s_wl;
+    std::vector<int64_t> s_P;
     std::vector<float> wden, wden_hi;
     std::vector<ChainSlice> cs;
     std::vector<ResTile> res_tiles;
@@ -3605,8 +3635,22 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
         std::vector<Entry> &mine = per_stream[(size_t)i];
         if (twin >= 0) {
             mine = per_stream[(size_t)twin];
+            t.wden = b->s[(size_t)twin].wden, t.otab = b->s[(size_t)twin].otab;
         } else {
             ChainBuilder cb(sd, c.chain_AR, c.chain_smask);
+            cb.count_only = on_device;
+            // the kernel's 64-bit k * res_num must hold the stream's largest product (the host's is 128 bits wide)
+            const bool otab_on_device =
+                on_device && sd.resample &&
+                ((unsigned __int128)(t.plan.out_frames + kTileOut) * sd.res_num >> 64) == 0;
+            const size_t wj0 = stg.wjobs.size();
+            int64_t p_off = 0, adv_off = 0;
+            if (on_device) { // the per-slice records the denominator kernel reads, for the whole stream
+                s_P.clear(), s_adv.clear(), s_wl.assign((size_t)T, 0);
+                for (const SliceRec &r : sl) s_P.push_back(r.P), s_adv.push_back(r.adv);
+                p_off = put(s_P.data(), s_P.size() * sizeof(int64_t));
+                adv_off = put(s_adv.data(), s_adv.size() * sizeof(int32_t));
+            }
             for (int g = 0; (int64_t)g * Tc < T; ++g) {
                 const int64_t t0 = (int64_t)g * Tc;
                 const int Tn = (int)((T - t0) < Tc ? (T - t0) : Tc);
@@ -3624,6 +3668,9 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
                 wden.clear(), wden_hi.clear(), cs.clear(), ro.clear();
                 const int64_t k0 = cb.begin_launch(sl[(size_t)t0]);
                 for (int64_t k = t0; k < t1; ++k) cb.add(sl[(size_t)k], t.plan.out_frames, wden, wden_hi);
+                if (on_device)
+                    for (int k = 0; k < Tn; ++k)
+                        s_wl[(size_t)(t0 + k)] = cb.launch_cs[(size_t)k].wden_off | (cb.launch_cs[(size_t)k].acc_pos & 3);
                 // one workgroup per (row, run): split the slot's slices so that the group fills the chip, by
                 // pv_batch_create's rule for the rows that are live in this group
                 const int live_rows = live[(size_t)g] * C;
@@ -3637,24 +3684,55 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
                         if (eff > best + 1e-9) best = eff, runs_wanted = r;
                     }
                 }
-                if (runs_env) runs_wanted = atoi(runs_env);
+                if (b->has_runs_knob) runs_wanted = b->runs_knob;
                 e.ms.runs = cb.end_launch(runs_wanted > 32 ? 32 : runs_wanted, cs, ro);
-                while (wden.size() & 3) wden.push_back(1.f);
-                for (int k = 0; k < 4; ++k) wden.push_back(1.f);
-                if (t.fast)
-                    for (float &v : wden) v = 1.0f / v;
                 while (ro.size() & 3) ro.push_back(0);
                 e.ps.cs_off = put(cs.data(), cs.size() * sizeof(ChainSlice));
                 e.ps.ro_off = put(ro.data(), ro.size() * sizeof(int32_t));
-                e.ps.wden_off = put(wden.data(), wden.size() * sizeof(float));
+                if (on_device) { // (every slice's entries are whole quads: no padding before the four trailing ones)
+                    MbWdenJob jb{};
+                    jb.total = (int32_t)(cb.wden_count + 4);
+                    jb.dst_off = e.ps.wden_off = reserve_dev((size_t)jb.total * sizeof(float));
+                    jb.p_off = p_off, jb.adv_off = adv_off;
+                    jb.t0 = (int32_t)t0, jb.Tn = Tn;
+                    jb.first_block = stg.wblocks;
+                    jb.N = sd.N, jb.fast = t.fast ? 1 : 0;
+                    jb.win_gain = sd.win_gain;
+                    stg.wblocks += mb_build_wden_blocks(jb.total);
+                    stg.wjobs.push_back(jb);
+                    t.wden.push_back(pv_mbatch::Span{jb.dst_off, (int64_t)jb.total * (int64_t)sizeof(float), false});
+                } else {
+                    while (wden.size() & 3) wden.push_back(1.f);
+                    for (int k = 0; k < 4; ++k) wden.push_back(1.f);
+                    if (t.fast)
+                        for (float &v : wden) v = 1.0f / v;
+                    e.ps.wden_off = put(wden.data(), wden.size() * sizeof(float));
+                    t.wden.push_back(pv_mbatch::Span{e.ps.wden_off, (int64_t)(wden.size() * sizeof(float)), true});
+                }
                 int64_t ka = sl[(size_t)t0].K0, kb = sl[(size_t)(t1 - 1)].K0 + sl[(size_t)(t1 - 1)].cnt;
                 if (ka > t.plan.out_frames) ka = t.plan.out_frames;
                 if (kb > t.plan.out_frames) kb = t.plan.out_frames;
                 res_tiles.clear(), res_otab.clear();
-                if (sd.resample && kb > ka) build_res_tiles_of(sd, ka, kb, res_tiles, res_otab);
+                if (sd.resample && kb > ka) build_res_tiles_of(sd, ka, kb, res_tiles, res_otab, otab_on_device);
                 e.ps.res_ntiles = (int32_t)res_tiles.size();
                 e.ps.res_off = put(res_tiles.data(), res_tiles.size() * sizeof(ResTile));
-                e.ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
+                e.otab_in_blob = !(otab_on_device && !res_tiles.empty());
+                if (e.otab_in_blob) {
+                    e.ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
+                    t.otab.push_back(pv_mbatch::Span{e.ps.otab_off, (int64_t)(res_otab.size() * sizeof(uint2)), true});
+                } else {
+                    MbOtabJob jb{};
+                    jb.ntiles = (int32_t)res_tiles.size();
+                    const size_t bytes = res_tiles.size() * (size_t)kTileOut * sizeof(uint2);
+                    jb.dst_off = e.ps.otab_off = reserve_dev(bytes);
+                    jb.ka = ka, jb.kb = kb;
+                    jb.res_num = sd.res_num, jb.res_den = sd.res_den;
+                    jb.filt_len = sd.filt_len, jb.oversample = sd.oversample, jb.interp = sd.interp ? 1 : 0;
+                    jb.first_block = stg.oblocks;
+                    stg.oblocks += mb_build_otab_blocks(jb.ntiles);
+                    stg.ojobs.push_back(jb);
+                    t.otab.push_back(pv_mbatch::Span{jb.dst_off, (int64_t)bytes, false});
+                }
                 e.ps.out_off = k0; // (+ the stream's own offset, below)
                 e.ps.out_stride_row = t.plan.out_frames;
                 e.ps.k_base = k0;
@@ -3669,14 +3747,18 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
                     e.q.sinc_len = (int32_t)sd.sinc.size();
                     e.q.tab_bytes = t.tab_bytes;
                     e.q.lds_floats = t.lds_floats;
-                    const float4 *te = b->d_tabs.p + (size_t)t.tab * b->tab_stride;
+                    const float4 *te = tab_base + (size_t)t.tab * stg.tab_stride;
                     e.q.sinc = reinterpret_cast<const float *>(te);
-                    e.q.tab4 = te + (b->max_sinc + 3) / 4;
+                    e.q.tab4 = te + stg.sinc4;
                 }
                 // the variant: frequency compensation, resampling, fast kernels, interpolated table (sort order)
                 e.key = ((sd.do_freq_comp ? 1 : 0) << 3) | ((sd.resample ? 1 : 0) << 2) | ((t.fast ? 1 : 0) << 1) |
                         ((sd.resample && sd.interp) ? 1 : 0);
                 mine.push_back(e);
+            }
+            if (on_device) {
+                const int64_t wl_off = put(s_wl.data(), s_wl.size() * sizeof(int32_t));
+                for (size_t k = wj0; k < stg.wjobs.size(); ++k) stg.wjobs[k].woff_off = wl_off;
             }
         }
         for (size_t g = 0; g < mine.size(); ++g) {
@@ -3688,7 +3770,16 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
             ent[g].push_back(e);
         }
     }
-    b->groups.resize((size_t)G);
+    // the blob follows the device-built region: what points into it moves by the region's size
+    stg.dev_bytes = (stg.dev_bytes + 255) & ~(int64_t)255;
+    const int64_t shift = stg.dev_bytes;
+    for (pv_mbatch::Stream &t : b->s) {
+        for (pv_mbatch::Span &sp : t.wden) sp.off += sp.in_blob ? shift : 0;
+        for (pv_mbatch::Span &sp : t.otab) sp.off += sp.in_blob ? shift : 0;
+    }
+    for (MbWdenJob &jb : stg.wjobs) jb.p_off += shift, jb.adv_off += shift, jb.woff_off += shift;
+    b->groups.assign((size_t)G, pv_mbatch::Group());
+    b->kernel_launches = 0;
     std::vector<PoolSlot> table;
     std::vector<PoolParams> params;
     std::vector<MbSlot> mbs;
@@ -3699,7 +3790,10 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
         pv_mbatch::Group &gr = b->groups[(size_t)g];
         table.clear(), params.clear(), mbs.clear();
         for (size_t k = 0; k < ev.size(); ++k) {
-            const Entry &e = ev[k];
+            Entry &e = ev[k];
+            e.ps.pinc_off += shift, e.ps.cs_off += shift, e.ps.ro_off += shift, e.ps.res_off += shift;
+            if (!on_device) e.ps.wden_off += shift;
+            if (e.otab_in_blob) e.ps.otab_off += shift;
             if (k == 0 || e.key != ev[k - 1].key)
                 gr.vr.push_back(MbVariant{(int)k, 0, e.key >> 3 & 1, e.key >> 2 & 1, e.key >> 1 & 1, e.key & 1, 0, 0, 0, 1});
             MbVariant &r = gr.vr.back();
@@ -3712,16 +3806,250 @@ int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t ns
             table.push_back(e.ps), params.push_back(e.q), mbs.push_back(e.ms);
         }
         gr.nslots = (int)ev.size();
-        gr.table_off = put(table.data(), table.size() * sizeof(PoolSlot));
-        gr.params_off = put(params.data(), params.size() * sizeof(PoolParams));
-        gr.mb_off = put(mbs.data(), mbs.size() * sizeof(MbSlot));
+        gr.table_off = shift + put(table.data(), table.size() * sizeof(PoolSlot));
+        gr.params_off = shift + put(params.data(), params.size() * sizeof(PoolParams));
+        gr.mb_off = shift + put(mbs.data(), mbs.size() * sizeof(MbSlot));
         b->kernel_launches += mb_group_kernels(gr, cm);
     }
-    if ((st = b->d_desc.upload(blob)) != PV_OK) return st;
-    for (const pv_mbatch::Group &gr : b->groups) // every variant present against its launcher's limits (launches nothing)
-        if ((st = mb_launch_group(b.get(), gr, nullptr, nullptr, nullptr, false)) != PV_OK) return st;
+    stg.wjobs_off = shift + put(stg.wjobs.data(), stg.wjobs.size() * sizeof(MbWdenJob));
+    stg.ojobs_off = shift + put(stg.ojobs.data(), stg.ojobs.size() * sizeof(MbOtabJob));
+    return PV_OK;
+}
+
+// every variant present against its launcher's limits (launches nothing)
+static int mb_check_groups(const pv_mbatch *b) {
+    for (const pv_mbatch::Group &gr : b->groups) {
+        const int st = mb_launch_group(b, gr, nullptr, nullptr, nullptr, false);
+        if (st != PV_OK) return st;
+    }
+    return PV_OK;
+}
+
+// Puts what mb_prepare staged on the device: new table-arena entries, the blob, and -- a redraw -- the two build
+// kernels over the region in front of it.  Everything that can fail for lack of memory comes first; nothing resident
+// is written before it.  grow: allocate an eighth more than needed (a redraw's next draw is about as long).
+static int mb_commit(pv_mbatch *b, MbStage &stg, bool grow) {
+    pv_mbatch::Dev &dv = *b->dev;
+    const Core &c = dv.core;
+    int st;
+    const size_t need = (size_t)stg.dev_bytes + stg.blob.size();
+    if (need > dv.d_desc.n || !dv.d_desc.p) {
+        DevBuf<char> fresh;
+        if ((st = fresh.alloc(need + (grow ? need / 8 : 0))) != PV_OK) return st;
+        dv.d_desc.swap(fresh);
+    }
+#ifdef PV_POISON // an entry the builders forget to write shows as NaN / -1, not as the draw before's value
+    else HIPC(hipMemset(dv.d_desc.p, 0xFF, dv.d_desc.n));
+#endif
+    if (stg.any_res && !c.stream.p && !dv.mix_stream.p)
+        if ((st = dv.mix_stream.alloc((size_t)c.rows * ((size_t)c.chain_smask + 1))) != PV_OK) return st;
+    if (stg.replace_tabs) dv.d_tabs.swap(stg.new_tabs);
+    dv.tabs = stg.tabs, dv.sinc4 = stg.sinc4, dv.tab_stride = stg.tab_stride, dv.tab_cap = stg.tab_cap;
+    std::vector<float4> img;
+    for (const auto &up : stg.tab_uploads) {
+        const Derived &d = *up.second;
+        img.assign(dv.tab_stride, make_float4(0, 0, 0, 0));
+        memcpy(img.data(), d.sinc.data(), d.sinc.size() * sizeof(float));
+        float4 *t4 = img.data() + dv.sinc4;
+        if (d.interp) // (as Core::init expands them)
+            for (int off = 0; off < d.oversample; ++off)
+                for (int j = 0; j < d.filt_len; ++j) {
+                    const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
+                    t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+                }
+        HIPC(hipMemcpy(dv.d_tabs.p + (size_t)up.first * dv.tab_stride, img.data(), img.size() * sizeof(float4),
+                       hipMemcpyHostToDevice));
+    }
+    if (!stg.blob.empty())
+        HIPC(hipMemcpy(dv.d_desc.p + stg.dev_bytes, stg.blob.data(), stg.blob.size(), hipMemcpyHostToDevice));
+    launch_mb_build_wden(reinterpret_cast<const MbWdenJob *>(dv.d_desc.p + stg.wjobs_off), (int)stg.wjobs.size(), stg.wblocks,
+                         dv.d_desc.p, c.window.p, nullptr);
+    launch_mb_build_otab(reinterpret_cast<const MbOtabJob *>(dv.d_desc.p + stg.ojobs_off), (int)stg.ojobs.size(), stg.oblocks,
+                         dv.d_desc.p, nullptr);
+    HIPC(hipGetLastError());
+    return PV_OK;
+}
+
+static int mb_chunk_slices(int rows) {
+    // slices per launch and slot: as pv_batch_create sizes its chunks (the fused path's wide ones: every stream here
+    // takes the fused path), AUDIOMOD_PV_CHUNK_SLICES included
+    int Tc = 131072 / rows;
+    if (Tc < 16) Tc = 16;
+    if (Tc > 512) Tc = 512;
+    if (const char *env = getenv("AUDIOMOD_PV_CHUNK_SLICES")) {
+        const int v = atoi(env);
+        if (v >= 4 && v <= 1024) Tc = v;
+    }
+    return Tc;
+}
+
+static int mb_max_adv(const std::vector<pv_mbatch::Stream> &v) {
+    int mx = 1; // the overlap-add rings are sized from the advances the plans really contain
+    for (const pv_mbatch::Stream &t : v)
+        for (const SliceRec &r : t.plan.slices) mx = r.adv > mx ? r.adv : mx;
+    return mx;
+}
+
+// a Core for b's configuration with rings for advances up to max_adv (its own constants: those of stream s0; only what
+// every stream shares is read from them)
+static int mb_init_core(const pv_mbatch *b, pv_mbatch::Dev &dv, const pv_mbatch_stream &s0, int max_adv) {
+    Core &c = dv.core;
+    c.chain_required = true;
+    c.fast_arith = b->arith == PV_ARITH_FAST;
+    c.chain_max_adv = max_adv;
+    pv_config c0 = b->cfg;
+    c0.time_ratio = s0.time_ratio;
+    c0.pitch_semitones = s0.pitch_semitones;
+    const int st = c.init(c0, b->device, (int)b->s.size(), b->Tc);
+    if (st != PV_OK) return st;
+    // (chain_waves: init takes sixteen waves for a plain stream 0 and twelve otherwise, eight at fft 4096; the per-slot
+    // fused kernels are compiled for at most twelve and their launcher clamps to that, so every variant of the corpus
+    // runs with the same wave count whichever stream comes first)
+    if (!c.use_chain || !c.wave_fft()) {
+        g_last_error = "mixed batch: needs the fused synthesis + overlap-add path (AUDIOMOD_PV_FUSED=0 turns it off)";
+        return PV_ERR_UNSUPPORTED;
+    }
+    return PV_OK;
+}
+
+static double mb_us(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::micro>(b - a).count();
+}
+
+extern "C" {
+
+int pv_mbatch_layout(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
+                     int64_t *out_frames, int64_t *slices, int64_t *in_off, int64_t *out_off, int64_t *in_floats,
+                     int64_t *out_floats) {
+    std::vector<pv_mbatch::Stream> v;
+    const int st = mb_plan(cfg, s, nstreams, block, flush, v, g_arith);
+    if (st != PV_OK) return st;
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (out_frames) out_frames[i] = v[i].plan.out_frames;
+        if (slices) slices[i] = (int64_t)v[i].plan.slices.size();
+        if (in_off) in_off[i] = v[i].in_off;
+        if (out_off) out_off[i] = v[i].out_off;
+    }
+    if (in_floats) *in_floats = v.back().in_off + (int64_t)cfg->channels * v.back().frames;
+    if (out_floats) *out_floats = v.back().out_off + (int64_t)cfg->channels * v.back().plan.out_frames;
+    return PV_OK;
+}
+
+int pv_mbatch_create(const pv_config *cfg, const pv_mbatch_stream *s, int32_t nstreams, int32_t block, int32_t flush,
+                     int device, pv_mbatch **out) {
+    if (out) *out = nullptr;
+    const auto t_begin = std::chrono::steady_clock::now();
+    std::unique_ptr<pv_mbatch> b(new pv_mbatch());
+    int st = mb_plan(cfg, s, nstreams, block, flush, b->s, g_arith);
+    if (st != PV_OK) return st;
+    const auto t_planned = std::chrono::steady_clock::now();
+    if (!out) {
+        g_last_error = "mixed batch: null handle pointer";
+        return PV_ERR_INVALID_ARG;
+    }
+    const int C = cfg->channels;
+    b->in_floats = b->s.back().in_off + (int64_t)C * b->s.back().frames;
+    b->out_floats = b->s.back().out_off + (int64_t)C * b->s.back().plan.out_frames;
+    b->cfg = *cfg, b->block = block, b->flush = flush, b->device = device, b->arith = g_arith;
+    b->Tc = mb_chunk_slices(nstreams * C);
+    if (const char *runs_env = getenv("AUDIOMOD_PV_CHAIN_RUNS")) // tuning knob, as pv_batch_create reads it
+        b->has_runs_knob = true, b->runs_knob = atoi(runs_env);
+    b->dev.reset(new pv_mbatch::Dev());
+    if ((st = mb_init_core(b.get(), *b->dev, s[0], mb_max_adv(b->s))) != PV_OK) return st;
+    MbStage stg;
+    if ((st = mb_prepare(b.get(), s, false, stg)) != PV_OK) return st;
+    if ((st = mb_commit(b.get(), stg, false)) != PV_OK) return st;
+    if ((st = mb_check_groups(b.get())) != PV_OK) return st;
+    b->plan_us = mb_us(t_begin, t_planned);
+    b->host_us = mb_us(t_planned, std::chrono::steady_clock::now());
+    b->device_us = 0;
     *out = b.release();
     return PV_OK;
+}
+
+// pv_mbatch_redraw: audiomod_pv.h.  Order: every check first (mb_plan on a staging object, the launchers' limits
+// against the Core the draw will run on), then the device is synchronised -- an earlier run may still read the
+// descriptors -- and only then anything resident is written.
+int pv_mbatch_redraw(pv_mbatch *b, const pv_mbatch_stream *s) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!b || !s) {
+        g_last_error = "mixed batch: null object or stream list";
+        return PV_ERR_INVALID_ARG;
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    std::unique_ptr<pv_mbatch> nb(new pv_mbatch());
+    const int n = (int)b->s.size(), C = b->cfg.channels;
+    int st = mb_plan(&b->cfg, s, n, b->block, b->flush, nb->s, b->arith);
+    if (st != PV_OK) return st;
+    const auto t_planned = std::chrono::steady_clock::now();
+    nb->in_floats = nb->s.back().in_off + (int64_t)C * nb->s.back().frames;
+    nb->out_floats = nb->s.back().out_off + (int64_t)C * nb->s.back().plan.out_frames;
+    nb->cfg = b->cfg, nb->block = b->block, nb->flush = b->flush, nb->device = b->device, nb->arith = b->arith;
+    nb->Tc = b->Tc, nb->has_runs_knob = b->has_runs_knob, nb->runs_knob = b->runs_knob;
+    HIPC(hipSetDevice(b->device));
+    // The Core: kept unless the draw's largest advance exceeds what its rings were sized for; then a new one, sized as
+    // pv_mbatch_create would size it, beside the old one until the checks have passed (the slow path: Core::init again).
+    const int mx = mb_max_adv(nb->s);
+    const bool rebuild = mx > b->dev->core.chain_max_adv;
+    if (rebuild) {
+        nb->dev.reset(new pv_mbatch::Dev());
+        if ((st = mb_init_core(nb.get(), *nb->dev, s[0], mx)) != PV_OK) return st;
+    } else {
+        nb->dev = std::move(b->dev); // (on loan while the draw is prepared and checked)
+    }
+    auto refuse = [&](int status) {
+        if (!rebuild) b->dev = std::move(nb->dev);
+        return status;
+    };
+    MbStage stg;
+    if ((st = mb_prepare(nb.get(), s, true, stg)) != PV_OK) return refuse(st);
+    if ((st = mb_check_groups(nb.get())) != PV_OK) return refuse(st);
+    {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) return refuse(hip_fail(e, "hipDeviceSynchronize", __LINE__));
+    }
+    if ((st = mb_commit(nb.get(), stg, true)) != PV_OK) return refuse(st);
+    const auto t_host = std::chrono::steady_clock::now();
+    {
+        const hipError_t e = hipDeviceSynchronize(); // the build kernels: a run may follow on any stream
+        if (e != hipSuccess) return refuse(hip_fail(e, "mixed batch descriptor build", __LINE__));
+    }
+    const auto t_done = std::chrono::steady_clock::now();
+    b->dev = std::move(nb->dev);
+    b->s = std::move(nb->s);
+    b->groups = std::move(nb->groups);
+    b->in_floats = nb->in_floats, b->out_floats = nb->out_floats, b->kernel_launches = nb->kernel_launches;
+    b->plan_us = mb_us(t_begin, t_planned), b->host_us = mb_us(t_planned, t_host), b->device_us = mb_us(t_host, t_done);
+    return PV_OK;
+}
+
+int pv_mbatch_last_build_timing(const pv_mbatch *b, double *plan_us, double *host_us, double *device_us) {
+    if (!b) return PV_ERR_INVALID_ARG;
+    if (plan_us) *plan_us = b->plan_us;
+    if (host_us) *host_us = b->host_us;
+    if (device_us) *device_us = b->device_us;
+    return PV_OK;
+}
+
+int64_t pv_mbatch_debug_descriptors(const pv_mbatch *b, int32_t stream, int which, void *out, int64_t max_bytes) {
+    g_last_error.clear();
+    if (!b || stream < 0 || (size_t)stream >= b->s.size() || (which != PV_MB_DESC_WDEN && which != PV_MB_DESC_OTAB) ||
+        max_bytes < 0 || (!out && max_bytes > 0))
+        return -(int64_t)PV_ERR_INVALID_ARG;
+    const std::vector<pv_mbatch::Span> &v = which == PV_MB_DESC_WDEN ? b->s[(size_t)stream].wden : b->s[(size_t)stream].otab;
+    int64_t total = 0;
+    for (const pv_mbatch::Span &sp : v) total += sp.bytes;
+    if (hipSetDevice(b->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -(int64_t)PV_ERR_HIP;
+    int64_t done = 0;
+    for (const pv_mbatch::Span &sp : v) {
+        const int64_t take = std::min(sp.bytes, max_bytes - done);
+        if (take <= 0) break;
+        if (hipMemcpy((char *)out + done, b->dev->d_desc.p + sp.off, (size_t)take, hipMemcpyDeviceToHost) != hipSuccess)
+            return -(int64_t)PV_ERR_HIP;
+        done += take;
+    }
+    return total;
 }
 
 void pv_mbatch_destroy(pv_mbatch *b) { delete b; }
@@ -3745,7 +4073,7 @@ int pv_mbatch_run(pv_mbatch *b, const float *d_in, float *d_out, void *hip_strea
     g_last_error.clear();
     plan_reason_clear();
     if (!b || !d_in || (!d_out && b->out_floats > 0)) return PV_ERR_INVALID_ARG; // an empty output needs no buffer
-    Core &c = b->core;
+    Core &c = b->dev->core;
     hipStream_t st = (hipStream_t)hip_stream;
     HIPC(hipSetDevice(c.device));
     int rc = c.reset_state(st); // every run starts every stream afresh (the accumulator halves restart with the plan's)

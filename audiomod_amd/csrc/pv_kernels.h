@@ -389,4 +389,30 @@ bool launch_mb_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLau
 // the pool's resampling bodies with as many rows per workgroup as a slot has (a.rows = C)
 bool launch_mb_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch = true);
 
+// Descriptor build on the device (pv_mbatch_redraw): one job per (stream, group) and array; every offset is a byte
+// offset into the descriptor block.  A job owns the blocks from first_block up to the next job's.
+struct MbWdenJob { // PoolSlot::wden_off's array: the window-sum denominators (reciprocals where `fast`)
+    int64_t dst_off;
+    int64_t p_off, adv_off, woff_off; // the stream's per-slice P (int64), adv and (ChainSlice::wden_off | acc_pos & 3)
+                                      // (int32), indexed by the stream's own slice number: coverage reaches back
+                                      // across group boundaries
+    int32_t t0, Tn;      // the group's slices
+    int32_t total;       // entries: the slices' quads and four trailing ones
+    int32_t first_block;
+    int32_t N, fast;
+    float win_gain;
+    int32_t pad;
+};
+struct MbOtabJob { // PoolSlot::otab_off's array: [ntiles][kTileOut] for outputs [ka, kb)
+    int64_t dst_off;
+    int64_t ka, kb;
+    uint32_t res_num, res_den;
+    int32_t filt_len, oversample, interp;
+    int32_t ntiles, first_block, pad;
+};
+int mb_build_wden_blocks(int total);
+int mb_build_otab_blocks(int ntiles);
+void launch_mb_build_wden(const MbWdenJob *jobs, int njobs, int nblocks, char *desc, const float *window, hipStream_t st);
+void launch_mb_build_otab(const MbOtabJob *jobs, int njobs, int nblocks, char *desc, hipStream_t st);
+
 } // namespace pv

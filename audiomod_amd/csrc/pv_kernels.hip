@@ -4970,4 +4970,123 @@ bool launch_mb_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams 
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Mixed batch, descriptor build on the device (pv_mbatch_redraw): the two per-sample arrays of a stream's descriptors,
+// written in the layout the stage kernels above read, from the per-slice records the host keeps.  One launch serves
+// every (stream, group): block b belongs to the last job whose first_block is at or before it.  A lane writes 16
+// bytes, neighbouring lanes neighbouring addresses.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kMbBuildThreads = 256;
+template <typename Job> __device__ __forceinline__ const Job &mb_build_job(const Job *__restrict__ jobs, int njobs) {
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    return jobs[lo];
+}
+
+// The window-sum denominators, as ChainBuilder::add / ChainBuilder::denominator (pv_engine.cc) compute them: sample n,
+// finalised by slice t, starts at 1 (n == 0) or 0 and adds window[n - P_j] * win_gain for every slice j <= t whose
+// frame covers it, oldest first; product and sum are rounded separately (this file is compiled with
+// -ffp-contract=off, as the host's is; the pragma says so again where it matters).  A lane writes one ring quad, which
+// lies within one slice: every slice's entries start on a 16-byte boundary.
+__global__ __launch_bounds__(kMbBuildThreads) void pv_mb_build_wden_kernel(const MbWdenJob *__restrict__ jobs, int njobs,
+                                                                           char *__restrict__ desc,
+                                                                           const float *__restrict__ window) {
+#pragma clang fp contract(off)
+    const MbWdenJob &jb = mb_build_job(jobs, njobs);
+    const int e0 = 4 * (((int)blockIdx.x - jb.first_block) * kMbBuildThreads + (int)threadIdx.x);
+    if (e0 >= jb.total) return;
+    const int64_t *__restrict__ P = reinterpret_cast<const int64_t *>(desc + jb.p_off);
+    const int32_t *__restrict__ adv = reinterpret_cast<const int32_t *>(desc + jb.adv_off);
+    const int32_t *__restrict__ wl = reinterpret_cast<const int32_t *>(desc + jb.woff_off); // wden_off | lead
+    int a = 0, b = jb.Tn - 1; // the last slice of the group that starts at or before the quad (an empty one never wins)
+    while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if ((wl[jb.t0 + mid] & ~3) <= e0) a = mid;
+        else b = mid - 1;
+    }
+    const int64_t t = (int64_t)jb.t0 + a;
+    const int w = wl[t], av = adv[t], N = jb.N;
+    const int i0 = e0 - (w & ~3) - (w & 3); // entry 0 of the slice belongs to sample P_t - lead
+    const int64_t Pt = P[t];
+    const float g = jb.win_gain;
+    float acc[4];
+    bool in[4], any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        in[j] = i0 + j >= 0 && i0 + j < av;
+        any = any || in[j];
+        acc[j] = Pt + i0 + j == 0 ? 1.f : 0.f;
+    }
+    if (any) {
+        int64_t jlo = t; // P never decreases: no slice before the first one that reaches the quad can cover it
+        while (jlo > 0 && P[jlo - 1] + N > Pt + i0) --jlo;
+        for (int64_t s = jlo; s <= t; ++s) {
+            const int64_t off0 = Pt + i0 - P[s];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t off = off0 + j;
+                if (in[j] && off >= 0 && off < N) {
+                    const float term = window[off] * g;
+                    acc[j] = acc[j] + term;
+                }
+            }
+        }
+    }
+    float4 v;
+    v.x = in[0] ? acc[0] : 1.f, v.y = in[1] ? acc[1] : 1.f, v.z = in[2] ? acc[2] : 1.f, v.w = in[3] ? acc[3] : 1.f;
+    if (jb.fast) v.x = 1.0f / v.x, v.y = 1.0f / v.y, v.z = 1.0f / v.z, v.w = 1.0f / v.w; // IEEE division, as the host's
+    *reinterpret_cast<float4 *>(desc + jb.dst_off + (int64_t)e0 * 4) = v;
+}
+
+// The resampler's output table, as build_res_tiles_of (pv_engine.cc) computes it, in 64-bit arithmetic (the host has
+// checked that the stream's largest k * res_num fits).  A lane writes two entries of one tile.
+__global__ __launch_bounds__(kMbBuildThreads) void pv_mb_build_otab_kernel(const MbOtabJob *__restrict__ jobs, int njobs,
+                                                                           char *__restrict__ desc) {
+    const MbOtabJob &jb = mb_build_job(jobs, njobs);
+    const int64_t e0 = 2 * (((int64_t)blockIdx.x - jb.first_block) * kMbBuildThreads + (int64_t)threadIdx.x);
+    if (e0 >= (int64_t)jb.ntiles * kTileOut) return;
+    const int64_t k0 = jb.ka + (e0 / kTileOut) * kTileOut;
+    const int o = (int)(e0 % kTileOut);
+    const int kcnt = (int)((jb.kb - k0) < kTileOut ? (jb.kb - k0) : kTileOut);
+    const uint64_t num = jb.res_num, den = jb.res_den;
+    const uint64_t q0 = ((uint64_t)k0 * num) / den; // n_lo = filt_len / 2 + q0 - filt_len + 1
+    uint32_t r[4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        r[2 * j] = 0u, r[2 * j + 1] = 0u;
+        if (o + j >= kcnt) continue;
+        const uint64_t tot = (uint64_t)(k0 + o + j) * num;
+        const uint64_t q = tot / den;
+        const uint32_t frac_num = (uint32_t)(tot - q * den);
+        const uint32_t xoff = (uint32_t)(q - q0);
+        uint32_t sub, fbits = 0;
+        if (jb.interp) {
+            const uint32_t ov = (uint32_t)jb.oversample;
+            sub = frac_num * ov / jb.res_den;
+            const float frac = ((float)((frac_num * ov) % jb.res_den)) / (float)jb.res_den;
+            fbits = __float_as_uint(frac);
+        } else {
+            sub = frac_num;
+        }
+        r[2 * j] = xoff | (sub << 16);
+        r[2 * j + 1] = fbits;
+    }
+    *reinterpret_cast<uint4 *>(desc + jb.dst_off + e0 * (int64_t)sizeof(uint2)) = make_uint4(r[0], r[1], r[2], r[3]);
+}
+
+void launch_mb_build_wden(const MbWdenJob *jobs, int njobs, int nblocks, char *desc, const float *window, hipStream_t st) {
+    if (njobs <= 0 || nblocks <= 0) return;
+    hipLaunchKernelGGL(pv_mb_build_wden_kernel, dim3(nblocks), dim3(kMbBuildThreads), 0, st, jobs, njobs, desc, window);
+}
+void launch_mb_build_otab(const MbOtabJob *jobs, int njobs, int nblocks, char *desc, hipStream_t st) {
+    if (njobs <= 0 || nblocks <= 0) return;
+    hipLaunchKernelGGL(pv_mb_build_otab_kernel, dim3(nblocks), dim3(kMbBuildThreads), 0, st, jobs, njobs, desc);
+}
+int mb_build_wden_blocks(int total) { return (total / 4 + kMbBuildThreads - 1) / kMbBuildThreads; }
+int mb_build_otab_blocks(int ntiles) { return (int)(((int64_t)ntiles * kTileOut / 2 + kMbBuildThreads - 1) / kMbBuildThreads); }
+
 } // namespace pv

@@ -162,6 +162,11 @@ def lib():
         getattr(L, name).restype = C.c_int32
     L.pv_mbatch_get_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Info)]
     L.pv_mbatch_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_mbatch_redraw.argtypes = [C.c_void_p, C.POINTER(MixedStream)]
+    f64p = C.POINTER(C.c_double)
+    L.pv_mbatch_last_build_timing.argtypes = [C.c_void_p, f64p, f64p, f64p]
+    L.pv_mbatch_debug_descriptors.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int64]
+    L.pv_mbatch_debug_descriptors.restype = C.c_int64
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -169,6 +174,7 @@ def lib():
 
 
 ARITH_FAST, ARITH_EXACT = 0, 1
+DESC_WDEN, DESC_OTAB = 0, 1  # pv_mbatch_debug_descriptors (PV_MB_DESC_*)
 
 
 def set_arithmetic(arith):
@@ -453,6 +459,10 @@ class MixedBatch:
         self.h = C.c_void_p()
         _check(self.L.pv_mbatch_create(C.byref(self.cfg), _mixed_streams(self.streams), len(self.streams), block,
                                        1 if flush else 0, device, C.byref(self.h)), "pv_mbatch_create")
+        self._refresh()
+
+    def _refresh(self):
+        """the layout the object has now (after creation and after every redraw)"""
         n = self.L.pv_mbatch_nstreams(self.h)
         self.out_frames = [self.L.pv_mbatch_out_frames(self.h, i) for i in range(n)]
         self.in_offsets = [self.L.pv_mbatch_in_offset(self.h, i) for i in range(n)]
@@ -461,6 +471,37 @@ class MixedBatch:
         self.out_floats = self.L.pv_mbatch_out_floats(self.h)
         self.launches = self.L.pv_mbatch_launches(self.h)  # launch groups per run
         self.kernel_launches = self.L.pv_mbatch_kernel_launches(self.h)  # kernels per run
+
+    def redraw(self, streams):
+        """New (frames, semitones, time_ratio) for every stream, in place: afterwards the object is what
+        MixedBatch(streams, ...) with the constructor's other arguments would be -- out_frames, the offsets and the
+        buffer sizes are refreshed, and pack / alloc_out / run / split follow the new layout.  Raises PvError on a
+        refusal, after which the object is unchanged and usable.  Synchronises the device."""
+        streams = [(int(f), float(s), float(r)) for f, s, r in streams]
+        if len(streams) != len(self.streams):
+            raise PvError("MixedBatch.redraw: %d streams for an object of %d" % (len(streams), len(self.streams)))
+        _check(self.L.pv_mbatch_redraw(self.h, _mixed_streams(streams)), "pv_mbatch_redraw")
+        self.streams = streams
+        self._refresh()
+
+    def last_build_timing(self):
+        """The last creation or redraw in microseconds: dict(plan_us, host_us, device_us) -- planning, the other host
+        work up to and including the uploads, the wait for the device build (0 after a creation)."""
+        v = [C.c_double(0) for _ in range(3)]
+        _check(self.L.pv_mbatch_last_build_timing(self.h, *[C.byref(x) for x in v]), "pv_mbatch_last_build_timing")
+        return dict(plan_us=v[0].value, host_us=v[1].value, device_us=v[2].value)
+
+    def debug_descriptors(self, i, which):
+        """Diagnostics: stream i's denominators (which = DESC_WDEN) or resampler output table (DESC_OTAB) as a uint32
+        array, copied back from the device."""
+        size = self.L.pv_mbatch_debug_descriptors(self.h, int(i), int(which), None, 0)
+        _check(int(-size) if size < 0 else 0, "pv_mbatch_debug_descriptors")
+        out = np.zeros(size // 4, np.uint32)
+        if size:
+            got = self.L.pv_mbatch_debug_descriptors(self.h, int(i), int(which), out.ctypes.data, size)
+            _check(int(-got) if got < 0 else 0, "pv_mbatch_debug_descriptors")
+            assert got == size
+        return out
 
     def close(self):
         if getattr(self, "h", None):

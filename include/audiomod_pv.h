@@ -277,6 +277,31 @@ const char *pv_kernel_name(int k);
  *   nstreams < 1, a frames < 1, block < 1, a NaN or infinite
  *   pitch / time ratio, cfg, s or out NULL                       PV_ERR_INVALID_ARG
  *   a stream whose cfg_i the engine itself refuses               that status; pv_last_error() names the stream index
+ *
+ * Re-drawing in place (augmentation draws new values every epoch or step):
+ *   pv_mbatch_redraw : gives every stream a new length, pitch and time ratio; `s` has pv_mbatch_nstreams(b)
+ *                      entries.  cfg, block, flush, the device, the pv_set_arithmetic setting and the two
+ *                      environment knobs stay as creation found them (they are not read again).  After PV_OK
+ *                      the object is what pv_mbatch_create(cfg, s, nstreams, block, flush, device) would have
+ *                      returned: every accessor returns the same value and pv_mbatch_run writes the same bits.
+ *                      All or nothing: every check of the table above, the resampler's LDS fit and the
+ *                      launchers' limits run before anything in the object changes; a refused redraw returns
+ *                      that status and the object runs exactly as before.  (PV_ERR_HIP from an allocation is
+ *                      reported the same way; from a copy or kernel after that, the descriptors are undefined.)
+ *                      Per-slice and per-tile records are planned on the host; the per-sample arrays
+ *                      (window-sum denominators, resampler output tables) are written by two kernels on the
+ *                      device.  Buffers grow and never shrink; only a draw whose largest overlap-add advance
+ *                      exceeds what the rings were sized for re-initialises the engine core (slow path).
+ *                      Synchronises the device before it writes (an earlier pv_mbatch_run may still be in
+ *                      flight on any stream) and again before it returns.
+ *   pv_mbatch_last_build_timing : the last create or redraw in three parts, microseconds: planning (per-stream
+ *                      constants and plans), the other host work up to and including the uploads, and the
+ *                      wait for the device build (0 after a create).  Any pointer may be NULL.
+ *   pv_mbatch_debug_descriptors : copies one per-stream descriptor array back from the device, at most
+ *                      max_bytes of it, and returns its whole length in bytes (or minus a PV_ERR_ status).
+ *                      PV_MB_DESC_WDEN: the stream's denominators, launch group after launch group, as the
+ *                      kernels read them (reciprocals for a PV_ARITH_FAST stream, padding included);
+ *                      PV_MB_DESC_OTAB: its resampler output table, likewise.
  * -------------------------------------------------------------------------------------------- */
 typedef struct pv_mbatch_stream {
     int64_t frames;
@@ -301,6 +326,11 @@ int32_t pv_mbatch_launches(const pv_mbatch *b);                /* launch groups 
 int32_t pv_mbatch_kernel_launches(const pv_mbatch *b);         /* kernels per run, all groups */
 int pv_mbatch_get_info(const pv_mbatch *b, int32_t i, pv_info *info);
 int pv_mbatch_run(pv_mbatch *b, const float *d_in, float *d_out, void *hip_stream); /* enqueues, does not synchronise */
+int pv_mbatch_redraw(pv_mbatch *b, const pv_mbatch_stream *s);
+int pv_mbatch_last_build_timing(const pv_mbatch *b, double *plan_us, double *host_us, double *device_us);
+#define PV_MB_DESC_WDEN 0
+#define PV_MB_DESC_OTAB 1
+int64_t pv_mbatch_debug_descriptors(const pv_mbatch *b, int32_t stream, int which, void *out, int64_t max_bytes);
 
 /* ----------------------------------------------------------------------------------------------
  * Host-staged many-stream job.  The reference's callers hold their audio in host memory (planar
