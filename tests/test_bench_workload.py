@@ -171,7 +171,9 @@ def test_host_staged_path_equals_device_resident(wire):
     """pv_hostio_*: streams held in host memory, staged in groups through the GPU (copy-in / kernels / copy-out
     overlapped).  float32 on the wire: bit-equal to the device-resident batch.  int16 on the wire: equal to the
     reference's WAV writer conversion (saturate(x * 32768) truncated, main/wavfile.cc:1334-1342) of that output.
-    11 streams in groups of 4: three full groups in flight and a short last one."""
+    11 streams in groups of 4: two full groups and a short last one -- three groups for three buffer slots, so no
+    slot is reused here and none of the reuse waits of pv_hostio_run executes; tests/test_hostio_gpu.py holds those
+    (eight groups, both wires, saturating int16 output, stale rows)."""
     import torch
 
     from audiomod_amd import engine as E
