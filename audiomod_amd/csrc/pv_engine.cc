@@ -1252,6 +1252,7 @@ struct pv_batch {
     hipStream_t res_stream = nullptr;   // fused path, resampling configurations: the resampling kernel's stream
     hipEvent_t ev_fused[4] = {}, ev_res[4] = {};
     int timing = 0; // 0 = off, n = instrument every n-th chunk
+    int64_t next_span = -1; // pv_batch_run_span: the launch the next span must start with (-1: only a first span may follow)
     std::vector<hipEvent_t> ev_pool; // kEvPerChunk per instrumented chunk
     std::vector<int> ev_chunk;       // chunk index of each used pool segment
     size_t ev_used = 0;
@@ -1462,22 +1463,8 @@ int pv_batch_create(const pv_config *cfg, int32_t nstreams, int64_t frames, int3
     if (!cfg || !out || nstreams < 1 || frames < 1 || block < 1) return PV_ERR_INVALID_ARG;
     *out = nullptr;
     std::unique_ptr<pv_batch> b(new pv_batch());
-    const int rows = nstreams * cfg->channels;
-    // slices per launch and row: 64 K slices per launch amortise the launch's fixed costs and tail (measured:
-    // +8 % over 16 K with 256 rows; flat beyond), and the planes of such a chunk are a few GB of the 288
-    // Round 2, fused path (192 rows and up): 128 K slices per launch, up to 512 per row -- half as many kernel
-    // boundaries (each a drain and a refill of the chip): 52.0 vs 52.9 ms per bench step; 768 per row: no further gain.
-    // Round 3: with PV_ARITH_FAST every wave-FFT configuration that has a free-form kernel takes the fused path at
-    // any row count (Core::fast_capable), and the wide chunks with it (8-95 streams: +5...20 % over the tile path).
-    const bool fast_wave = g_arith == PV_ARITH_FAST && (cfg->fftsize > 256 && cfg->fftsize <= 4096);
-    const bool wide = rows >= 192 || fast_wave;
-    int Tc = (wide ? 131072 : 65536) / (rows > 0 ? rows : 1);
-    if (Tc < 16) Tc = 16;
-    if (Tc > (wide ? 512 : 256)) Tc = wide ? 512 : 256;
-    if (const char *env = getenv("AUDIOMOD_PV_CHUNK_SLICES")) { // tuning knob: slices per launch and row
-        const int v = atoi(env);
-        if (v >= 4 && v <= 1024) Tc = v;
-    }
+    // slices per launch and row (pv_plan.cc: the span planner uses the same rule)
+    const int Tc = batch_chunk_slices(*cfg, nstreams, g_arith == PV_ARITH_FAST);
     b->core.pipelined_planes = Core::pipeline_wanted(*cfg);
     b->core.fast_arith = g_arith == PV_ARITH_FAST;
     int st;
@@ -1660,21 +1647,14 @@ int pv_batch_enable_timing(pv_batch *b, int on) {
     return PV_OK;
 }
 
-int pv_batch_run(pv_batch *b, const float *d_in, float *d_out, void *hip_stream) {
-    g_last_error.clear();
-    plan_reason_clear();
-    if (!b || !d_in || (!d_out && b->plan.out_frames > 0)) return PV_ERR_INVALID_ARG; // an empty output needs no buffer
+// Enqueues launches [first, first + count) of the batch on `st`.  ia addresses the input rows; `out` is where output
+// frame k_base of row 0 goes, rows out_stride_row floats apart.  The whole job (pv_batch_run) and a span
+// (pv_batch_run_span) differ only in these addresses and in the range: inside it the order is the same, the software
+// pipeline fills at its first launch and drains at its last.  timed: pv_batch_enable_timing's events (whole runs only).
+static int batch_enqueue(pv_batch *b, const InAddr &ia, float *d_out, int64_t out_stride_row, int64_t k_base,
+                         size_t first, size_t count, hipStream_t st, bool timed) {
     Core &c = b->core;
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPC(hipSetDevice(c.device));
-    int rc = c.reset_state(st);
-    if (rc != PV_OK) return rc;
-    InAddr ia;
-    ia.in = d_in;
-    ia.stride_c = b->frames;
-    ia.stride_s = b->frames * c.C;
-    ia.mask = ~0ull;
-    ia.len = b->frames;
+    int rc;
     // Instrumentation: HIP events around each kernel of every `timing`-th chunk.  An event record costs a few
     // microseconds of stream time, so instrumenting every launch would slow the run it measures by ~10 %.
     InAddr car{};
@@ -1690,7 +1670,7 @@ int pv_batch_run(pv_batch *b, const float *d_in, float *d_out, void *hip_stream)
     // (indices first, pointers after the pool has stopped growing: a pointer into ev_pool taken before a later
     // push_back would dangle)
     std::vector<long> ev_index(b->chunks.size(), -1);
-    for (size_t ci = 0; ci < b->chunks.size(); ++ci) {
+    for (size_t ci = first; timed && ci < first + count; ++ci) {
         if (!(b->timing > 0 && (int)(ci % (size_t)b->timing) == (b->timing / 2) % b->timing)) continue;
         const size_t need = b->ev_used + kEvPerChunk;
         bool ok = true;
@@ -1728,17 +1708,18 @@ int pv_batch_run(pv_batch *b, const float *d_in, float *d_out, void *hip_stream)
             cl.res_stream = b->res_stream;
             cl.ev_fused = b->ev_fused[ci & 3];
             cl.ev_res = b->ev_res[ci & 3];
-            cl.ev_ring_free = ci >= 2 ? b->ev_res[(ci - 2) & 3] : nullptr;
+            cl.ev_ring_free = ci >= first + 2 ? b->ev_res[(ci - 2) & 3] : nullptr;
             cl.late_chain = late;
-            cl.out = d_out + ch.k0;
+            cl.out = d_out + (ch.k0 - k_base);
         }
         c.launch_chunk(ia, ch.t0, ch.Tn, b->d_pinc.p + ch.t0, b->d_tiles.p + ch.tile_begin, ch.ntiles, b->d_P.p,
                        b->d_wacc.p + (size_t)ch.tile_begin * c.wacc_pitch,
                        b->d_whisper.p ? b->d_whisper.p + (size_t)ch.t0 * c.C * c.HP : nullptr,
-                       c.d.vocoder ? &car : nullptr, d_out, b->plan.out_frames, 0, st, ev, part, b->chain_stream,
+                       c.d.vocoder ? &car : nullptr, d_out, out_stride_row, k_base, st, ev, part, b->chain_stream,
                        b->ev_match[ci & 3], b->ev_chain[ci & 3], false, c.use_chain ? &cl : nullptr);
     };
-    const size_t nchunks = b->chunks.size();
+    // (f = the range's first launch, nchunks = one past its last: the loops below are pv_batch_run's with 0 -> f)
+    const size_t f = first, nchunks = first + count;
     if (piped) {
         // the chain stream must not start before the caller's stream has reached this run (state reset, inputs)
         // Fused path with a resampling kernel: three stages -- front of chunk i, resampling of chunk i-2, fused
@@ -1749,43 +1730,138 @@ int pv_batch_run(pv_batch *b, const float *d_in, float *d_out, void *hip_stream)
         std::vector<hipEvent_t *> evs(nchunks, nullptr);
         const bool ahead = three && c.ahead && !late;
         if (ahead) {
-            for (size_t ci = 0; ci < nchunks; ++ci) evs[ci] = events_for(ci);
-            if (nchunks > 0) launch(0, evs[0], 6); // A(0)
-            for (size_t ci = 0; ci < nchunks; ++ci) {
+            for (size_t ci = f; ci < nchunks; ++ci) evs[ci] = events_for(ci);
+            if (nchunks > f) launch(f, evs[f], 6); // A(f)
+            for (size_t ci = f; ci < nchunks; ++ci) {
                 launch(ci, evs[ci], 7);                                  // M(ci), chain(ci) handed to its stream
-                if (ci > 1) launch(ci - 2, evs[ci - 2], 4);              // R(ci-2)   beside the chain
+                if (ci > f + 1) launch(ci - 2, evs[ci - 2], 4);          // R(ci-2)   beside the chain
                 if (ci + 1 < nchunks) launch(ci + 1, evs[ci + 1], 6);    // A(ci+1)   beside what is left of it
-                if (ci > 0) launch(ci - 1, evs[ci - 1], 3);              // F(ci-1)
+                if (ci > f) launch(ci - 1, evs[ci - 1], 3);              // F(ci-1)
             }
-            if (nchunks > 1) launch(nchunks - 2, evs[nchunks - 2], 4);
-            if (nchunks > 0) launch(nchunks - 1, evs[nchunks - 1], 3), launch(nchunks - 1, evs[nchunks - 1], 4);
+            if (nchunks > f + 1) launch(nchunks - 2, evs[nchunks - 2], 4);
+            if (nchunks > f) launch(nchunks - 1, evs[nchunks - 1], 3), launch(nchunks - 1, evs[nchunks - 1], 4);
         } else {
-        for (size_t ci = 0; ci < nchunks; ++ci) {
+        for (size_t ci = f; ci < nchunks; ++ci) {
             evs[ci] = events_for(ci);
             launch(ci, evs[ci], 1);
             if (three) {
-                if (ci > 1) launch(ci - 2, evs[ci - 2], 4);
-                if (ci > 0) launch(ci - 1, evs[ci - 1], 3);
+                if (ci > f + 1) launch(ci - 2, evs[ci - 2], 4);
+                if (ci > f) launch(ci - 1, evs[ci - 1], 3);
                 if (late) launch(ci, evs[ci], 5); // the chain of chunk i starts behind the fused kernel of chunk i-1
-            } else if (ci > 0) {
+            } else if (ci > f) {
                 launch(ci - 1, evs[ci - 1], 2);
             }
         }
         if (three) {
-            if (nchunks > 1) launch(nchunks - 2, evs[nchunks - 2], 4);
-            if (nchunks > 0) launch(nchunks - 1, evs[nchunks - 1], 3), launch(nchunks - 1, evs[nchunks - 1], 4);
-        } else if (nchunks > 0) {
+            if (nchunks > f + 1) launch(nchunks - 2, evs[nchunks - 2], 4);
+            if (nchunks > f) launch(nchunks - 1, evs[nchunks - 1], 3), launch(nchunks - 1, evs[nchunks - 1], 4);
+        } else if (nchunks > f) {
             launch(nchunks - 1, evs[nchunks - 1], 2);
         }
         }
     } else {
-        for (size_t ci = 0; ci < nchunks; ++ci) launch(ci, events_for(ci), 0);
+        for (size_t ci = f; ci < nchunks; ++ci) launch(ci, events_for(ci), 0);
     }
     if (b->res_stream && c.use_chain) // the caller synchronises `st`: it has to cover the resampling stream too
-        for (size_t ci = nchunks > 2 ? nchunks - 2 : 0; ci < nchunks; ++ci)
+        for (size_t ci = nchunks > f + 2 ? nchunks - 2 : f; ci < nchunks; ++ci)
             HIPC(hipStreamWaitEvent(st, b->ev_res[ci & 3], 0));
     if ((rc = c.take_launch_error()) != PV_OK) return rc;
     HIPC(hipGetLastError());
+    return PV_OK;
+}
+
+int pv_batch_run(pv_batch *b, const float *d_in, float *d_out, void *hip_stream) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!b || !d_in || (!d_out && b->plan.out_frames > 0)) return PV_ERR_INVALID_ARG; // an empty output needs no buffer
+    Core &c = b->core;
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPC(hipSetDevice(c.device));
+    b->next_span = -1; // a whole run in between restarts the spans
+    int rc = c.reset_state(st);
+    if (rc != PV_OK) return rc;
+    InAddr ia;
+    ia.in = d_in;
+    ia.stride_c = b->frames;
+    ia.stride_s = b->frames * c.C;
+    ia.mask = ~0ull;
+    ia.len = b->frames;
+    return batch_enqueue(b, ia, d_out, b->plan.out_frames, 0, 0, b->chunks.size(), st, true);
+}
+
+int64_t pv_batch_plan_spans(const pv_config *cfg, int32_t nstreams, int64_t frames, int32_t block, int32_t flush,
+                            int32_t launches_per_span, pv_batch_span_info *out, int64_t max) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!cfg || nstreams < 1 || frames < 1 || block < 1 || launches_per_span < 1 || max < 0 || (max > 0 && !out))
+        return -(int64_t)PV_ERR_INVALID_ARG;
+    Derived d;
+    BatchPlan bp;
+    int st;
+    if ((st = derive(*cfg, d)) != PV_OK) return -(int64_t)st;
+    if ((st = plan_batch(d, frames, block, flush != 0, bp)) != PV_OK) return -(int64_t)st;
+    const int Tc = batch_chunk_slices(*cfg, nstreams, g_arith == PV_ARITH_FAST);
+    const int64_t L = batch_launches(bp, Tc);
+    int64_t count = 0;
+    if (L == 0) { // no slices: one empty span
+        pv_batch_span_info e;
+        if ((st = batch_span(d, bp, frames, Tc, 0, 0, e)) != PV_OK) return -(int64_t)st;
+        if (max > 0) out[0] = e;
+        return 1;
+    }
+    for (int64_t f = 0; f < L; f += launches_per_span, ++count) {
+        const int64_t n = L - f < launches_per_span ? L - f : launches_per_span;
+        pv_batch_span_info e;
+        if ((st = batch_span(d, bp, frames, Tc, (int32_t)f, (int32_t)n, e)) != PV_OK) return -(int64_t)st;
+        if (count < max) out[count] = e;
+    }
+    return count;
+}
+
+int pv_batch_span(const pv_batch *b, int32_t first_launch, int32_t launches, pv_batch_span_info *out) {
+    if (!b || !out) return PV_ERR_INVALID_ARG;
+    return batch_span(b->core.d, b->plan, b->frames, b->core.Tc, first_launch, launches, *out);
+}
+
+int pv_batch_run_span(pv_batch *b, int32_t first_launch, int32_t launches, const float *d_in_win, int64_t in_pitch,
+                      float *d_out_win, int64_t out_pitch, void *hip_stream) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!b) return PV_ERR_INVALID_ARG;
+    Core &c = b->core;
+    // every refusal comes before anything is enqueued or changed
+    pv_batch_span_info sp;
+    if (batch_span(c.d, b->plan, b->frames, c.Tc, first_launch, launches, sp) != PV_OK) return PV_ERR_INVALID_ARG;
+    if (first_launch != 0 && (int64_t)first_launch != b->next_span) {
+        g_last_error = "pv_batch_run_span: a span must start at launch 0 or follow the previous span";
+        return PV_ERR_INVALID_ARG;
+    }
+    const int64_t in_len = sp.in_end - sp.in_begin, out_len = sp.out_end - sp.out_begin;
+    if (in_pitch < in_len || out_pitch < out_len || in_pitch < 0 || out_pitch < 0 || (in_pitch & 3) || (out_pitch & 3) ||
+        (reinterpret_cast<uintptr_t>(d_in_win) & 15u) || (reinterpret_cast<uintptr_t>(d_out_win) & 15u) ||
+        (!d_in_win && in_len > 0) || (!d_out_win && out_len > 0))
+        return PV_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPC(hipSetDevice(c.device));
+    b->next_span = -1; // (until this span is enqueued whole)
+    if (first_launch == 0) {
+        const int rc = c.reset_state(st);
+        if (rc != PV_OK) return rc;
+    }
+    // The kernels address a row's input by its frame number: the window's row 0 would start in_begin floats before
+    // d_in_win.  in_begin and the pitch are multiples of 4, so every row of that virtual array starts on a 16-byte
+    // boundary, and the loads stay inside [in_begin, in_end) of each row (pv_plan.cc batch_span).  The length stays
+    // the stream's: it is what decides between a loaded frame and a flush zero, as in the whole run.
+    InAddr ia;
+    // (formed as an integer: the address lies before the window's allocation, and d_in_win may be NULL for an empty range)
+    ia.in = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(d_in_win) - (uintptr_t)sp.in_begin * sizeof(float));
+    ia.stride_c = in_pitch;
+    ia.stride_s = in_pitch * c.C;
+    ia.mask = ~0ull;
+    ia.len = b->frames;
+    const int rc = batch_enqueue(b, ia, d_out_win, out_pitch, sp.out_begin, (size_t)first_launch, (size_t)launches, st, false);
+    if (rc != PV_OK) return rc;
+    b->next_span = (int64_t)first_launch + launches;
     return PV_OK;
 }
 

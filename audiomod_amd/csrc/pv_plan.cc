@@ -454,6 +454,96 @@ int plan_batch(const Derived &d, int64_t frames, int block, bool flush, BatchPla
     return PV_OK;
 }
 
+int batch_chunk_slices(const pv_config &cfg, int nstreams, bool fast_arith) {
+    const int rows = nstreams * cfg.channels;
+    // slices per launch and row: 64 K slices per launch amortise the launch's fixed costs and tail (measured:
+    // +8 % over 16 K with 256 rows; flat beyond), and the planes of such a chunk are a few GB of the 288
+    // Round 2, fused path (192 rows and up): 128 K slices per launch, up to 512 per row -- half as many kernel
+    // boundaries (each a drain and a refill of the chip): 52.0 vs 52.9 ms per bench step; 768 per row: no further gain.
+    // Round 3: with PV_ARITH_FAST every wave-FFT configuration that has a free-form kernel takes the fused path at
+    // any row count (Core::fast_capable), and the wide chunks with it (8-95 streams: +5...20 % over the tile path).
+    const bool fast_wave = fast_arith && (cfg.fftsize > 256 && cfg.fftsize <= 4096);
+    const bool wide = rows >= 192 || fast_wave;
+    int Tc = (wide ? 131072 : 65536) / (rows > 0 ? rows : 1);
+    if (Tc < 16) Tc = 16;
+    if (Tc > (wide ? 512 : 256)) Tc = wide ? 512 : 256;
+    if (const char *env = getenv("AUDIOMOD_PV_CHUNK_SLICES")) { // tuning knob: slices per launch and row
+        const int v = atoi(env);
+        if (v >= 4 && v <= 1024) Tc = v;
+    }
+    return Tc;
+}
+
+int64_t batch_launches(const BatchPlan &bp, int Tc) { return ((int64_t)bp.slices.size() + Tc - 1) / Tc; }
+
+// A span's ranges.
+//   Output: launch i emits the outputs of its slices [t0, t1): [K0(t0), K0(t1 - 1) + cnt(t1 - 1)) clipped to
+//   out_frames -- pv_batch_create's ka / kb, for which it builds the overlap-add tiles, the resampling tiles or the
+//   fused kernel's k_off / kcnt; K0 accumulates cnt, so consecutive launches' ranges abut and partition [0, out_frames).
+//   Input: slice t's frame is the N input frames from a0 = t * hop; frames at or beyond `frames` (the flush) are zeros
+//   the kernels make up themselves (every load tests against InAddr::len = frames).  What the three analysis kernels
+//   (pv_kernels.hip) load for slice t of a row whose first frame sits on a 16-byte boundary:
+//     pv_analyze_kernel (generic)       element by element, g < len:                    [a0, min(frames, a0 + N))
+//     analyze_wave_role / _split_role   slow branch, the same:                         [a0, min(frames, a0 + N))
+//                                       fast branch, taken when a0 + N + 4 <= frames:   64 * Q + 1 = N / 4 + 1 aligned
+//                                       16-byte pieces from the one that holds a0:      [a0 - a0 % 4, a0 - a0 % 4 + N + 4)
+//   (a0 % 4 is the piece offset because a window's row starts aligned and in_begin is a multiple of 4).  The fast
+//   branch's guard looks at the stream's length, not at a window's end, so the window must hold the extra piece:
+//   both branches lie inside [a0 - a0 % 4, min(frames, a0 - a0 % 4 + N + 4)) -- the fast one because its guard gives
+//   a0 - a0 % 4 + N + 4 <= a0 + N + 4 <= frames.  Lower and upper end grow with t, so a span's range is the first
+//   slice's begin and the last slice's end.  A slice that lies wholly in the flush reads nothing: the begin is capped
+//   at frames (rounded down to a multiple of 4).  The vocoder's carrier row is analysed from the batch's own
+//   device-resident carrier signal (its InAddr, its length), never from the caller's window.
+int batch_span(const Derived &d, const BatchPlan &bp, int64_t frames, int Tc, int32_t first, int32_t n,
+               pv_batch_span_info &o) {
+    const int64_t T = (int64_t)bp.slices.size();
+    if (Tc < 1 || frames < 0) return PV_ERR_INVALID_ARG;
+    const int64_t L = batch_launches(bp, Tc);
+    o = pv_batch_span_info{};
+    if (L == 0 && first == 0 && n == 0) return PV_OK;
+    if (first < 0 || n < 1 || (int64_t)first + n > L) return PV_ERR_INVALID_ARG;
+    const int64_t t0 = (int64_t)first * Tc;
+    const int64_t t1 = ((int64_t)first + n) * Tc < T ? ((int64_t)first + n) * Tc : T;
+    o.first_launch = first;
+    o.launches = n;
+    o.slice_begin = t0;
+    o.slice_end = t1;
+    int64_t ka = bp.slices[(size_t)t0].K0;
+    int64_t kb = bp.slices[(size_t)(t1 - 1)].K0 + bp.slices[(size_t)(t1 - 1)].cnt;
+    if (ka > bp.out_frames) ka = bp.out_frames;
+    if (kb > bp.out_frames) kb = bp.out_frames;
+    o.out_begin = ka;
+    o.out_end = kb;
+    const int64_t a_first = t0 * (int64_t)d.hop, a_last = (t1 - 1) * (int64_t)d.hop;
+    int64_t lo = a_first < frames ? a_first : frames;
+    lo -= lo & 3;
+    int64_t hi = (a_last - (a_last & 3)) + d.N + 4;
+    if (hi > frames) hi = frames;
+    if (hi < lo) hi = lo;
+    o.in_begin = lo;
+    o.in_end = hi;
+    return PV_OK;
+}
+
+// Input: the hull of n * Tc frames, hop apart, each N + 4 long, begun up to 3 frames early by the alignment.
+// Output: a span advances the overlap-add stream by its slices' shift increments, each at most hop (the modes
+// without a phase stage), floor(hop * hs_ratio) (integer ratio) or lrint(2 * hop * hs_ratio) (next_increment's
+// clamp), and never more than N (try_slice refuses it); without resampling the outputs are those samples, with it
+// the outputs k with floor(k * num / den) inside them: at most ceil(adv * den / num) + 1.
+void batch_span_bounds(const Derived &d, int Tc, int32_t n, int64_t &in_max, int64_t &out_max) {
+    const int64_t slices = (int64_t)n * Tc;
+    in_max = (slices - 1) * d.hop + d.N + 4 + 3;
+    const float ideal = (size_t)d.hop * d.hs_ratio;
+    int64_t shift;
+    if (d.robotic || d.whisper || d.constant || d.vocoder) shift = d.hop;
+    else if (d.int_ratio) shift = (int64_t)((size_t)d.hop * d.hs_ratio);
+    else shift = std::lrint(ideal * 2);
+    if (shift > d.N) shift = d.N;
+    if (shift < 1) shift = 1;
+    const int64_t adv = slices * shift;
+    out_max = d.resample ? (int64_t)(((unsigned __int128)adv * d.res_den + d.res_num - 1) / d.res_num) + 1 : adv;
+}
+
 // Rosenberg glottal pulse (gen/rosenberg.cc:19-53): per period of round(sample_rate / f) samples an opening phase
 // of n1 = round(alpha * period) samples, 0.5 (1 - cos(pi n / n1)), a closing phase of n2 = round(beta * period)
 // samples, cos(pi (n - n1) / (2 n2)), then silence; the sample counter runs 0 .. period inclusive.  Arithmetic

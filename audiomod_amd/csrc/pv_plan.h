@@ -137,6 +137,21 @@ struct BatchPlan {
 };
 int plan_batch(const Derived &d, int64_t frames, int block, bool flush, BatchPlan &bp);
 
+// Slices per launch ("chunk") and row of the batch engine for `nstreams` streams of cfg: pv_batch_create's rule,
+// the tuning knob AUDIOMOD_PV_CHUNK_SLICES included.  fast_arith: the pv_set_arithmetic setting is PV_ARITH_FAST.
+int batch_chunk_slices(const pv_config &cfg, int nstreams, bool fast_arith);
+// launches of a batch whose plan is bp: ceil(slices / Tc)
+int64_t batch_launches(const BatchPlan &bp, int Tc);
+// What launches [first, first + n) of such a batch cover, per row: slices, the input frames their kernels may read
+// and the output frames they write (include/audiomod_pv.h pv_batch_span_info; the derivation is at the definition).
+// n >= 1 and first + n <= batch_launches(), or first == n == 0 for a plan without slices (an empty span);
+// anything else returns PV_ERR_INVALID_ARG.
+int batch_span(const Derived &d, const BatchPlan &bp, int64_t frames, int Tc, int32_t first, int32_t n,
+               pv_batch_span_info &o);
+// Upper bounds of in_end - in_begin and out_end - out_begin of ANY span of n launches of Tc slices, from the derived
+// constants alone (not from a plan): a window of these sizes serves a job of every length.
+void batch_span_bounds(const Derived &d, int Tc, int32_t n, int64_t &in_max, int64_t &out_max);
+
 int64_t bytes_per_slice(const Derived &d);
 
 // The phases whisperSlice (phasevocoderprocess.cc:814-822) draws in a fresh reference process: glibc's rand()

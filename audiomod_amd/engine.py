@@ -56,6 +56,15 @@ class MixedStream(C.Structure):
     _fields_ = [("frames", C.c_int64), ("time_ratio", C.c_float), ("pitch_semitones", C.c_float)]
 
 
+class SpanInfo(C.Structure):
+    _fields_ = [("first_launch", C.c_int32), ("launches", C.c_int32), ("slice_begin", C.c_int64),
+                ("slice_end", C.c_int64), ("in_begin", C.c_int64), ("in_end", C.c_int64), ("out_begin", C.c_int64),
+                ("out_end", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PoolRange(C.Structure):
     _fields_ = [("min_semitones", C.c_float), ("max_semitones", C.c_float), ("min_time_ratio", C.c_float),
                 ("max_time_ratio", C.c_float)]
@@ -115,6 +124,16 @@ def lib():
     L.pv_batch_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pv_batch_enable_timing.argtypes = [C.c_void_p, C.c_int]
     L.pv_batch_kernel_times.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_batch_plan_spans.argtypes = [C.POINTER(Config), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(SpanInfo), C.c_int64]
+    L.pv_batch_plan_spans.restype = C.c_int64
+    L.pv_batch_span.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SpanInfo)]
+    L.pv_batch_run_span.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                    C.c_void_p]
+    L.pv_hostio_create_segmented.argtypes = [C.POINTER(Config), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int,
+                                             C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.pv_hostio_staging_bytes.argtypes = [C.c_void_p]
+    L.pv_hostio_staging_bytes.restype = C.c_int64
     L.pv_hostio_create.argtypes = [C.POINTER(Config), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int, C.c_int32,
                                    C.c_int32, C.POINTER(C.c_void_p)]
     L.pv_hostio_destroy.argtypes = [C.c_void_p]
@@ -235,6 +254,24 @@ def whisper_phases(n):
     out = np.zeros(n, np.float32)
     _check(lib().pv_plan_whisper_phases(n, out.ctypes.data), "pv_plan_whisper_phases")
     return out
+
+
+def plan_spans(nstreams, frames, launches_per_span=1, channels=2, block=480, flush=True, **config):
+    """Host only (works without a GPU): the spans of Batch(nstreams, frames, ...) cut every `launches_per_span`
+    launches, as a list of dicts (include/audiomod_pv.h pv_batch_span_info): first_launch, launches, slice_begin /
+    slice_end, in_begin / in_end (input frames of a row the span may read), out_begin / out_end (output frames it
+    writes)."""
+    cfg = make_config(channels, **config)
+    L = lib()
+    args = (C.byref(cfg), int(nstreams), int(frames), int(block), 1 if flush else 0, int(launches_per_span))
+    n = L.pv_batch_plan_spans(*args, None, 0)
+    if n < 0:
+        _check(int(-n), "pv_batch_plan_spans")
+    arr = (SpanInfo * max(n, 1))()
+    got = L.pv_batch_plan_spans(*args, arr, n)
+    if got < 0:
+        _check(int(-got), "pv_batch_plan_spans")
+    return [arr[i].as_dict() for i in range(min(n, got))]
 
 
 def _pp(rows):
@@ -407,8 +444,36 @@ class Batch:
                                    C.c_void_p(s.cuda_stream)), "pv_batch_run")
         return d_out
 
+    def span(self, first, n):
+        """What launches [first, first + n) cover per row (a dict, see plan_spans)."""
+        i = SpanInfo()
+        _check(self.L.pv_batch_span(self.h, int(first), int(n), C.byref(i)), "pv_batch_span")
+        return i.as_dict()
+
+    def run_span(self, first, n, d_in_win, d_out_win=None, stream=None):
+        """Runs launches [first, first + n) on windows of the rows.  d_in_win: float32 CUDA tensor [nstreams, channels,
+        in_pitch] whose rows hold input frames [in_begin, in_end) of span(first, n) from offset 0; d_out_win
+        [nstreams, channels, out_pitch] receives output frames [out_begin, out_end) likewise (allocated when None).
+        Pitches are multiples of 4.  first == 0 starts afresh; any other span must follow the previous one.
+        Asynchronous; both windows may be reused in stream order afterwards.  The spans of a job, concatenated, are
+        run()'s output bit for bit.  enable_timing() does not cover spans."""
+        import torch
+        sp = self.span(first, n)
+        assert d_in_win.is_cuda and d_in_win.dtype == torch.float32 and d_in_win.is_contiguous()
+        assert tuple(d_in_win.shape[:2]) == (self.nstreams, self.channels) and d_in_win.dim() == 3
+        if d_out_win is None:
+            pitch = max((sp["out_end"] - sp["out_begin"] + 3) // 4 * 4, 4)
+            d_out_win = torch.empty((self.nstreams, self.channels, pitch), dtype=torch.float32, device=d_in_win.device)
+        assert d_out_win.is_cuda and d_out_win.dtype == torch.float32 and d_out_win.is_contiguous()
+        assert tuple(d_out_win.shape[:2]) == (self.nstreams, self.channels) and d_out_win.dim() == 3
+        s = stream if stream is not None else torch.cuda.current_stream(d_in_win.device)
+        _check(self.L.pv_batch_run_span(self.h, int(first), int(n), C.c_void_p(d_in_win.data_ptr()),
+                                        int(d_in_win.shape[2]), C.c_void_p(d_out_win.data_ptr()),
+                                        int(d_out_win.shape[2]), C.c_void_p(s.cuda_stream)), "pv_batch_run_span")
+        return d_out_win
+
     def enable_timing(self, every=1):
-        """every = 0/False: off; n: HIP events around the kernels of every n-th chunk."""
+        """every = 0/False: off; n: HIP events around the kernels of every n-th chunk (of run(), not of run_span())."""
         _check(self.L.pv_batch_enable_timing(self.h, int(every)), "pv_batch_enable_timing")
 
     def kernel_times(self):
@@ -552,20 +617,34 @@ class MixedBatch:
 class HostIO:
     """nstreams independent streams whose input and output live in HOST memory (what the reference's callers hold:
     main/main.cc:152-162,484-491), float32 or int16 on the wire; groups of streams are staged through the GPU with
-    copy-in, kernels and copy-out overlapped (include/audiomod_pv.h pv_hostio_*)."""
+    copy-in, kernels and copy-out overlapped (include/audiomod_pv.h pv_hostio_*).
+
+    launches_per_segment=k stages by TIME instead (pv_hostio_create_segmented): one batch of all streams run in
+    segments of k launches through three window slots, so the device holds three windows of audio whatever `frames`
+    is; streams_per_group is then unused.  None (the default) is the grouped object.  Same bits either way."""
 
     def __init__(self, nstreams, frames, channels=2, block=480, flush=True, device=0, streams_per_group=16,
-                 wire="f32", **kw):
+                 wire="f32", launches_per_segment=None, **kw):
         self.L = lib()
         self.cfg = make_config(channels, **kw)
         self.nstreams, self.frames, self.channels = nstreams, frames, channels
         self.wire = {"f32": 0, "i16": 1}[wire]
         self.dtype = np.float32 if self.wire == 0 else np.int16
         self.h = C.c_void_p()
-        _check(self.L.pv_hostio_create(C.byref(self.cfg), nstreams, frames, block, 1 if flush else 0, device,
-                                       streams_per_group, self.wire, C.byref(self.h)), "pv_hostio_create")
+        self.launches_per_segment = launches_per_segment
+        if launches_per_segment is None:
+            _check(self.L.pv_hostio_create(C.byref(self.cfg), nstreams, frames, block, 1 if flush else 0, device,
+                                           streams_per_group, self.wire, C.byref(self.h)), "pv_hostio_create")
+        else:
+            _check(self.L.pv_hostio_create_segmented(C.byref(self.cfg), nstreams, frames, block, 1 if flush else 0,
+                                                     device, int(launches_per_segment), self.wire, C.byref(self.h)),
+                   "pv_hostio_create_segmented")
         self.out_frames = self.L.pv_hostio_out_frames(self.h)
         self._pinned = []
+
+    def staging_bytes(self):
+        """Device bytes of the staging buffers (grouped: three groups' whole streams; segmented: three windows)."""
+        return self.L.pv_hostio_staging_bytes(self.h)
 
     def pinned(self, shape):
         """numpy array of this job's wire type in page-locked host memory (freed with the object)"""

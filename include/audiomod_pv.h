@@ -241,6 +241,55 @@ int pv_batch_enable_timing(pv_batch *b, int on);
 int pv_batch_kernel_times(pv_batch *b, double ms[PV_NUM_KERNELS], int64_t launches[PV_NUM_KERNELS]);
 const char *pv_kernel_name(int k);
 
+/* Batch spans: a batch run in TIME segments, so that only a window of every row is in device memory at once.
+ * pv_batch_run walks pv_batch_launches() launches of Tc slices per row each, all state carried between them inside
+ * the object; a span is a run of consecutive launches [first_launch, first_launch + launches).
+ *   pv_batch_plan_spans : host only, like pv_mbatch_layout: the spans of the batch that pv_batch_create(cfg, nstreams,
+ *                         frames, block, flush) would build under the current pv_set_arithmetic setting and
+ *                         AUDIOMOD_PV_CHUNK_SLICES, cut every `launches_per_span` launches.  Writes min(count, max)
+ *                         entries, returns the count or minus a pv_status.  A job without slices has one empty span
+ *                         (launches = 0).  NULL cfg, nstreams / frames / block / launches_per_span < 1 (or NULL out
+ *                         with max > 0): PV_ERR_INVALID_ARG; a configuration the engine refuses: its status.
+ *   pv_batch_span       : the same for an existing batch and an arbitrary span (launches >= 1 inside the batch's).
+ * Contract of the ranges (per row, in frames): the out ranges of consecutive spans partition [0, out_frames) in
+ * order (empty ranges occur); 0 <= in_begin <= in_end <= frames, in_begin a multiple of 4; begins and ends never
+ * decrease from span to span; a merged span's ranges are the hull of its parts'.  [in_begin, in_end) contains
+ * [slice_begin * hop, min(frames, (slice_end - 1) * hop + fftsize)) AND everything else the span's kernels load: the
+ * analysis kernels fetch the aligned 16-byte pieces that hold a frame plus one more (up to 3 frames before and 4
+ * after it), see audiomod_amd/csrc/pv_plan.cc batch_span.  The flush zeros beyond `frames` are never read from memory.
+ *   pv_batch_run_span   : runs one span on windows of the rows:
+ *       d_in_win : [nstreams][channels][in_pitch],  row r holds input frames [in_begin, in_end) from offset 0
+ *       d_out_win: [nstreams][channels][out_pitch], row r receives output frames [out_begin, out_end) from offset 0
+ *     pitches in floats, multiples of 4, >= the range's length; bases 16-byte aligned (anything else:
+ *     PV_ERR_INVALID_ARG; d_out_win may be NULL when the span's out range is empty, d_in_win when its in range is).
+ *     No kernel reads or writes a window outside the reported ranges.
+ *     first_launch == 0 starts every stream afresh, as pv_batch_run does; any other value must be the launch after
+ *     the previous span's last, otherwise the call returns PV_ERR_INVALID_ARG, enqueues nothing and leaves the
+ *     object as it was.  A pv_batch_run in between restarts (the next span must be a first one again).
+ *     Enqueues only and returns without synchronising; when it returns, everything the span put on the batch's
+ *     internal streams is ordered before later work on `hip_stream`, so both windows may be reused in stream order.
+ *     The state a span hands to the next is ordered by that same rule only: consecutive spans go on the same
+ *     `hip_stream`, or on streams the caller has ordered himself (the next span's stream waits for an event recorded
+ *     behind the previous span) -- nothing inside the object orders two spans on unrelated streams.
+ *     For any division of the launches into spans the concatenated outputs are pv_batch_run's, bit for bit.  Inside
+ *     a span the launches keep pv_batch_run's order (its software pipeline included); the pipeline drains at the
+ *     span's end and the next span starts with its own first analysis, which is what a span costs.
+ *     pv_batch_enable_timing instruments pv_batch_run only; spans are never instrumented.
+ * What still grows with the length: the per-slice and per-sample descriptors (overlap-add plan, window-sum
+ * denominators, resampler tables) are built for the whole job at creation -- about 12-14 bytes of host and device
+ * memory per output frame, shared by all streams.  That, not the audio, is the remaining limit on a job's length. */
+typedef struct pv_batch_span_info {
+    int32_t first_launch, launches;
+    int64_t slice_begin, slice_end;   /* slices per row covered */
+    int64_t in_begin, in_end;         /* input frames of a row the span's kernels may read  */
+    int64_t out_begin, out_end;       /* output frames of a row the span writes             */
+} pv_batch_span_info;
+int64_t pv_batch_plan_spans(const pv_config *cfg, int32_t nstreams, int64_t frames, int32_t block, int32_t flush,
+                            int32_t launches_per_span, pv_batch_span_info *out, int64_t max);
+int pv_batch_span(const pv_batch *b, int32_t first_launch, int32_t launches, pv_batch_span_info *out);
+int pv_batch_run_span(pv_batch *b, int32_t first_launch, int32_t launches, const float *d_in_win, int64_t in_pitch,
+                      float *d_out_win, int64_t out_pitch, void *hip_stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Mixed batch: the batch engine for streams that differ in LENGTH, PITCH and TIME RATIO -- an offline
  * corpus (augmentation with a random shift and stretch per clip, a folder of files) in one object,
@@ -360,6 +409,20 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
 typedef struct pv_hostio pv_hostio;
 int pv_hostio_create(const pv_config *cfg, int32_t nstreams, int64_t frames, int32_t block, int32_t flush, int device,
                      int32_t streams_per_group, int32_t wire, pv_hostio **out);
+/* Staging by TIME instead of by stream: ONE batch of all `nstreams` streams, run in segments of
+ * `launches_per_segment` launches (pv_batch_run_span) through three window slots.  Per segment a pitched copy brings
+ * every row's [in_begin, in_end) up, the span runs, and a pitched copy takes [out_begin, out_end) down, on the same
+ * three HIP streams with the same event chaining as the grouped object; int16 is converted on the device, window by
+ * window.  Device memory for audio is three windows whatever `frames` is, and the result equals the grouped
+ * object's and the device-resident batch's bit for bit.  pv_hostio_run, pv_hostio_out_frames and pv_hostio_destroy
+ * serve both kinds of object.  NULL cfg / out, nstreams, frames or launches_per_segment < 1, an unknown wire:
+ * PV_ERR_INVALID_ARG, before any device call.
+ * The windows are sized from the configuration alone, for the worst case of any span of that many launches (every
+ * slice at the largest shift increment the planner may choose, twice the nominal one): the output windows, and with
+ * them pv_hostio_staging_bytes, are about twice what a steady job fills.  Copies move the actual ranges only. */
+int pv_hostio_create_segmented(const pv_config *cfg, int32_t nstreams, int64_t frames, int32_t block, int32_t flush,
+                               int device, int32_t launches_per_segment, int32_t wire, pv_hostio **out);
+int64_t pv_hostio_staging_bytes(const pv_hostio *h); /* device bytes of the staging buffers (both kinds of object) */
 void pv_hostio_destroy(pv_hostio *h);
 int64_t pv_hostio_out_frames(const pv_hostio *h);
 int pv_hostio_run(pv_hostio *h, const void *host_in, void *host_out);
