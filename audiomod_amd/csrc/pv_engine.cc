@@ -69,6 +69,19 @@ static int count_gfx950() {
     return ok;
 }
 
+// The phase stage of a configuration: -1 = none (the modes without a phase recurrence), else its coremode: 0 = the
+// propagation kernel, 1 = match kernel + rotation chain, 2 = no phase kernel (synthesis reads the analysis phases)
+static int phase_mode(const Derived &d) {
+    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
+    return bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+}
+// LDS bytes of the resampler's filter table: the per-offset float4 rows (Core::tab4) or the sinc table itself
+static int res_tab_bytes(const Derived &d) {
+    return !d.resample ? 0
+           : d.interp  ? d.oversample * (d.filt_len + 1) * 16
+                       : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
+}
+
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
@@ -366,17 +379,37 @@ struct Core {
     // ... for any derived constants (the stream pool asks it per slot)
     static bool fast_capable_of(const Derived &d, bool fast_arith) {
         if (!(fast_arith && (d.fft.nc == 256 || d.fft.nc == 512 || d.fft.nc == 1024 || d.fft.nc == 2048))) return false;
+        SynthArgs probe = synth_variant(d);
+        probe.tb.nc = d.fft.nc;
+        probe.whisper = d.whisper ? reinterpret_cast<const float *>(&d) : nullptr; // (only tested against null)
+        return synth_chain_has_fast(probe);
+    }
+    // what selects the synthesis kernel's variant, from the derived constants alone
+    static SynthArgs synth_variant(const Derived &d) {
         SynthArgs sa{};
-        sa.tb.nc = d.fft.nc;
         sa.do_freq_comp = d.do_freq_comp ? 1 : 0;
         sa.voc_band_len = d.vocoder ? d.voc_band_len : -1;
         sa.robotic = d.robotic ? 1 : 0;
         sa.passthru = d.constant ? 1 : 0;
-        sa.whisper = d.whisper ? reinterpret_cast<const float *>(&d) : nullptr; // (only tested against null)
-        const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
-        sa.coremode = bypass ? 0 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
-        return synth_chain_has_fast(sa);
+        sa.coremode = std::max(0, phase_mode(d));
+        return sa;
     }
+    // The kernels' argument blocks (pv_kernels.h), filled with everything that is a property of this Core: its derived
+    // constants, its buffers and its sizes.  nrows: the rows one launch covers -- `rows` on the batch and streaming
+    // paths (launch_chunk), C on the slot-table paths, where a launch serves a table of slots with C rows each.  What
+    // belongs to one launch (t0, s0, Tn, phase_inc, the input address, the chain's plan and outputs) stays zero here:
+    // launch_chunk sets it, the slot-table paths bring it per slot (PoolSlot / PoolParams / MbSlot).
+    // A new kernel argument is filled in here, or at the one call site whose value differs.
+    AnalyzeArgs analyze_args(int nrows) const;
+    MatchArgs match_args(int nrows) const;
+    SeqArgs seq_args(int nrows) const;
+    PropArgs prop_args(int nrows) const;
+    SynthArgs synth_args(int nrows) const;
+    ChainArgs chain_args(int nrows) const;
+    // the resampling kernel's block in two parts: what every path shares, and on top of it the filter set-up of a Core
+    // whose rows all share d (a mixed launch leaves that zero: each slot brings its own through PoolParams)
+    ResArgs res_args(int nrows) const;
+    ResArgs res_args_uniform(int nrows) const;
 
     int init(const pv_config &cfg, int dev, int nstreams, int chunk_slices);
     int reset_state(hipStream_t st);
@@ -477,7 +510,7 @@ int Core::init(const pv_config &cfg, int dev, int nstreams, int chunk_slices) {
         // 64 outputs are deferred by up to one slice (ChainBuilder), so the stream ring keeps W advances plus one
         // filter length plus the span of 64 outputs.
         if (chain_max_adv <= 0) {
-            const bool fixed_shift = d.robotic || d.whisper || d.constant || d.vocoder;
+            const bool fixed_shift = phase_mode(d) < 0;
             double m = fixed_shift ? (double)d.hop : (d.int_ratio ? (double)d.hop * d.hs_ratio : 2.0 * d.hop * d.hs_ratio + 1);
             chain_max_adv = (int)(m < d.N ? m + 1 : d.N);
         }
@@ -648,7 +681,7 @@ int Core::init(const pv_config &cfg, int dev, int nstreams, int chunk_slices) {
         if (d.resample)
             if ((st = stream.alloc((size_t)rows * ((size_t)chain_smask + 1))) != PV_OK) return st;
     }
-    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder; // modes without a phase recurrence
+    const bool bypass = phase_mode(d) < 0; // modes without a phase recurrence
     if (d.vocoder) {
         if ((st = cmag.alloc((size_t)TR * HP)) != PV_OK) return st;
         if ((st = cphase.alloc((size_t)TR * HP)) != PV_OK) return st;
@@ -695,9 +728,7 @@ bool Core::can_single_launch() const {
     probe.qa.hs = d.hs;
     probe.qa.PKP = PKP;
     probe.coremode = 1;
-    probe.oa.tab_bytes = !d.resample ? 0
-                         : d.interp  ? d.oversample * (d.filt_len + 1) * 16
-                                     : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
+    probe.oa.tab_bytes = res_tab_bytes(d);
     probe.oa.lds_floats = ola_lds_floats;
     return stream_kernel_supported(probe);
 }
@@ -839,6 +870,104 @@ static void build_res_tiles_of(const Derived &d, int64_t ka, int64_t kb, std::ve
     }
 }
 
+AnalyzeArgs Core::analyze_args(int nrows) const {
+    AnalyzeArgs aa{};
+    aa.tb = tb;
+    aa.hop = d.hop;
+    aa.TR = TR;
+    aa.rows = nrows;
+    aa.PKP = PKP;
+    aa.find_peaks = phase_mode(d) == 1 ? 1 : 0;
+    aa.split = split_analysis ? 1 : 0;
+    aa.mag = mag.p;
+    aa.phase = phase.p;
+    aa.peaks = peaks.p;
+    aa.npk = npk.p;
+    return aa;
+}
+MatchArgs Core::match_args(int nrows) const {
+    MatchArgs ma{};
+    ma.N = d.N, ma.hs = d.hs, ma.HP = HP, ma.PKP = PKP, ma.C = C, ma.hop = d.hop, ma.TR = TR, ma.rows = nrows;
+    ma.two_pi_hop = d.two_pi_hop;
+    ma.phase = phase.p, ma.peaks = peaks.p, ma.npk = npk.p, ma.recs = recs.p, ma.modes = modes.p;
+    return ma;
+}
+SeqArgs Core::seq_args(int nrows) const {
+    SeqArgs qa{};
+    qa.N = d.N, qa.hs = d.hs, qa.HP = HP, qa.PKP = PKP, qa.C = C, qa.hop = d.hop, qa.TR = TR, qa.rows = nrows;
+    qa.two_pi_hop = d.two_pi_hop;
+    qa.phase = phase.p, qa.peaks = peaks.p, qa.npk = npk.p, qa.recs = recs.p, qa.modes = modes.p;
+    qa.rot = rot.p, qa.outphase = outphase.p;
+    qa.st_kind = st_kind.p, qa.st_rot = st_rot.p, qa.st_po = st_po.p;
+    qa.high_prio = 1, qa.narrow = 0; // (launch_chunk alone reads the environment's knobs for these)
+    return qa;
+}
+PropArgs Core::prop_args(int nrows) const {
+    PropArgs pa{};
+    pa.N = d.N, pa.hs = d.hs, pa.HP = HP, pa.C = C, pa.hop = d.hop, pa.TR = TR, pa.rows = nrows;
+    pa.two_pi_hop = d.two_pi_hop;
+    pa.phase = phase.p, pa.outphase = outphase.p, pa.st_pp = st_pp.p, pa.st_po = st_po.p;
+    return pa;
+}
+SynthArgs Core::synth_args(int nrows) const {
+    // passthru, voc_band_len and the carrier planes come from d on every path: pool_scope and mb_scope refuse the
+    // CONSTANT and vocoder modes (and WHISPER), so on the slot-table paths they are 0, -1 and null as before.  Only
+    // `whisper` is missing: the random phases are a launch's (launch_chunk).
+    SynthArgs sa = synth_variant(d);
+    sa.tb = tb;
+    sa.hop = d.hop;
+    sa.C = C;
+    sa.two_pi_hop = d.two_pi_hop;
+    sa.freq_comp = d.freq_comp;
+    sa.fixed_gain = d.fixed_gain;
+    sa.inv_n = d.inv_n;
+    sa.cmag = cmag.p;
+    sa.cphase = cphase.p;
+    sa.TR = TR;
+    sa.rows = nrows;
+    sa.PKP = PKP;
+    sa.mag = mag.p, sa.phase = phase.p, sa.outphase = outphase.p, sa.peaks = peaks.p, sa.npk = npk.p;
+    sa.modes = modes.p, sa.rot = rot.p, sa.frames = frames.p, sa.FR = FR;
+    return sa;
+}
+ChainArgs Core::chain_args(int nrows) const {
+    ChainArgs ca{};
+    ca.N = d.N;
+    ca.rows = nrows;
+    ca.C = C;
+    ca.AR = chain_AR;
+    ca.smask = chain_smask;
+    ca.waves = chain_waves;
+    ca.runs = 1; // (launch_chunk: the launch's own; the mixed batch: per slot, MbSlot)
+    ca.st_acc = st_acc.p;
+    ca.stream = stream.p;
+    ca.resample = d.resample ? 1 : 0;
+    ca.frames = frames.p;
+    ca.FR = FR;
+    ca.fast = fast_chain() ? 1 : 0;
+    return ca;
+}
+ResArgs Core::res_args(int nrows) const {
+    ResArgs ra{};
+    ra.rows = nrows;
+    ra.smask = chain_smask;
+    ra.stream = stream.p;
+    return ra;
+}
+ResArgs Core::res_args_uniform(int nrows) const {
+    ResArgs ra = res_args(nrows);
+    ra.interp = d.interp ? 1 : 0;
+    ra.filt_len = d.filt_len;
+    ra.oversample = d.oversample;
+    ra.sinc = sinc.p;
+    ra.sinc_len = d.resample ? (int)d.sinc.size() : 0;
+    ra.tab4 = tab4.p;
+    ra.lds_floats = ola_lds_floats;
+    ra.tab_bytes = res_tab_bytes(d);
+    ra.fast = fast_chain() ? 1 : 0; // (the modes with a free-form fused kernel: none of them can put NaN into the stream)
+    return ra;
+}
+
 void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_pinc, const OlaTile *d_tiles,
                         int ntiles, const int64_t *d_P, const float *d_wacc, const float *d_whisper,
                         const InAddr *carrier, float *out, int64_t out_stride_row, int64_t k_base,
@@ -857,8 +986,7 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
     if (part == 5 || part == 6 || part == 7) part = 1;
     const bool front = part != 2, back = part != 1;
     StreamArgs fused{};
-    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
-    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    const int cm = phase_mode(d);
     auto rec = [&](int i) {
         if (ev) HIPV(hipEventRecord(ev[i], st));
     };
@@ -881,23 +1009,13 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
             rec(2 * k + 1);
         }
     };
-    AnalyzeArgs aa{};
-    aa.tb = tb;
-    aa.ia = ia;
-    aa.hop = d.hop;
+    // every stage's block: the Core's builder, then what belongs to this launch
     const int s0 = (int)(t0 % TR);
+    AnalyzeArgs aa = analyze_args(rows);
+    aa.ia = ia;
     aa.t0 = t0;
     aa.s0 = s0;
     aa.Tn = Tn;
-    aa.TR = TR;
-    aa.rows = rows;
-    aa.PKP = PKP;
-    aa.find_peaks = cm == 1 ? 1 : 0;
-    aa.split = split_analysis ? 1 : 0;
-    aa.mag = mag.p;
-    aa.phase = phase.p;
-    aa.peaks = peaks.p;
-    aa.npk = npk.p;
     const bool do_analysis = front && !only_chain && !no_analysis;
     if (do_analysis) rec(2 * PV_K_ANALYZE);
     if (single_launch) fused.aa = aa;
@@ -916,55 +1034,22 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
     if (only_analysis) return;
 
     if (cm == 1) {
-        MatchArgs ma{};
-        ma.N = d.N;
-        ma.hs = d.hs;
-        ma.HP = HP;
-        ma.PKP = PKP;
-        ma.C = C;
-        ma.hop = d.hop;
-        ma.TR = TR;
-        ma.rows = rows;
-        ma.Tn = Tn;
-        ma.two_pi_hop = d.two_pi_hop;
+        MatchArgs ma = match_args(rows);
         ma.t0 = t0;
         ma.s0 = s0;
+        ma.Tn = Tn;
         ma.phase_inc = d_pinc;
-        ma.phase = phase.p;
-        ma.peaks = peaks.p;
-        ma.npk = npk.p;
-        ma.recs = recs.p;
-        ma.modes = modes.p;
         const bool phase_fused = fuse_phase && part == 0 && !single_launch && !ev; // (filled in below: needs qa)
         if (front && !only_chain) rec(2 * PV_K_MATCH);
         if (single_launch) fused.ma = ma;
         else if (front && !only_chain && !phase_fused) launch_match(ma, st); HIPV(hipGetLastError());
         if (front && !only_chain) rec(2 * PV_K_MATCH + 1);
-        SeqArgs qa{};
-        qa.N = d.N;
-        qa.hs = d.hs;
-        qa.HP = HP;
-        qa.PKP = PKP;
-        qa.C = C;
-        qa.hop = d.hop;
-        qa.TR = TR;
-        qa.rows = rows;
-        qa.Tn = Tn;
-        qa.two_pi_hop = d.two_pi_hop;
+        SeqArgs qa = seq_args(rows);
         qa.t0 = t0;
         qa.s0 = s0;
+        qa.Tn = Tn;
         qa.phase_inc = d_pinc;
-        qa.phase = phase.p;
-        qa.peaks = peaks.p;
-        qa.npk = npk.p;
-        qa.recs = recs.p;
-        qa.modes = modes.p;
-        qa.rot = rot.p;
-        qa.outphase = outphase.p;
-        qa.st_kind = st_kind.p;
-        qa.st_rot = st_rot.p;
-        qa.st_po = st_po.p;
-        {
+        { // this path's knobs (the slot-table paths keep the builder's 1 / 0)
             static const int prio = [] {
                 const char *e = getenv("AUDIOMOD_PV_SEQ_PRIO");
                 return e ? atoi(e) : -1;
@@ -985,59 +1070,21 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
             HIPV(hipGetLastError());
         } else side_stream(PV_K_SEQ, [&](hipStream_t s) { launch_seq(qa, s); HIPV(hipGetLastError()); });
     } else if (cm == 0) {
-        PropArgs pa{};
-        pa.N = d.N;
-        pa.hs = d.hs;
-        pa.HP = HP;
-        pa.C = C;
-        pa.hop = d.hop;
-        pa.TR = TR;
-        pa.rows = rows;
-        pa.Tn = Tn;
-        pa.two_pi_hop = d.two_pi_hop;
+        PropArgs pa = prop_args(rows);
         pa.t0 = t0;
         pa.s0 = s0;
+        pa.Tn = Tn;
         pa.phase_inc = d_pinc;
-        pa.phase = phase.p;
-        pa.outphase = outphase.p;
-        pa.st_pp = st_pp.p;
-        pa.st_po = st_po.p;
         if (single_launch) fused.pa = pa;
         else side_stream(PV_K_PROP, [&](hipStream_t s) { launch_prop(pa, s); HIPV(hipGetLastError()); });
     }
 
-    SynthArgs sa{};
-    sa.tb = tb;
-    sa.hop = d.hop;
-    sa.C = C;
-    sa.two_pi_hop = d.two_pi_hop;
-    sa.do_freq_comp = d.do_freq_comp ? 1 : 0;
-    sa.freq_comp = d.freq_comp;
-    sa.fixed_gain = d.fixed_gain;
-    sa.inv_n = d.inv_n;
-    sa.robotic = d.robotic ? 1 : 0;
-    sa.passthru = d.constant ? 1 : 0;
+    SynthArgs sa = synth_args(rows);
     sa.whisper = d.whisper ? d_whisper : nullptr;
-    sa.voc_band_len = d.vocoder ? d.voc_band_len : -1;
-    sa.cmag = cmag.p;
-    sa.cphase = cphase.p;
-    sa.coremode = cm < 0 ? 0 : cm;
     sa.t0 = t0;
     sa.s0 = s0;
     sa.Tn = Tn;
-    sa.TR = TR;
-    sa.rows = rows;
-    sa.PKP = PKP;
     sa.phase_inc = d_pinc;
-    sa.mag = mag.p;
-    sa.phase = phase.p;
-    sa.outphase = outphase.p;
-    sa.peaks = peaks.p;
-    sa.npk = npk.p;
-    sa.modes = modes.p;
-    sa.rot = rot.p;
-    sa.frames = frames.p;
-    sa.FR = FR;
     if (d.cepstral && !only_resample) {
         CepstralArgs ca{};
         ca.tb = tb;
@@ -1055,14 +1102,8 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
     }
     if (chain && !single_launch) {
         if (!back) return;
-        ChainArgs ca{};
-        ca.N = d.N;
-        ca.rows = rows;
-        ca.C = C;
+        ChainArgs ca = chain_args(rows);
         ca.Tn = Tn;
-        ca.AR = chain_AR;
-        ca.smask = chain_smask;
-        ca.waves = chain_waves;
         {
 #ifdef PV_DIAG
             static const int diag = [] {
@@ -1079,7 +1120,6 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
         ca.wden_hi = chain->wden_hi;
         // the ring images: this launch reads one half and writes the other (ChainArgs::st_acc_in); launches are
         // enqueued in slice order on one stream, so flipping at enqueue time is flipping in execution order
-        ca.st_acc = st_acc.p;
         ca.acc_sel = acc_half | (t0 == 0 ? 2 : 0);
         if (!only_resample) acc_half ^= 1;
 #ifdef PV_DIAG
@@ -1088,35 +1128,16 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
         // accumulator image puts out (reset_state leaves the image alone under the same switch)
         if (debug_stale_acc()) ca.acc_sel = 4; // bit 2 (diagnostic builds): read AND write half 0, never fresh
 #endif
-        ca.stream = stream.p;
-        ca.resample = d.resample ? 1 : 0;
         ca.out = chain->out;
         ca.out_stride_row = out_stride_row;
-        ca.frames = frames.p;
-        ca.FR = FR;
         ca.t0 = t0;
-        ca.fast = fast_chain() ? 1 : 0;
-        ResArgs ra{};
-        ra.rows = rows;
+        ResArgs ra = res_args_uniform(rows);
         ra.ntiles = chain->res_ntiles;
-        ra.smask = chain_smask;
-        ra.stream = stream.p;
         ra.tiles = chain->res_tiles;
         ra.otab = chain->res_otab;
-        ra.interp = d.interp ? 1 : 0;
-        ra.filt_len = d.filt_len;
-        ra.oversample = d.oversample;
-        ra.sinc = sinc.p;
-        ra.sinc_len = d.resample ? (int)d.sinc.size() : 0;
-        ra.tab4 = tab4.p;
-        ra.lds_floats = ola_lds_floats;
-        ra.tab_bytes = !d.resample ? 0
-                       : d.interp  ? d.oversample * (d.filt_len + 1) * 16
-                                   : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
         ra.out = out;
         ra.out_stride_row = out_stride_row;
         ra.k_base = k_base;
-        ra.fast = fast_chain() ? 1 : 0; // (the modes with a free-form fused kernel: none of them can put NaN into the stream)
         if (d.resample && chain->res_stream && chain->ev_ring_free && !only_resample)
             HIPV(hipStreamWaitEvent(st, chain->ev_ring_free, 0));
         if (only_resample) {
@@ -1174,9 +1195,7 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
     oa.lds_floats = ola_lds_floats;
     oa.wacc_pitch = wacc_pitch;
     oa.otab_off = otab_off;
-    oa.tab_bytes = !d.resample ? 0
-                   : d.interp  ? d.oversample * (d.filt_len + 1) * 16
-                               : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
+    oa.tab_bytes = res_tab_bytes(d);
     oa.out = out;
     oa.out_stride_row = out_stride_row;
     oa.k_base = k_base;
@@ -1869,8 +1888,7 @@ int pv_batch_kernel_times(pv_batch *b, double ms[PV_NUM_KERNELS], int64_t launch
     if (!b) return PV_ERR_INVALID_ARG;
     // fold finished event pairs into the accumulators
     const Derived &d = b->core.d;
-    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
-    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    const int cm = phase_mode(d);
     for (size_t i = 0; i + kEvPerChunk <= b->ev_used; i += kEvPerChunk) {
         for (int k = 0; k < PV_NUM_KERNELS; ++k) {
             if ((k == PV_K_MATCH || k == PV_K_SEQ) && cm != 1) continue;
@@ -1930,7 +1948,7 @@ int pv_create(const pv_config *cfg, int device, pv_engine **out) {
     // most outputs one group of slices can emit
     // (largest shift increment -- the hop itself in the modes that do not stretch, else the upper clamp
     // lrint(2 * hop * ratio), phasevocoderprocess.cc:394-395 -- through the resampler where there is one)
-    const bool fixed_shift = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
+    const bool fixed_shift = phase_mode(c.d) < 0;
     const double max_shift = fixed_shift ? (double)c.d.hop : 2.0 * c.d.hop * c.d.hs_ratio + 1;
     const double per_slice = c.d.resample ? max_shift * c.d.res_den / c.d.res_num + 2 : max_shift + 2;
     e->out_cap = (int)(kStreamChunk * per_slice) + 64;
@@ -2279,7 +2297,7 @@ static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch
 
 // the chain kernel's largest overlap-add advance for one set of derived constants (as Core::init computes it)
 static int pool_max_adv(const Derived &d) {
-    const bool fixed_shift = d.robotic || d.whisper || d.constant || d.vocoder;
+    const bool fixed_shift = phase_mode(d) < 0;
     const double m = fixed_shift ? (double)d.hop : (d.int_ratio ? (double)d.hop * d.hs_ratio : 2.0 * d.hop * d.hs_ratio + 1);
     return (int)(m < d.N ? m + 1 : d.N);
 }
@@ -2288,9 +2306,6 @@ static int pool_res_lds_floats(const Derived &d) {
     const double step = (double)d.res_num / (double)d.res_den;
     const int tile_span = (int)(kTileOut * step) + d.filt_len + 4;
     return (tile_span + 4 + 3) & ~3;
-}
-static int pool_res_tab_bytes(const Derived &d) {
-    return d.interp ? d.oversample * (d.filt_len + 1) * 16 : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
 }
 static bool pool_in_range(const pv_pool_range &r, float time_ratio, float semis) {
     return semis >= r.min_semitones && semis <= r.max_semitones && time_ratio >= r.min_time_ratio &&
@@ -2336,7 +2351,7 @@ static void pool_size_range(const pv_config &cfg, const pv_pool_range &r, PoolSi
         if (d.hop > z.max_hop) z.max_hop = d.hop;
         int adv = pool_max_adv(d);
         // below hs_ratio 1 the input hop is constant and the advance grows towards hs_ratio 1: bound it there
-        if (d.hs_ratio < 1 && !(d.robotic || d.whisper || d.constant || d.vocoder)) {
+        if (d.hs_ratio < 1 && phase_mode(d) >= 0) {
             const int up = (int)(2.0 * d.hop + 2 < d.N ? 2.0 * d.hop + 2 : d.N);
             if (up > adv) adv = up;
         }
@@ -2346,7 +2361,7 @@ static void pool_size_range(const pv_config &cfg, const pv_pool_range &r, PoolSi
             const double step = (double)d.res_num / (double)d.res_den;
             if (step > step_max) step_max = step;
             if (pool_res_lds_floats(d) > z.res_lds_floats) z.res_lds_floats = pool_res_lds_floats(d);
-            if (pool_res_tab_bytes(d) > z.res_tab_bytes) z.res_tab_bytes = pool_res_tab_bytes(d);
+            if (res_tab_bytes(d) > z.res_tab_bytes) z.res_tab_bytes = res_tab_bytes(d);
         }
     }
     if (z.any_resample) {
@@ -2398,9 +2413,8 @@ static int pool_create(const pv_config *cfg, const pv_pool_range *range, int32_t
         if (range) {
             // the range's worst case against every per-slot kernel's limits
             pool_size_range(*cfg, *range, z);
-            const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
             const int PKP = ((d.hs / 3 + 2) + 7) & ~7; // (as Core::init)
-            if (!bypass && cfg->coremode == 1 && !pool_phase_supported(d.hs, PKP)) {
+            if (phase_mode(d) == 1 && !pool_phase_supported(d.hs, PKP)) {
                 g_last_error = "stream pool range: the per-slot phase kernel (match + rotation chain) does not fit one workgroup";
                 return PV_ERR_UNSUPPORTED;
             }
@@ -2430,12 +2444,11 @@ static int pool_create(const pv_config *cfg, const pv_pool_range *range, int32_t
     if (range) c.chain_max_adv = z.max_adv; // (sizes the stream ring for every slot)
     int st = c.init(*cfg, device, capacity, kStreamChunk);
     if (st != PV_OK) return st;
-    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
     if (!c.use_chain || !c.wave_fft()) {
         g_last_error = "stream pool: needs the fused synthesis + overlap-add path (AUDIOMOD_PV_FUSED=0 turns it off)";
         return PV_ERR_UNSUPPORTED;
     }
-    if (!bypass && c.d.cfg.coremode == 1 && !pool_phase_supported(c.d.hs, c.PKP)) {
+    if (phase_mode(c.d) == 1 && !pool_phase_supported(c.d.hs, c.PKP)) {
         g_last_error = "stream pool: the phase-locked kernel of this configuration does not fit one workgroup";
         return PV_ERR_UNSUPPORTED;
     }
@@ -2553,7 +2566,7 @@ static int pool_open_at(pv_pool *p, float time_ratio, float semis, int32_t *slot
         const Derived &d = *own;
         const char *big = d.hop > p->max_hop ? "input hop" : pool_max_adv(d) > c.chain_max_adv ? "overlap-add advance" : nullptr;
         if (!big && d.resample &&
-            (pool_res_lds_floats(d) > p->max_res_lds_floats || pool_res_tab_bytes(d) > p->max_res_tab_bytes ||
+            (pool_res_lds_floats(d) > p->max_res_lds_floats || res_tab_bytes(d) > p->max_res_tab_bytes ||
              (int)d.sinc.size() > p->max_sinc || (d.interp && d.oversample * (d.filt_len + 1) > p->max_tab4)))
             big = "resampler set-up";
         if (big) {
@@ -2611,7 +2624,7 @@ static int pool_open_at(pv_pool *p, float time_ratio, float semis, int32_t *slot
     sl.tab = tab;
     if (tab >= 0) ++p->tabs[(size_t)tab].refs;
     sl.lds_floats = sl.d->resample ? pool_res_lds_floats(*sl.d) : 0;
-    sl.tab_bytes = sl.d->resample ? pool_res_tab_bytes(*sl.d) : 0;
+    sl.tab_bytes = res_tab_bytes(*sl.d);
     sl.planner.reset(new Planner(*sl.d));
     sl.chain.reset(new ChainBuilder(*sl.d, c.chain_AR, c.chain_smask));
     sl.fed = sl.uploaded = sl.slices = 0;
@@ -2676,14 +2689,24 @@ int32_t pv_pool_retrieve(pv_pool *p, int32_t slot, float *const *out, int32_t n)
     return got;
 }
 
-// the stages of one launch group for every slot in it (the fields as Core::launch_chunk sets them, rows = C);
+// the pool's ingest ring as the analysis kernel's input: slot s at s * stride_s, never past an end
+static InAddr pool_ring_addr(const pv_pool *p) {
+    InAddr ia{};
+    ia.in = p->d_in.p;
+    ia.stride_c = p->ring;
+    ia.stride_s = (int64_t)p->ring * p->core.C;
+    ia.mask = (uint64_t)(p->ring - 1);
+    ia.len = INT64_MAX;
+    return ia;
+}
+
+// the stages of one launch group for every slot in it (Core's argument builders with rows = C);
 // launch = false: launch nothing, only ask the launchers whether this configuration fits them (pv_pool_create)
 static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch) {
     const Core &c = p->core;
     const Derived &d = c.d;
     hipStream_t st = p->stream;
-    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
-    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    const int cm = phase_mode(d);
     auto refused = [](const char *what) {
         g_last_error = std::string("stream pool: no per-slot ") + what + " kernel for this configuration";
         return PV_ERR_UNSUPPORTED;
@@ -2693,95 +2716,27 @@ static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch
         return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
     };
     int rc;
-    AnalyzeArgs aa{};
-    aa.tb = c.tb;
-    aa.ia.in = p->d_in.p;
-    aa.ia.stride_c = p->ring;
-    aa.ia.stride_s = (int64_t)p->ring * c.C;
-    aa.ia.mask = (uint64_t)(p->ring - 1);
-    aa.ia.len = INT64_MAX;
-    aa.hop = d.hop;
-    aa.TR = c.TR;
-    aa.rows = c.C;
-    aa.PKP = c.PKP;
-    aa.find_peaks = cm == 1 ? 1 : 0;
-    aa.split = c.split_analysis ? 1 : 0;
-    aa.mag = c.mag.p;
-    aa.phase = c.phase.p;
-    aa.peaks = c.peaks.p;
-    aa.npk = c.npk.p;
+    AnalyzeArgs aa = c.analyze_args(c.C);
+    aa.ia = pool_ring_addr(p);
     if (launch && !launch_pool_analyze(aa, pl, st)) return refused("analysis");
     if (launch && (rc = launched("pool analysis launch")) != PV_OK) return rc;
     if (!launch) {
     } else if (cm == 1) {
-        MatchArgs ma{};
-        ma.N = d.N, ma.hs = d.hs, ma.HP = c.HP, ma.PKP = c.PKP, ma.C = c.C, ma.hop = d.hop, ma.TR = c.TR, ma.rows = c.C;
-        ma.two_pi_hop = d.two_pi_hop;
-        ma.phase = c.phase.p, ma.peaks = c.peaks.p, ma.npk = c.npk.p, ma.recs = c.recs.p, ma.modes = c.modes.p;
-        SeqArgs qa{};
-        qa.N = d.N, qa.hs = d.hs, qa.HP = c.HP, qa.PKP = c.PKP, qa.C = c.C, qa.hop = d.hop, qa.TR = c.TR, qa.rows = c.C;
-        qa.two_pi_hop = d.two_pi_hop;
-        qa.phase = c.phase.p, qa.peaks = c.peaks.p, qa.npk = c.npk.p, qa.recs = c.recs.p, qa.modes = c.modes.p;
-        qa.rot = c.rot.p, qa.outphase = c.outphase.p;
-        qa.st_kind = c.st_kind.p, qa.st_rot = c.st_rot.p, qa.st_po = c.st_po.p;
-        qa.high_prio = 1;
+        const MatchArgs ma = c.match_args(c.C);
+        const SeqArgs qa = c.seq_args(c.C);
         if (!launch_pool_phase(ma, qa, pl, st)) return refused("phase");
         if ((rc = launched("pool phase launch")) != PV_OK) return rc;
     } else if (cm == 0) {
-        PropArgs pa{};
-        pa.N = d.N, pa.hs = d.hs, pa.HP = c.HP, pa.C = c.C, pa.hop = d.hop, pa.TR = c.TR, pa.rows = c.C;
-        pa.two_pi_hop = d.two_pi_hop;
-        pa.phase = c.phase.p, pa.outphase = c.outphase.p, pa.st_pp = c.st_pp.p, pa.st_po = c.st_po.p;
+        const PropArgs pa = c.prop_args(c.C);
         if (!launch_pool_prop(pa, pl, st)) return refused("propagation");
         if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
     }
-    SynthArgs sa{};
-    sa.tb = c.tb;
-    sa.hop = d.hop;
-    sa.C = c.C;
-    sa.two_pi_hop = d.two_pi_hop;
-    sa.do_freq_comp = d.do_freq_comp ? 1 : 0;
-    sa.freq_comp = d.freq_comp;
-    sa.fixed_gain = d.fixed_gain;
-    sa.inv_n = d.inv_n;
-    sa.robotic = d.robotic ? 1 : 0;
-    sa.voc_band_len = -1;
-    sa.coremode = cm < 0 ? 0 : cm;
-    sa.TR = c.TR;
-    sa.rows = c.C;
-    sa.PKP = c.PKP;
-    sa.mag = c.mag.p, sa.phase = c.phase.p, sa.outphase = c.outphase.p, sa.peaks = c.peaks.p, sa.npk = c.npk.p;
-    sa.modes = c.modes.p, sa.rot = c.rot.p, sa.frames = c.frames.p, sa.FR = c.FR;
-    ChainArgs ca{};
-    ca.N = d.N;
-    ca.rows = c.C;
-    ca.C = c.C;
-    ca.AR = c.chain_AR;
-    ca.smask = c.chain_smask;
-    ca.waves = c.chain_waves;
-    ca.runs = 1;
-    ca.st_acc = c.st_acc.p;
-    ca.stream = c.stream.p;
-    ca.resample = d.resample ? 1 : 0;
-    ca.frames = c.frames.p;
-    ca.FR = c.FR;
-    ca.fast = c.fast_chain() ? 1 : 0;
+    const SynthArgs sa = c.synth_args(c.C);
+    const ChainArgs ca = c.chain_args(c.C);
     if (!launch_pool_synth_chain(sa, ca, pl, st, launch)) return refused("synthesis + overlap-add");
     if (launch && (rc = launched("pool synthesis + overlap-add launch")) != PV_OK) return rc;
     if (d.resample) {
-        ResArgs ra{};
-        ra.rows = c.C;
-        ra.smask = c.chain_smask;
-        ra.stream = c.stream.p;
-        ra.interp = d.interp ? 1 : 0;
-        ra.filt_len = d.filt_len;
-        ra.oversample = d.oversample;
-        ra.sinc = c.sinc.p;
-        ra.sinc_len = (int)d.sinc.size();
-        ra.tab4 = c.tab4.p;
-        ra.lds_floats = c.ola_lds_floats;
-        ra.tab_bytes = d.interp ? d.oversample * (d.filt_len + 1) * 16 : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
-        ra.fast = c.fast_chain() ? 1 : 0;
+        const ResArgs ra = c.res_args_uniform(c.C);
         if (!launch_pool_resample(ra, pl, st, launch)) return refused("resampling");
         if (launch && (rc = launched("pool resampling launch")) != PV_OK) return rc;
     }
@@ -2796,14 +2751,20 @@ struct VariantRun {
     int first, count;
     int dfc, res, fast, interp;
     int max_tiles, lds_floats, tab_bytes;
+    int max_runs; // (mixed batch: the most runs a slot of the entry splits its slices into; a pool's slots have one)
 };
+// the entries from `a` on that share one launch of the fused kernel: consecutive, they differ in interp only
+static size_t variant_group_end(const std::vector<VariantRun> &runs, size_t a) {
+    size_t e = a + 1;
+    while (e < runs.size() && runs[e].dfc == runs[a].dfc && runs[e].res == runs[a].res && runs[e].fast == runs[a].fast) ++e;
+    return e;
+}
 static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const PoolParams *q,
                                  const std::vector<VariantRun> &runs, int *nlaunch) {
     const Core &c = p->core;
     const Derived &d = c.d; // (only what every slot shares: sizes, mode, coremode)
     hipStream_t st = p->stream;
-    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
-    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    const int cm = phase_mode(d);
     auto refused = [](const char *what) {
         g_last_error = std::string("stream pool: no per-slot ") + what + " kernel for this configuration";
         return PV_ERR_UNSUPPORTED;
@@ -2814,86 +2775,36 @@ static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const P
         return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
     };
     int rc;
-    AnalyzeArgs aa{};
-    aa.tb = c.tb;
-    aa.ia.in = p->d_in.p;
-    aa.ia.stride_c = p->ring;
-    aa.ia.stride_s = (int64_t)p->ring * c.C;
-    aa.ia.mask = (uint64_t)(p->ring - 1);
-    aa.ia.len = INT64_MAX;
-    aa.hop = d.hop; // (per slot: PoolParams)
-    aa.TR = c.TR;
-    aa.rows = c.C;
-    aa.PKP = c.PKP;
-    aa.find_peaks = cm == 1 ? 1 : 0;
-    aa.split = c.split_analysis ? 1 : 0;
-    aa.mag = c.mag.p;
-    aa.phase = c.phase.p;
-    aa.peaks = c.peaks.p;
-    aa.npk = c.npk.p;
+    AnalyzeArgs aa = c.analyze_args(c.C); // (its hop is stream 0's: the kernel takes each slot's from PoolParams)
+    aa.ia = pool_ring_addr(p);
     if (!launch_pmix_analyze(aa, pl, q, st)) return refused("analysis");
     if ((rc = launched("pool analysis launch")) != PV_OK) return rc;
     if (cm == 1) {
-        MatchArgs ma{};
-        ma.N = d.N, ma.hs = d.hs, ma.HP = c.HP, ma.PKP = c.PKP, ma.C = c.C, ma.hop = d.hop, ma.TR = c.TR, ma.rows = c.C;
-        ma.two_pi_hop = d.two_pi_hop;
-        ma.phase = c.phase.p, ma.peaks = c.peaks.p, ma.npk = c.npk.p, ma.recs = c.recs.p, ma.modes = c.modes.p;
-        SeqArgs qa{};
-        qa.N = d.N, qa.hs = d.hs, qa.HP = c.HP, qa.PKP = c.PKP, qa.C = c.C, qa.hop = d.hop, qa.TR = c.TR, qa.rows = c.C;
-        qa.two_pi_hop = d.two_pi_hop;
-        qa.phase = c.phase.p, qa.peaks = c.peaks.p, qa.npk = c.npk.p, qa.recs = c.recs.p, qa.modes = c.modes.p;
-        qa.rot = c.rot.p, qa.outphase = c.outphase.p;
-        qa.st_kind = c.st_kind.p, qa.st_rot = c.st_rot.p, qa.st_po = c.st_po.p;
-        qa.high_prio = 1;
+        const MatchArgs ma = c.match_args(c.C);
+        const SeqArgs qa = c.seq_args(c.C);
         if (!launch_pmix_phase(ma, qa, pl, q, st)) return refused("phase");
         if ((rc = launched("pool phase launch")) != PV_OK) return rc;
     } else if (cm == 0) {
-        PropArgs pa{};
-        pa.N = d.N, pa.hs = d.hs, pa.HP = c.HP, pa.C = c.C, pa.hop = d.hop, pa.TR = c.TR, pa.rows = c.C;
-        pa.two_pi_hop = d.two_pi_hop;
-        pa.phase = c.phase.p, pa.outphase = c.outphase.p, pa.st_pp = c.st_pp.p, pa.st_po = c.st_po.p;
+        const PropArgs pa = c.prop_args(c.C);
         if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
         if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
     }
     float *stream = c.stream.p ? c.stream.p : p->mix_stream.p;
     for (size_t a = 0; a < runs.size();) {
-        // the synthesis variant's runs: consecutive, they differ in interp only
-        size_t b = a + 1;
-        while (b < runs.size() && runs[b].dfc == runs[a].dfc && runs[b].res == runs[a].res && runs[b].fast == runs[a].fast) ++b;
+        const size_t b = variant_group_end(runs, a);
         const VariantRun &ra0 = runs[a];
         PoolLaunch sub = pl;
         sub.slots = pl.slots + ra0.first;
         sub.nslots = runs[b - 1].first + runs[b - 1].count - ra0.first;
-        SynthArgs sa{};
-        sa.tb = c.tb;
-        sa.hop = d.hop;
-        sa.C = c.C;
-        sa.two_pi_hop = d.two_pi_hop;
+        // the group's variant in place of stream 0's: whether to compensate, to resample, to take the fast kernel;
+        // the compensation factor and the gain themselves are per slot (PoolParams), the block's are neutral
+        SynthArgs sa = c.synth_args(c.C);
         sa.do_freq_comp = ra0.dfc;
         sa.freq_comp = 1;
         sa.fixed_gain = 1;
-        sa.inv_n = d.inv_n;
-        sa.robotic = d.robotic ? 1 : 0;
-        sa.voc_band_len = -1;
-        sa.coremode = cm < 0 ? 0 : cm;
-        sa.TR = c.TR;
-        sa.rows = c.C;
-        sa.PKP = c.PKP;
-        sa.mag = c.mag.p, sa.phase = c.phase.p, sa.outphase = c.outphase.p, sa.peaks = c.peaks.p, sa.npk = c.npk.p;
-        sa.modes = c.modes.p, sa.rot = c.rot.p, sa.frames = c.frames.p, sa.FR = c.FR;
-        ChainArgs ca{};
-        ca.N = d.N;
-        ca.rows = c.C;
-        ca.C = c.C;
-        ca.AR = c.chain_AR;
-        ca.smask = c.chain_smask;
-        ca.waves = c.chain_waves;
-        ca.runs = 1;
-        ca.st_acc = c.st_acc.p;
+        ChainArgs ca = c.chain_args(c.C);
         ca.stream = stream;
         ca.resample = ra0.res;
-        ca.frames = c.frames.p;
-        ca.FR = c.FR;
         ca.fast = ra0.fast;
         if (!launch_pmix_synth_chain(sa, ca, sub, q + ra0.first, st)) return refused("synthesis + overlap-add");
         if ((rc = launched("pool synthesis + overlap-add launch")) != PV_OK) return rc;
@@ -2904,12 +2815,10 @@ static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const P
             rs.slots = pl.slots + rv.first;
             rs.nslots = rv.count;
             rs.max_tiles = rv.max_tiles;
-            ResArgs ra{};
-            ra.rows = c.C;
-            ra.smask = c.chain_smask;
+            ResArgs ra = c.res_args(c.C); // (not the uniform part: each slot brings its own filter set-up, PoolParams)
             ra.stream = stream;
             ra.interp = rv.interp;
-            ra.lds_floats = rv.lds_floats; // (the largest of the run's slots; each slot brings its own set-up)
+            ra.lds_floats = rv.lds_floats; // (the largest of the run's slots)
             ra.tab_bytes = rv.tab_bytes;
             ra.fast = rv.fast;
             if (!launch_pmix_resample(ra, rs, q + rv.first, st)) return refused("resampling");
@@ -3156,7 +3065,7 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
                 q2[k] = params[(size_t)ord[k]];
                 const int key = vkey[(size_t)ord[k]];
                 if (k == 0 || key != vkey[(size_t)ord[k - 1]])
-                    vr.push_back(VariantRun{(int)k, 0, key >> 3 & 1, key >> 2 & 1, key >> 1 & 1, key & 1, 0, 0, 0});
+                    vr.push_back(VariantRun{(int)k, 0, key >> 3 & 1, key >> 2 & 1, key >> 1 & 1, key & 1, 0, 0, 0, 1});
                 VariantRun &r = vr.back();
                 ++r.count;
                 if (t2[k].res_ntiles > r.max_tiles) r.max_tiles = t2[k].res_ntiles;
@@ -3197,8 +3106,7 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
     ce = hipMemcpyAsync(p->d_desc.p, p->h_desc.p, blob.size(), hipMemcpyHostToDevice, p->stream);
     if (ce != hipSuccess) return fail(hip_fail(ce, "descriptor upload", __LINE__));
     int nlaunch = 0;
-    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
-    const int cm = bypass ? -1 : ((c.d.cfg.coremode == 1 || c.d.cfg.coremode == 2) ? c.d.cfg.coremode : 0);
+    const int cm = phase_mode(c.d);
     for (int gi = 0; gi <= groups; ++gi) {
         const Group &g = grp[(size_t)gi];
         launch_pool_ingest(p->stage_src, p->d_in.p, p->ring, C, reinterpret_cast<const PoolIngest *>(p->d_desc.p + g.ingest_off),
@@ -3277,11 +3185,6 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
 // has its own Derived, plan_batch() plan and ChainBuilder output, all built and uploaded once, at creation.  A launch
 // group covers slices [g*Tc, (g+1)*Tc) of every stream that still has slices there; its PoolSlot / PoolParams / MbSlot
 // tables are sorted by kernel variant like a mixed pool's feed.
-struct MbVariant { // contiguous table entries of one kernel variant (the sort order of the group's tables)
-    int first, count;
-    int dfc, res, fast, interp;
-    int max_tiles, lds_floats, tab_bytes, max_runs;
-};
 } // extern "C"
 
 struct pv_mbatch {
@@ -3316,7 +3219,7 @@ struct pv_mbatch {
     struct Group {
         int64_t table_off = 0, params_off = 0, mb_off = 0;
         int nslots = 0, max_tn = 0;
-        std::vector<MbVariant> vr;
+        std::vector<VariantRun> vr;
     };
     std::vector<Group> groups;
     int kernel_launches = 0; // kernels per run
@@ -3399,7 +3302,7 @@ static int mb_plan(const pv_config *cfg, const pv_mbatch_stream *s, int32_t n, i
         }
         if (t.d.resample) {
             t.lds_floats = pool_res_lds_floats(t.d);
-            t.tab_bytes = pool_res_tab_bytes(t.d);
+            t.tab_bytes = res_tab_bytes(t.d);
             if ((size_t)t.tab_bytes + sizeof(float) * (size_t)t.lds_floats * NR > 160 * 1024 - 512) {
                 g_last_error = "mixed batch: stream " + std::to_string(i) +
                                ": the resampling kernel's filter table and tile do not fit the LDS at this pitch";
@@ -3418,23 +3321,22 @@ static int mb_plan(const pv_config *cfg, const pv_mbatch_stream *s, int32_t n, i
 // kernels one launch group enqueues (mb_launch_group)
 static int mb_group_kernels(const pv_mbatch::Group &g, int cm) {
     int k = 1 + (cm == 1 ? 2 : cm == 0 ? 1 : 0);
-    for (size_t a = 0; a < g.vr.size(); ++a) {
-        const bool first_of_synth = a == 0 || g.vr[a].dfc != g.vr[a - 1].dfc || g.vr[a].res != g.vr[a - 1].res ||
-                                    g.vr[a].fast != g.vr[a - 1].fast;
-        k += (first_of_synth ? 1 : 0) + (g.vr[a].res && g.vr[a].max_tiles > 0 ? 1 : 0);
+    for (size_t a = 0; a < g.vr.size();) {
+        const size_t e = variant_group_end(g.vr, a);
+        ++k;
+        for (; a < e; ++a) k += g.vr[a].res && g.vr[a].max_tiles > 0 ? 1 : 0;
     }
     return k;
 }
 
-// the stages of one launch group (the fields as Core::launch_chunk sets them, rows = C); launch = false: launch nothing,
+// the stages of one launch group (Core's argument builders with rows = C); launch = false: launch nothing,
 // only ask the launchers whether this configuration fits them (pv_mbatch_create)
 static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const float *d_in, float *d_out, hipStream_t st,
                            bool launch = true) {
     const Core &c = b->dev->core;
     const char *desc = b->dev->d_desc.p;
     const Derived &d = c.d; // (only what every stream shares: sizes, mode, coremode)
-    const bool bypass = d.robotic || d.whisper || d.constant || d.vocoder;
-    const int cm = bypass ? -1 : ((d.cfg.coremode == 1 || d.cfg.coremode == 2) ? d.cfg.coremode : 0);
+    const int cm = phase_mode(d);
     auto refused = [](const char *what) {
         g_last_error = std::string("mixed batch: no ") + what + " kernel for this configuration";
         return PV_ERR_UNSUPPORTED;
@@ -3454,35 +3356,15 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
     const PoolParams *q = reinterpret_cast<const PoolParams *>(desc + g.params_off);
     const MbSlot *ms = reinterpret_cast<const MbSlot *>(desc + g.mb_off);
     if (launch) {
-        AnalyzeArgs aa{};
-        aa.tb = c.tb;
-        aa.ia.in = d_in; // (per slot: MbSlot)
+        AnalyzeArgs aa = c.analyze_args(c.C); // (its hop is stream 0's: the kernel takes each slot's from PoolParams)
+        aa.ia.in = d_in; // (no ring: each slot's offset and length are in MbSlot)
         aa.ia.mask = ~0ull;
-        aa.hop = d.hop; // (per slot: PoolParams)
-        aa.TR = c.TR;
-        aa.rows = c.C;
-        aa.PKP = c.PKP;
-        aa.find_peaks = cm == 1 ? 1 : 0;
-        aa.split = c.split_analysis ? 1 : 0;
-        aa.mag = c.mag.p;
-        aa.phase = c.phase.p;
-        aa.peaks = c.peaks.p;
-        aa.npk = c.npk.p;
         if (!launch_mb_analyze(aa, pl, q, ms, st)) return refused("analysis");
         if ((rc = launched("mixed batch analysis launch")) != PV_OK) return rc;
     }
     if (cm == 1) {
-        MatchArgs ma{};
-        ma.N = d.N, ma.hs = d.hs, ma.HP = c.HP, ma.PKP = c.PKP, ma.C = c.C, ma.hop = d.hop, ma.TR = c.TR, ma.rows = c.C;
-        ma.two_pi_hop = d.two_pi_hop;
-        ma.phase = c.phase.p, ma.peaks = c.peaks.p, ma.npk = c.npk.p, ma.recs = c.recs.p, ma.modes = c.modes.p;
-        SeqArgs qa{};
-        qa.N = d.N, qa.hs = d.hs, qa.HP = c.HP, qa.PKP = c.PKP, qa.C = c.C, qa.hop = d.hop, qa.TR = c.TR, qa.rows = c.C;
-        qa.two_pi_hop = d.two_pi_hop;
-        qa.phase = c.phase.p, qa.peaks = c.peaks.p, qa.npk = c.npk.p, qa.recs = c.recs.p, qa.modes = c.modes.p;
-        qa.rot = c.rot.p, qa.outphase = c.outphase.p;
-        qa.st_kind = c.st_kind.p, qa.st_rot = c.st_rot.p, qa.st_po = c.st_po.p;
-        qa.high_prio = 1;
+        const MatchArgs ma = c.match_args(c.C);
+        const SeqArgs qa = c.seq_args(c.C);
         if (launch) {
             launch_mb_match(ma, pl, q, st);
             if ((rc = launched("mixed batch match launch")) != PV_OK) return rc;
@@ -3492,72 +3374,44 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
             return refused("rotation chain");
         }
     } else if (cm == 0 && launch) {
-        PropArgs pa{};
-        pa.N = d.N, pa.hs = d.hs, pa.HP = c.HP, pa.C = c.C, pa.hop = d.hop, pa.TR = c.TR, pa.rows = c.C;
-        pa.two_pi_hop = d.two_pi_hop;
-        pa.phase = c.phase.p, pa.outphase = c.outphase.p, pa.st_pp = c.st_pp.p, pa.st_po = c.st_po.p;
+        const PropArgs pa = c.prop_args(c.C);
         if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
         if ((rc = launched("mixed batch propagation launch")) != PV_OK) return rc;
     }
     float *stream = c.stream.p ? c.stream.p : b->dev->mix_stream.p;
-    const std::vector<MbVariant> &runs = g.vr;
+    const std::vector<VariantRun> &runs = g.vr;
     for (size_t a = 0; a < runs.size();) {
-        // the synthesis variant's entries: consecutive, they differ in interp only
-        size_t e = a + 1;
-        while (e < runs.size() && runs[e].dfc == runs[a].dfc && runs[e].res == runs[a].res && runs[e].fast == runs[a].fast) ++e;
-        const MbVariant &ra0 = runs[a];
+        const size_t e = variant_group_end(runs, a);
+        const VariantRun &ra0 = runs[a];
         PoolLaunch sub = pl;
         sub.slots = pl.slots + ra0.first;
         sub.nslots = runs[e - 1].first + runs[e - 1].count - ra0.first;
         int max_runs = 1;
         for (size_t k = a; k < e; ++k) max_runs = std::max(max_runs, runs[k].max_runs);
-        SynthArgs sa{};
-        sa.tb = c.tb;
-        sa.hop = d.hop;
-        sa.C = c.C;
-        sa.two_pi_hop = d.two_pi_hop;
+        // the group's variant in place of stream 0's: whether to compensate, to resample, to take the fast kernel;
+        // the compensation factor and the gain themselves are per slot (PoolParams), the block's are neutral
+        SynthArgs sa = c.synth_args(c.C);
         sa.do_freq_comp = ra0.dfc;
         sa.freq_comp = 1;
         sa.fixed_gain = 1;
-        sa.inv_n = d.inv_n;
-        sa.robotic = d.robotic ? 1 : 0;
-        sa.voc_band_len = -1;
-        sa.coremode = cm < 0 ? 0 : cm;
-        sa.TR = c.TR;
-        sa.rows = c.C;
-        sa.PKP = c.PKP;
-        sa.mag = c.mag.p, sa.phase = c.phase.p, sa.outphase = c.outphase.p, sa.peaks = c.peaks.p, sa.npk = c.npk.p;
-        sa.modes = c.modes.p, sa.rot = c.rot.p, sa.frames = c.frames.p, sa.FR = c.FR;
-        ChainArgs ca{};
-        ca.N = d.N;
-        ca.rows = c.C;
-        ca.C = c.C;
-        ca.AR = c.chain_AR;
-        ca.smask = c.chain_smask;
-        ca.waves = c.chain_waves;
-        ca.runs = 1; // (per slot: MbSlot)
-        ca.st_acc = c.st_acc.p;
+        ChainArgs ca = c.chain_args(c.C);
         ca.stream = stream;
         ca.resample = ra0.res;
-        ca.frames = c.frames.p;
-        ca.FR = c.FR;
         ca.fast = ra0.fast;
         if (!launch_mb_synth_chain(sa, ca, sub, q + ra0.first, ms + ra0.first, max_runs, st, launch))
             return refused("synthesis + overlap-add");
         if ((rc = launched("mixed batch synthesis + overlap-add launch")) != PV_OK) return rc;
         for (size_t k = a; k < e && ra0.res; ++k) {
-            const MbVariant &rv = runs[k];
+            const VariantRun &rv = runs[k];
             if (rv.max_tiles <= 0 && launch) continue; // (dropped or truncated slices only: no output completed)
             PoolLaunch rs = pl;
             rs.slots = pl.slots + rv.first;
             rs.nslots = rv.count;
             rs.max_tiles = rv.max_tiles;
-            ResArgs ra{};
-            ra.rows = c.C;
-            ra.smask = c.chain_smask;
+            ResArgs ra = c.res_args(c.C); // (not the uniform part: each slot brings its own filter set-up, PoolParams)
             ra.stream = stream;
             ra.interp = rv.interp;
-            ra.lds_floats = rv.lds_floats; // (the largest of the entries' slots; each slot brings its own set-up)
+            ra.lds_floats = rv.lds_floats; // (the largest of the entries' slots)
             ra.tab_bytes = rv.tab_bytes;
             ra.fast = rv.fast;
             if (!launch_mb_resample(ra, rs, q + rv.first, st, launch)) return refused("resampling");
@@ -3654,8 +3508,7 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
     int st = mb_plan_tabs(b, c.fast_arith, on_device ? 2 : 1, stg);
     if (st != PV_OK) return st;
     const float4 *tab_base = stg.replace_tabs ? stg.new_tabs.p : b->dev->d_tabs.p;
-    const bool bypass = c.d.robotic || c.d.whisper || c.d.constant || c.d.vocoder;
-    const int cm = bypass ? -1 : ((c.d.cfg.coremode == 1 || c.d.cfg.coremode == 2) ? c.d.cfg.coremode : 0);
+    const int cm = phase_mode(c.d);
     int64_t maxT = 0;
     for (const pv_mbatch::Stream &t : b->s) maxT = std::max(maxT, (int64_t)t.plan.slices.size());
     const int G = (int)((maxT + Tc - 1) / Tc);
@@ -3871,8 +3724,8 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
             if (!on_device) e.ps.wden_off += shift;
             if (e.otab_in_blob) e.ps.otab_off += shift;
             if (k == 0 || e.key != ev[k - 1].key)
-                gr.vr.push_back(MbVariant{(int)k, 0, e.key >> 3 & 1, e.key >> 2 & 1, e.key >> 1 & 1, e.key & 1, 0, 0, 0, 1});
-            MbVariant &r = gr.vr.back();
+                gr.vr.push_back(VariantRun{(int)k, 0, e.key >> 3 & 1, e.key >> 2 & 1, e.key >> 1 & 1, e.key & 1, 0, 0, 0, 1});
+            VariantRun &r = gr.vr.back();
             ++r.count;
             r.max_tiles = std::max(r.max_tiles, (int)e.ps.res_ntiles);
             r.lds_floats = std::max(r.lds_floats, (int)e.q.lds_floats);
