@@ -870,6 +870,10 @@ template <int NC, int WPB> __global__ __launch_bounds__(64 * WPB) void pv_analyz
     analyze_wave_role<NC, WPB * WF<NC>::LDS_CF * sizeof(cf)>(a, row, tl, lds);
 }
 
+// The most dynamic LDS a kernel of this file asks for (the CU's 160 KiB less a margin); every "does it fit" test and
+// the attribute below use this one value.
+constexpr size_t kMaxDynLds = 160 * 1024 - 512;
+
 // Kernels may need more than the default 64 KiB of dynamic LDS.  hipFuncSetAttribute applies to the device that is
 // current at the call, so the "done" mark is kept per kernel AND device (a bit per device index; atomics because two
 // host threads may launch for the first time together -- setting the attribute twice is harmless).
@@ -879,8 +883,23 @@ template <typename K> static void allow_big_lds_dev(K kernel, unsigned long long
     const unsigned long long bit = 1ull << (dev & 63);
     if (__atomic_load_n(&done_mask, __ATOMIC_ACQUIRE) & bit) return;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 512);
+                              (int)kMaxDynLds);
     __atomic_fetch_or(&done_mask, bit, __ATOMIC_RELEASE);
+}
+// Launch of a kernel that may need the attribute: the mark lives here, one per kernel instantiation K, and the
+// attribute is set before K's first launch on a device.  (Kernels that never need it are launched directly.)
+template <auto K, typename... Args>
+static void launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+    static unsigned long long done_mask = 0;
+    allow_big_lds_dev(K, done_mask);
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+}
+// (for a launcher that chooses among instantiations of which only some need the attribute; the others fit the
+// default and stay without it)
+template <auto K, bool kBigLds, typename... Args>
+static void launch_maybe_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+    if constexpr (kBigLds) launch_big_lds<K>(grid, block, lds, st, args...);
+    else hipLaunchKernelGGL(K, grid, block, lds, st, args...);
 }
 
 void launch_analyze(const AnalyzeArgs &a, hipStream_t st) {
@@ -910,9 +929,7 @@ void launch_analyze(const AnalyzeArgs &a, hipStream_t st) {
             }
             constexpr int WPB = 1;
             const int grid = 8 * ((a.rows + 7) / 8) * ((a.Tn + WPB - 1) / WPB);
-            static unsigned long long big = 0;
-            allow_big_lds_dev(pv_analyze_wave_kernel<2048, WPB>, big);
-            hipLaunchKernelGGL((pv_analyze_wave_kernel<2048, WPB>), dim3(grid), dim3(64 * WPB),
+            launch_big_lds<pv_analyze_wave_kernel<2048, WPB>>(dim3(grid), dim3(64 * WPB),
                                WPB * WF<2048>::LDS_CF * sizeof(cf) + 4 * PV_ATAN_BLOB_WORDS, st, a);
         }
         return;
@@ -1498,14 +1515,12 @@ __host__ __device__ size_t seq_lds_bytes(const SeqArgs &a) { return sizeof(float
 
 void launch_seq(const SeqArgs &a, hipStream_t st) {
     const size_t lds = seq_lds_bytes(a);
-    static unsigned long long big1 = 0, big3 = 0;
     if (a.narrow && a.PKP <= 3 * 1024) {
         // three peaks per lane: a third of the waves (two per row at 2048 points), so that the kernel finds room on
         // a CU beside the fused kernel's workgroup
         int nt = ((a.PKP + 2) / 3 + 63) & ~63;
         if (nt > 1024) nt = 1024;
-        allow_big_lds_dev(pv_seq_kernel<3>, big3);
-        hipLaunchKernelGGL(pv_seq_kernel<3>, dim3(a.rows), dim3(nt), lds, st, a);
+        launch_big_lds<pv_seq_kernel<3>>(dim3(a.rows), dim3(nt), lds, st, a);
         return;
     }
     const int nt = seq_threads(a.PKP);
@@ -1522,19 +1537,15 @@ void launch_seq(const SeqArgs &a, hipStream_t st) {
     // small batches, which are bound by this chain and leave the LDS free (20 streams: 10.6 -> 11.0 G samples/s).
     const int D = depth ? (depth <= 4 ? 4 : 8) : (a.rows <= 96 ? 8 : 4);
     const size_t ring_lds = ((lds + 15) & ~(size_t)15) + (size_t)D * nt * sizeof(PeakRec);
-    if (!no_ring && a.PKP <= nt && ring_lds <= 160 * 1024 - 512) {
-        static unsigned long long bigr4 = 0, bigr8 = 0;
+    if (!no_ring && a.PKP <= nt && ring_lds <= kMaxDynLds) {
         if (D == 4) {
-            allow_big_lds_dev(pv_seq_ring_kernel<4>, bigr4);
-            hipLaunchKernelGGL(pv_seq_ring_kernel<4>, dim3(a.rows), dim3(nt), ring_lds, st, a);
+            launch_big_lds<pv_seq_ring_kernel<4>>(dim3(a.rows), dim3(nt), ring_lds, st, a);
         } else {
-            allow_big_lds_dev(pv_seq_ring_kernel<8>, bigr8);
-            hipLaunchKernelGGL(pv_seq_ring_kernel<8>, dim3(a.rows), dim3(nt), ring_lds, st, a);
+            launch_big_lds<pv_seq_ring_kernel<8>>(dim3(a.rows), dim3(nt), ring_lds, st, a);
         }
         return;
     }
-    allow_big_lds_dev(pv_seq_kernel<1>, big1);
-    hipLaunchKernelGGL(pv_seq_kernel<1>, dim3(a.rows), dim3(nt), lds, st, a);
+    launch_big_lds<pv_seq_kernel<1>>(dim3(a.rows), dim3(nt), lds, st, a);
 }
 
 // (true when the fused kernel was launched; false: the caller launches the two kernels)
@@ -1544,10 +1555,8 @@ bool launch_phase(const MatchArgs &m, const SeqArgs &a, hipStream_t st) {
     const size_t seq_l = ((seq_lds_bytes(a) + 15) & ~(size_t)15) + (size_t)D * nt * sizeof(PeakRec);
     const size_t match_l = (size_t)(nt / 64) * match_wave_lds(m.hs, m.PKP);
     const size_t lds = seq_l > match_l ? seq_l : match_l;
-    if (a.PKP > nt || lds > 160 * 1024 - 512 || a.narrow) return false;
-    static unsigned long long big = 0;
-    allow_big_lds_dev(pv_phase_kernel<D>, big);
-    hipLaunchKernelGGL(pv_phase_kernel<D>, dim3(a.rows), dim3(nt), lds, st, m, a);
+    if (a.PKP > nt || lds > kMaxDynLds || a.narrow) return false;
+    launch_big_lds<pv_phase_kernel<D>>(dim3(a.rows), dim3(nt), lds, st, m, a);
     return true;
 }
 
@@ -2245,9 +2254,7 @@ void launch_synth(const SynthArgs &a, hipStream_t st) {
                 else hipLaunchKernelGGL((pv_synth_wave_kernel<1024, WPB, 2>), dim3(grid), dim3(64 * WPB), lds, st, a);
                 return;
             }
-            static unsigned long long big1 = 0;
-            allow_big_lds_dev(pv_synth_wave_kernel<1024, WPB>, big1);
-            hipLaunchKernelGGL((pv_synth_wave_kernel<1024, WPB>), dim3(grid), dim3(64 * WPB),
+            launch_big_lds<pv_synth_wave_kernel<1024, WPB>>(dim3(grid), dim3(64 * WPB),
                                WPB * WF<1024>::LDS_CF * sizeof(cf), st, a);
         } else {
             constexpr int WPB = 1;
@@ -2261,9 +2268,7 @@ void launch_synth(const SynthArgs &a, hipStream_t st) {
                 else hipLaunchKernelGGL((pv_synth_wave_kernel<2048, WPB, 2>), dim3(grid), dim3(64 * WPB), lds, st, a);
                 return;
             }
-            static unsigned long long big2 = 0;
-            allow_big_lds_dev(pv_synth_wave_kernel<2048, WPB>, big2);
-            hipLaunchKernelGGL((pv_synth_wave_kernel<2048, WPB>), dim3(grid), dim3(64 * WPB),
+            launch_big_lds<pv_synth_wave_kernel<2048, WPB>>(dim3(grid), dim3(64 * WPB),
                                WPB * WF<2048>::LDS_CF * sizeof(cf), st, a);
         }
         return;
@@ -2271,9 +2276,7 @@ void launch_synth(const SynthArgs &a, hipStream_t st) {
     const int grid = 8 * ((a.rows + 7) / 8) * a.Tn;
     const size_t lds = (size_t)(2 * a.tb.nc + 1) * sizeof(float2) + sizeof(float) * (a.tb.hs + 4 + a.PKP) +
                        sizeof(uint16_t) * a.PKP;
-    static unsigned long long big = 0;
-    allow_big_lds_dev(pv_synth_kernel, big);
-    hipLaunchKernelGGL(pv_synth_kernel, dim3(grid), dim3(generic_fft_threads(a.tb.nc)), lds, st, a);
+    launch_big_lds<pv_synth_kernel>(dim3(grid), dim3(generic_fft_threads(a.tb.nc)), lds, st, a);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -2568,9 +2571,7 @@ void launch_cepstral(const CepstralArgs &a, hipStream_t st) {
     const int grid = 8 * ((a.rows + 7) / 8) * a.Tn;
     if (a.tb.nc != 1024 && a.tb.nc != 2048) {
         const size_t lds = (size_t)(2 * a.tb.nc + 1) * sizeof(float2) + sizeof(float) * (a.tb.hs + 4 + 64);
-        static unsigned long long big = 0;
-        allow_big_lds_dev(pv_cepstral_kernel, big);
-        hipLaunchKernelGGL(pv_cepstral_kernel, dim3(grid), dim3(generic_fft_threads(a.tb.nc)), lds, st, a);
+        launch_big_lds<pv_cepstral_kernel>(dim3(grid), dim3(generic_fft_threads(a.tb.nc)), lds, st, a);
         return;
     }
     if (a.tb.nc == 1024) {
@@ -2785,16 +2786,12 @@ size_t ola_lds_bytes(const OlaArgs &a, int rows_per_group) {
 void launch_ola(const OlaArgs &a, hipStream_t st) {
     const size_t lds = ola_lds_bytes(a, kOlaRows);
     const dim3 grid(a.ntiles, (a.rows + kOlaRows - 1) / kOlaRows);
-    static unsigned long long big0 = 0, big1 = 0, big2 = 0;
     if (!a.resample) {
-        allow_big_lds_dev(pv_ola_kernel<0>, big0);
-        hipLaunchKernelGGL(pv_ola_kernel<0>, grid, dim3(kTileOut), lds, st, a);
+        launch_big_lds<pv_ola_kernel<0>>(grid, dim3(kTileOut), lds, st, a);
     } else if (!a.interp) {
-        allow_big_lds_dev(pv_ola_kernel<1>, big1);
-        hipLaunchKernelGGL(pv_ola_kernel<1>, grid, dim3(kTileOut), lds, st, a);
+        launch_big_lds<pv_ola_kernel<1>>(grid, dim3(kTileOut), lds, st, a);
     } else {
-        allow_big_lds_dev(pv_ola_kernel<2>, big2);
-        hipLaunchKernelGGL(pv_ola_kernel<2>, grid, dim3(kTileOut), lds, st, a);
+        launch_big_lds<pv_ola_kernel<2>>(grid, dim3(kTileOut), lds, st, a);
     }
 }
 
@@ -3252,86 +3249,98 @@ size_t chain_lds_bytes(const ChainArgs &a, int nc_wave) {
     return (size_t)a.waves * per_wave + chain_shared_bytes(a);
 }
 
-template <int NC, int kPlainCore> static void launch_synth_chain_res(const SynthArgs &s, const ChainArgs &c, hipStream_t st) {
-    const size_t lds = chain_lds_bytes(c, NC);
-    const bool use_fast = kPlainCore >= 0 && c.fast;
-    const int kMaxThreads = use_fast ? chain_kernel_max_threads(NC, kPlainCore, true) : chain_kernel_max_threads(NC, kPlainCore, false);
-    if (64 * c.waves > kMaxThreads) { // (never: Core::init sizes chain_waves by the same rule; a launch beyond the bounds faults)
-        fprintf(stderr, "audiomod_pv: fused kernel launch of %d waves exceeds its bounds (%d threads): not launched\n", c.waves, kMaxThreads);
-        return;
-    }
-    const dim3 grid(c.rows, c.runs), block(64 * c.waves);
-    static unsigned long long m0 = 0, m1 = 0, f0 = 0, f1 = 0;
-    if constexpr (kPlainCore >= 0) { // the specialisations have a free-form (PV_ARITH_FAST) twin
-        if (c.fast) {
-            if (!c.resample) {
-                allow_big_lds_dev(pv_synth_chain_kernel<NC, kPlainCore, 0, true>, f0);
-                hipLaunchKernelGGL((pv_synth_chain_kernel<NC, kPlainCore, 0, true>), grid, block, lds, st, s, c);
-            } else {
-                allow_big_lds_dev(pv_synth_chain_kernel<NC, kPlainCore, 1, true>, f1);
-                hipLaunchKernelGGL((pv_synth_chain_kernel<NC, kPlainCore, 1, true>), grid, block, lds, st, s, c);
-            }
-            return;
-        }
-    }
-    if (!c.resample) {
-        allow_big_lds_dev(pv_synth_chain_kernel<NC, kPlainCore, 0>, m0);
-        hipLaunchKernelGGL((pv_synth_chain_kernel<NC, kPlainCore, 0>), grid, block, lds, st, s, c);
-    } else {
-        allow_big_lds_dev(pv_synth_chain_kernel<NC, kPlainCore, 1>, m1);
-        hipLaunchKernelGGL((pv_synth_chain_kernel<NC, kPlainCore, 1>), grid, block, lds, st, s, c);
-    }
+// --- Where a fused kernel is chosen (all four sets: this batch kernel and the pool / pmix / mb slot-table kernels) ---
+static bool chain_nc_has_wave(int nc) { return nc == 256 || nc == 512 || nc == 1024 || nc == 2048; }
+
+// The specialisation (kPlainCore) a configuration gets: 0 / 1 / 2 = the plain kernel of that core mode, 3 = frequency
+// compensation with the phase-locked core (formant / gender modes; nc 1024, that is fft 2048, only), -1 = the all-modes kernel.
+static int synth_chain_plain_core(const SynthArgs &s) {
+    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
+    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
+                           !synth_generic_only() && s.coremode == 1;
+    if (fc_locked) return s.tb.nc == 1024 ? 3 : -1;
+    return plain ? s.coremode : -1;
 }
 // does launch_synth_chain pick a free-form kernel for this configuration?  (the engine then uploads the window-sum
 // denominators as reciprocals)
-bool synth_chain_has_fast(const SynthArgs &s) {
-    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
-    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                           !synth_generic_only() && s.coremode == 1;
-    return (s.tb.nc == 1024 && (plain || fc_locked)) || (s.tb.nc == 2048 && plain) ||
-           ((s.tb.nc == 512 || s.tb.nc == 256) && plain);
+bool synth_chain_has_fast(const SynthArgs &s) { return chain_nc_has_wave(s.tb.nc) && synth_chain_plain_core(s) >= 0; }
+
+// The ladder from run-time values to template arguments, in three steps: nc -> NC, the predicate's value -> kPlainCore,
+// (c.resample, c.fast) -> (kRes, kFast).  A new size or specialisation is added here, once.  What differs between the
+// kernel sets is in `Set` (BatchChainSet below, PoolChainSet, PmixChainSet, MbChainSet further down):
+//   set.launch<NC, kPlainCore, kRes, kFast>(c, block, lds)   names the kernel, its grid and trailing arguments;
+//   Set::max_threads(NC, kPlainCore, kFast)                  the launch bounds the kernel is compiled for;
+//   Set::fit_waves(c, max_threads)                           what a launch wider than that does (false: no launch).
+// launch == false: the checks only.
+template <class Set, int NC, int kPlainCore> static bool launch_chain_variant(const Set &set, const ChainArgs &c_in, bool launch) {
+    const bool use_fast = kPlainCore >= 0 && c_in.fast;
+    const int max_threads = use_fast ? Set::max_threads(NC, kPlainCore, true) : Set::max_threads(NC, kPlainCore, false);
+    ChainArgs c = c_in;
+    if (!Set::fit_waves(c, max_threads)) return false;
+    const size_t lds = chain_lds_bytes(c, NC);
+    if (!launch) return true;
+    const dim3 block(64 * c.waves);
+    if constexpr (kPlainCore >= 0) { // the specialisations have a free-form (PV_ARITH_FAST) twin
+        if (c.fast) {
+            if (!c.resample) set.template launch<NC, kPlainCore, 0, true>(c, block, lds);
+            else set.template launch<NC, kPlainCore, 1, true>(c, block, lds);
+            return true;
+        }
+    }
+    if (!c.resample) set.template launch<NC, kPlainCore, 0, false>(c, block, lds);
+    else set.template launch<NC, kPlainCore, 1, false>(c, block, lds);
+    return true;
+}
+template <class Set, int NC> static bool launch_chain_core(const Set &set, const ChainArgs &c, int plain_core, bool launch) {
+    if constexpr (NC == 1024) // the only size with the frequency-compensation specialisation
+        if (plain_core == 3) return launch_chain_variant<Set, NC, 3>(set, c, launch);
+    switch (plain_core) {
+    case 1: return launch_chain_variant<Set, NC, 1>(set, c, launch);
+    case 0: return launch_chain_variant<Set, NC, 0>(set, c, launch);
+    case 2: return launch_chain_variant<Set, NC, 2>(set, c, launch);
+    default: return launch_chain_variant<Set, NC, -1>(set, c, launch);
+    }
+}
+// (nc: the wave transform's size; false where there is none)
+template <class Set> static bool launch_chain(const Set &set, const SynthArgs &s, int nc, const ChainArgs &c, bool launch) {
+    const int plain_core = synth_chain_plain_core(s);
+    switch (nc) {
+    case 256: return launch_chain_core<Set, 256>(set, c, plain_core, launch);   // fft 512
+    case 512: return launch_chain_core<Set, 512>(set, c, plain_core, launch);   // fft 1024
+    case 1024: return launch_chain_core<Set, 1024>(set, c, plain_core, launch); // fft 2048
+    case 2048: return launch_chain_core<Set, 2048>(set, c, plain_core, launch); // fft 4096
+    default: return false;
+    }
 }
 
-void launch_synth_chain(const SynthArgs &s, const ChainArgs &c, hipStream_t st) {
-    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
-    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                           !synth_generic_only() && s.coremode == 1;
-    if (s.tb.nc == 256) { // fft 512
-        if (plain && s.coremode == 1) launch_synth_chain_res<256, 1>(s, c, st);
-        else if (plain && s.coremode == 0) launch_synth_chain_res<256, 0>(s, c, st);
-        else if (plain) launch_synth_chain_res<256, 2>(s, c, st);
-        else launch_synth_chain_res<256, -1>(s, c, st);
-    } else if (s.tb.nc == 512) { // fft 1024: the plain specialisations (sixteen waves, as the engine sizes the launch), else all modes
-        if (plain && s.coremode == 1) launch_synth_chain_res<512, 1>(s, c, st);
-        else if (plain && s.coremode == 0) launch_synth_chain_res<512, 0>(s, c, st);
-        else if (plain) launch_synth_chain_res<512, 2>(s, c, st);
-        else launch_synth_chain_res<512, -1>(s, c, st);
-    } else if (s.tb.nc == 1024) {
-        if (fc_locked) launch_synth_chain_res<1024, 3>(s, c, st);
-        else if (plain && s.coremode == 1) launch_synth_chain_res<1024, 1>(s, c, st);
-        else if (plain && s.coremode == 0) launch_synth_chain_res<1024, 0>(s, c, st);
-        else if (plain) launch_synth_chain_res<1024, 2>(s, c, st);
-        else launch_synth_chain_res<1024, -1>(s, c, st);
-    } else {
-        if (plain && s.coremode == 1) launch_synth_chain_res<2048, 1>(s, c, st);
-        else if (plain && s.coremode == 0) launch_synth_chain_res<2048, 0>(s, c, st);
-        else if (plain) launch_synth_chain_res<2048, 2>(s, c, st);
-        else launch_synth_chain_res<2048, -1>(s, c, st);
+struct BatchChainSet { // grid (rows, runs); no trailing arguments
+    const SynthArgs &s;
+    hipStream_t st;
+    static constexpr int max_threads(int NC, int kPlainCore, bool kFast) { return chain_kernel_max_threads(NC, kPlainCore, kFast); }
+    static bool fit_waves(const ChainArgs &c, int max_threads) {
+        if (64 * c.waves <= max_threads) return true;
+        // (never: Core::init sizes chain_waves by the same rule; a launch beyond the bounds faults)
+        fprintf(stderr, "audiomod_pv: fused kernel launch of %d waves exceeds its bounds (%d threads): not launched\n", c.waves, max_threads);
+        return false;
     }
+    template <int NC, int kPlainCore, int kRes, bool kFast> void launch(const ChainArgs &c, dim3 block, size_t lds) const {
+        launch_big_lds<pv_synth_chain_kernel<NC, kPlainCore, kRes, kFast>>(dim3(c.rows, c.runs), block, lds, st, s, c);
+    }
+};
+void launch_synth_chain(const SynthArgs &s, const ChainArgs &c, hipStream_t st) {
+    // (the engine comes here for the four sizes with a wave transform only; any other would get the 4096-point
+    // kernel, as it always did)
+    (void)launch_chain(BatchChainSet{s, st}, s, chain_nc_has_wave(s.tb.nc) ? s.tb.nc : 2048, c, true);
 }
 
 void launch_frames_chain(const ChainArgs &c, hipStream_t st) {
     const size_t lds = chain_lds_bytes(c, 0);
     const dim3 grid(c.rows, c.runs), block(64 * c.waves);
-    static unsigned long long m0 = 0, m1 = 0;
     if (!c.resample) {
-        allow_big_lds_dev(pv_frames_chain_kernel<0>, m0);
-        hipLaunchKernelGGL(pv_frames_chain_kernel<0>, grid, block, lds, st, c);
+        launch_big_lds<pv_frames_chain_kernel<0>>(grid, block, lds, st, c);
     } else {
-        allow_big_lds_dev(pv_frames_chain_kernel<1>, m1);
-        hipLaunchKernelGGL(pv_frames_chain_kernel<1>, grid, block, lds, st, c);
+        launch_big_lds<pv_frames_chain_kernel<1>>(grid, block, lds, st, c);
     }
 }
 
@@ -3710,13 +3719,10 @@ __global__ __launch_bounds__(kTileOut) __attribute__((amdgpu_waves_per_eu(4))) v
 template <int NR> static void launch_resample_fast_rows(const ResArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
     const dim3 grid(a.ntiles, (a.rows + NR - 1) / NR);
-    static unsigned long long m1 = 0, m2 = 0;
     if (a.interp) {
-        allow_big_lds_dev(pv_resample_fast_kernel<2, NR>, m2);
-        hipLaunchKernelGGL((pv_resample_fast_kernel<2, NR>), grid, dim3(kTileOut), lds, st, a);
+        launch_big_lds<pv_resample_fast_kernel<2, NR>>(grid, dim3(kTileOut), lds, st, a);
     } else {
-        allow_big_lds_dev(pv_resample_fast_kernel<1, NR>, m1);
-        hipLaunchKernelGGL((pv_resample_fast_kernel<1, NR>), grid, dim3(kTileOut), lds, st, a);
+        launch_big_lds<pv_resample_fast_kernel<1, NR>>(grid, dim3(kTileOut), lds, st, a);
     }
 }
 static void launch_resample_fast(const ResArgs &a, hipStream_t st) {
@@ -3736,13 +3742,10 @@ static void launch_resample_fast(const ResArgs &a, hipStream_t st) {
         const size_t padded = fl * (nrl * res_mfma_xstride(a.lds_floats) + kTileOut / 64);
         const size_t lds = (size_t)a.tab_bytes + std::max(fl * nrl * (size_t)a.lds_floats, padded);
         const dim3 grid(a.ntiles, (a.rows + kResMfmaRows - 1) / kResMfmaRows);
-        static unsigned long long m1 = 0, m2 = 0;
         if (a.interp) {
-            allow_big_lds_dev(pv_resample_mfma_kernel<2>, m2);
-            hipLaunchKernelGGL(pv_resample_mfma_kernel<2>, grid, dim3(kTileOut), lds, st, a);
+            launch_big_lds<pv_resample_mfma_kernel<2>>(grid, dim3(kTileOut), lds, st, a);
         } else {
-            allow_big_lds_dev(pv_resample_mfma_kernel<1>, m1);
-            hipLaunchKernelGGL(pv_resample_mfma_kernel<1>, grid, dim3(kTileOut), lds, st, a);
+            launch_big_lds<pv_resample_mfma_kernel<1>>(grid, dim3(kTileOut), lds, st, a);
         }
         return;
     }
@@ -3758,13 +3761,10 @@ void launch_resample(const ResArgs &a, hipStream_t st) {
     if (a.fast) return launch_resample_fast(a, st);
     const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * kResRows;
     const dim3 grid(a.ntiles, (a.rows + kResRows - 1) / kResRows);
-    static unsigned long long m1 = 0, m2 = 0;
     if (a.interp) {
-        allow_big_lds_dev(pv_resample_kernel<2>, m2);
-        hipLaunchKernelGGL(pv_resample_kernel<2>, grid, dim3(kTileOut), lds, st, a);
+        launch_big_lds<pv_resample_kernel<2>>(grid, dim3(kTileOut), lds, st, a);
     } else {
-        allow_big_lds_dev(pv_resample_kernel<1>, m1);
-        hipLaunchKernelGGL(pv_resample_kernel<1>, grid, dim3(kTileOut), lds, st, a);
+        launch_big_lds<pv_resample_kernel<1>>(grid, dim3(kTileOut), lds, st, a);
     }
 }
 
@@ -3833,7 +3833,7 @@ static size_t stream_lds_bytes(const StreamArgs &s) {
 }
 
 bool stream_kernel_supported(const StreamArgs &s) {
-    return (s.aa.tb.nc == 1024 || s.aa.tb.nc == 2048) && stream_lds_bytes(s) <= 160 * 1024 - 512;
+    return (s.aa.tb.nc == 1024 || s.aa.tb.nc == 2048) && stream_lds_bytes(s) <= kMaxDynLds;
 }
 
 // The wave-per-frame analysis code addresses atan2f's table by a compile-time LDS address, which is right only while
@@ -3856,13 +3856,9 @@ bool lds_starts_at_zero() {
 void launch_stream(const StreamArgs &s, hipStream_t st) {
     const size_t lds = stream_lds_bytes(s);
     if (s.aa.tb.nc == 1024) {
-        static unsigned long long big1 = 0;
-        allow_big_lds_dev(pv_stream_kernel<1024>, big1);
-        hipLaunchKernelGGL((pv_stream_kernel<1024>), dim3(1), dim3(kStreamThreads), lds, st, s);
+        launch_big_lds<pv_stream_kernel<1024>>(dim3(1), dim3(kStreamThreads), lds, st, s);
     } else {
-        static unsigned long long big2 = 0;
-        allow_big_lds_dev(pv_stream_kernel<2048>, big2);
-        hipLaunchKernelGGL((pv_stream_kernel<2048>), dim3(1), dim3(kStreamThreads), lds, st, s);
+        launch_big_lds<pv_stream_kernel<2048>>(dim3(1), dim3(kStreamThreads), lds, st, s);
     }
 }
 
@@ -4130,32 +4126,34 @@ __global__ __launch_bounds__(128) void pv_pool_analyze_split_kernel(const Analyz
     analyze_split_role<WF2048S, WF2048S::LDS_CF * sizeof(cf)>(pool_view(a, ps), row, tl, reinterpret_cast<cf *>(smem_raw));
 }
 
-bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st) {
+// The slot-table analysis launch of all three sets (pool, pmix, mb): grid (rows * frames, slots), one wave per frame
+// or, at 4096 points with a.split, two.  `Set` names the set's two kernels (set.wave<NC, kBigLds>, set.split) and
+// appends its trailing arguments.  Only the 4096-point wave kernel needs more than the default dynamic LDS.
+template <class Set> static bool launch_slot_analyze(const Set &set, const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st) {
     const dim3 grid(a.rows * p.max_tn, p.nslots);
     const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
     switch (a.tb.nc) {
-    case 256:
-        hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<256>, grid, dim3(64), WF<256>::LDS_CF * sizeof(cf) + atab, st, a, p);
-        return true;
-    case 512:
-        hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<512>, grid, dim3(64), WF<512>::LDS_CF * sizeof(cf) + atab, st, a, p);
-        return true;
-    case 1024:
-        hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<1024>, grid, dim3(64), WF<1024>::LDS_CF * sizeof(cf) + atab, st, a, p);
-        return true;
+    case 256: set.template wave<256, false>(grid, WF<256>::LDS_CF * sizeof(cf) + atab, st, a); return true;
+    case 512: set.template wave<512, false>(grid, WF<512>::LDS_CF * sizeof(cf) + atab, st, a); return true;
+    case 1024: set.template wave<1024, false>(grid, WF<1024>::LDS_CF * sizeof(cf) + atab, st, a); return true;
     case 2048:
-        if (a.split) {
-            hipLaunchKernelGGL(pv_pool_analyze_split_kernel, grid, dim3(WF2048S::LANES),
-                               WF2048S::LDS_CF * sizeof(cf) + atab + 64, st, a, p);
-        } else {
-            static unsigned long long big = 0;
-            allow_big_lds_dev(pv_pool_analyze_wave_kernel<2048>, big);
-            hipLaunchKernelGGL(pv_pool_analyze_wave_kernel<2048>, grid, dim3(64), WF<2048>::LDS_CF * sizeof(cf) + atab,
-                               st, a, p);
-        }
+        if (a.split) set.split(grid, WF2048S::LDS_CF * sizeof(cf) + atab + 64, st, a);
+        else set.template wave<2048, true>(grid, WF<2048>::LDS_CF * sizeof(cf) + atab, st, a);
         return true;
     default: return false;
     }
+}
+struct PoolAnalyzeSet { // trailing argument p
+    const PoolLaunch &p;
+    template <int NC, bool kBigLds> void wave(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
+        launch_maybe_big_lds<pv_pool_analyze_wave_kernel<NC>, kBigLds>(grid, dim3(64), lds, st, a, p);
+    }
+    void split(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
+        hipLaunchKernelGGL(pv_pool_analyze_split_kernel, grid, dim3(WF2048S::LANES), lds, st, a, p);
+    }
+};
+bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st) {
+    return launch_slot_analyze(PoolAnalyzeSet{p}, a, p, st);
 }
 
 // phase-locked mode: match + rotation chain of a slot's rows (pv_phase_kernel), one workgroup per (channel, slot)
@@ -4198,13 +4196,11 @@ static size_t pool_phase_lds(int hs, int PKP) {
     const size_t match_l = (size_t)(nt / 64) * match_wave_lds(hs, PKP);
     return seq_l > match_l ? seq_l : match_l;
 }
-bool pool_phase_supported(int hs, int PKP) { return PKP <= seq_threads(PKP) && pool_phase_lds(hs, PKP) <= 160 * 1024 - 512; }
+bool pool_phase_supported(int hs, int PKP) { return PKP <= seq_threads(PKP) && pool_phase_lds(hs, PKP) <= kMaxDynLds; }
 
 bool launch_pool_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, hipStream_t st) {
     if (!pool_phase_supported(a.hs, a.PKP)) return false;
-    static unsigned long long big = 0;
-    allow_big_lds_dev(pv_pool_phase_kernel<kPoolSeqDepth>, big);
-    hipLaunchKernelGGL(pv_pool_phase_kernel<kPoolSeqDepth>, dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
+    launch_big_lds<pv_pool_phase_kernel<kPoolSeqDepth>>(dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
                        pool_phase_lds(a.hs, a.PKP), st, m, a, p);
     return true;
 }
@@ -4270,72 +4266,23 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     pool_synth_chain_role<NC, kPlainCore, kRes, kFast>(sv, cv, blockIdx.x, smem_raw);
 }
 
-template <int NC, int kPlainCore>
-static bool launch_pool_synth_chain_res(const SynthArgs &s, const ChainArgs &c_in, const PoolLaunch &p, hipStream_t st,
-                                        bool launch) {
-    const bool use_fast = kPlainCore >= 0 && c_in.fast;
-    const int kMaxThreads = use_fast ? pool_chain_max_threads(NC, kPlainCore, true) : pool_chain_max_threads(NC, kPlainCore, false);
-    ChainArgs c = c_in;
-    if (64 * c.waves > kMaxThreads) c.waves = kMaxThreads / 64;
-    if (c.waves < 1) return false;
-    const size_t lds = chain_lds_bytes(c, NC);
-    if (!launch) return true;
-    const dim3 grid(c.rows, p.nslots), block(64 * c.waves);
-    static unsigned long long m0 = 0, m1 = 0, f0 = 0, f1 = 0;
-    if constexpr (kPlainCore >= 0) {
-        if (c.fast) {
-            if (!c.resample) {
-                allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 0, true>, f0);
-                hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 0, true>), grid, block, lds, st, s, c, p);
-            } else {
-                allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 1, true>, f1);
-                hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 1, true>), grid, block, lds, st, s, c, p);
-            }
-            return true;
-        }
-    }
-    if (!c.resample) {
-        allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 0, false>, m0);
-        hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 0, false>), grid, block, lds, st, s, c, p);
-    } else {
-        allow_big_lds_dev(pv_pool_synth_chain_kernel<NC, kPlainCore, 1, false>, m1);
-        hipLaunchKernelGGL((pv_pool_synth_chain_kernel<NC, kPlainCore, 1, false>), grid, block, lds, st, s, c, p);
-    }
-    return true;
+// The slot-table sets clamp the launch to the kernel's bounds (no launch below one wave).
+static bool slot_chain_fit_waves(ChainArgs &c, int max_threads) {
+    if (64 * c.waves > max_threads) c.waves = max_threads / 64;
+    return c.waves >= 1;
 }
-
-// the same choice of specialisation as launch_synth_chain
+struct PoolChainSet { // grid (rows, slots); trailing argument p
+    const SynthArgs &s;
+    const PoolLaunch &p;
+    hipStream_t st;
+    static constexpr int max_threads(int NC, int kPlainCore, bool kFast) { return pool_chain_max_threads(NC, kPlainCore, kFast); }
+    static bool fit_waves(ChainArgs &c, int max_threads) { return slot_chain_fit_waves(c, max_threads); }
+    template <int NC, int kPlainCore, int kRes, bool kFast> void launch(const ChainArgs &c, dim3 block, size_t lds) const {
+        launch_big_lds<pv_pool_synth_chain_kernel<NC, kPlainCore, kRes, kFast>>(dim3(c.rows, p.nslots), block, lds, st, s, c, p);
+    }
+};
 bool launch_pool_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, hipStream_t st, bool launch) {
-    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
-    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                           !synth_generic_only() && s.coremode == 1;
-    if (s.tb.nc == 256) {
-        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<256, 1>(s, c, p, st, launch);
-        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<256, 0>(s, c, p, st, launch);
-        if (plain) return launch_pool_synth_chain_res<256, 2>(s, c, p, st, launch);
-        return launch_pool_synth_chain_res<256, -1>(s, c, p, st, launch);
-    }
-    if (s.tb.nc == 512) {
-        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<512, 1>(s, c, p, st, launch);
-        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<512, 0>(s, c, p, st, launch);
-        if (plain) return launch_pool_synth_chain_res<512, 2>(s, c, p, st, launch);
-        return launch_pool_synth_chain_res<512, -1>(s, c, p, st, launch);
-    }
-    if (s.tb.nc == 1024) {
-        if (fc_locked) return launch_pool_synth_chain_res<1024, 3>(s, c, p, st, launch);
-        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<1024, 1>(s, c, p, st, launch);
-        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<1024, 0>(s, c, p, st, launch);
-        if (plain) return launch_pool_synth_chain_res<1024, 2>(s, c, p, st, launch);
-        return launch_pool_synth_chain_res<1024, -1>(s, c, p, st, launch);
-    }
-    if (s.tb.nc == 2048) {
-        if (plain && s.coremode == 1) return launch_pool_synth_chain_res<2048, 1>(s, c, p, st, launch);
-        if (plain && s.coremode == 0) return launch_pool_synth_chain_res<2048, 0>(s, c, p, st, launch);
-        if (plain) return launch_pool_synth_chain_res<2048, 2>(s, c, p, st, launch);
-        return launch_pool_synth_chain_res<2048, -1>(s, c, p, st, launch);
-    }
-    return false;
+    return launch_chain(PoolChainSet{s, p, st}, s, s.tb.nc, c, launch);
 }
 
 // resampling: grid (tiles, row groups, slots)
@@ -4368,29 +4315,38 @@ template <int kRes> __global__ __launch_bounds__(kTileOut) void pv_pool_resample
     pool_resample_fast_role<kRes, kPoolResFastRows>(v, blockIdx.x, blockIdx.y, smem_raw);
 }
 
-bool launch_pool_resample(const ResArgs &a, const PoolLaunch &p, hipStream_t st, bool launch) {
-    const int NR = a.fast ? kPoolResFastRows : kResRows;
+// The slot-table resampler launch of all three sets: NR rows per workgroup, grid (tiles, row groups, slots); the
+// free-form (kFast) or the reference-order kernel, interpolated or direct table.  `Set` names the set's kernels
+// (set.fast<kRes, NR> / set.exact<kRes>) and appends its trailing arguments.  launch == false: the LDS check only.
+template <class Set, bool kFast, int NR>
+static bool launch_slot_resample(const Set &set, const ResArgs &a, const PoolLaunch &p, hipStream_t st, bool launch) {
     const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
-    if (lds > 160 * 1024 - 512) return false;
+    if (lds > kMaxDynLds) return false;
     if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
     const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
-    static unsigned long long m1 = 0, m2 = 0, f1 = 0, f2 = 0;
-    if (a.fast) {
-        if (a.interp) {
-            allow_big_lds_dev(pv_pool_resample_fast_kernel<2>, f2);
-            hipLaunchKernelGGL(pv_pool_resample_fast_kernel<2>, grid, dim3(kTileOut), lds, st, a, p);
-        } else {
-            allow_big_lds_dev(pv_pool_resample_fast_kernel<1>, f1);
-            hipLaunchKernelGGL(pv_pool_resample_fast_kernel<1>, grid, dim3(kTileOut), lds, st, a, p);
-        }
-    } else if (a.interp) {
-        allow_big_lds_dev(pv_pool_resample_kernel<2>, m2);
-        hipLaunchKernelGGL(pv_pool_resample_kernel<2>, grid, dim3(kTileOut), lds, st, a, p);
+    if constexpr (kFast) {
+        if (a.interp) set.template fast<2, NR>(grid, lds, st, a);
+        else set.template fast<1, NR>(grid, lds, st, a);
     } else {
-        allow_big_lds_dev(pv_pool_resample_kernel<1>, m1);
-        hipLaunchKernelGGL(pv_pool_resample_kernel<1>, grid, dim3(kTileOut), lds, st, a, p);
+        if (a.interp) set.template exact<2>(grid, lds, st, a);
+        else set.template exact<1>(grid, lds, st, a);
     }
     return true;
+}
+
+struct PoolResampleSet { // trailing argument p
+    const PoolLaunch &p;
+    template <int kRes, int NR> void fast(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {
+        static_assert(NR == kPoolResFastRows, "the kernel's row count");
+        launch_big_lds<pv_pool_resample_fast_kernel<kRes>>(grid, dim3(kTileOut), lds, st, a, p);
+    }
+    template <int kRes> void exact(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {
+        launch_big_lds<pv_pool_resample_kernel<kRes>>(grid, dim3(kTileOut), lds, st, a, p);
+    }
+};
+bool launch_pool_resample(const ResArgs &a, const PoolLaunch &p, hipStream_t st, bool launch) {
+    return a.fast ? launch_slot_resample<PoolResampleSet, true, kPoolResFastRows>({p}, a, p, st, launch)
+                  : launch_slot_resample<PoolResampleSet, false, kResRows>({p}, a, p, st, launch);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -4422,32 +4378,18 @@ __global__ __launch_bounds__(128) void pv_pmix_analyze_split_kernel(const Analyz
     analyze_split_role<WF2048S, WF2048S::LDS_CF * sizeof(cf)>(v, row, tl, reinterpret_cast<cf *>(smem_raw));
 }
 
-bool launch_pmix_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
-    const dim3 grid(a.rows * p.max_tn, p.nslots);
-    const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
-    switch (a.tb.nc) {
-    case 256:
-        hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<256>, grid, dim3(64), WF<256>::LDS_CF * sizeof(cf) + atab, st, a, p, q);
-        return true;
-    case 512:
-        hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<512>, grid, dim3(64), WF<512>::LDS_CF * sizeof(cf) + atab, st, a, p, q);
-        return true;
-    case 1024:
-        hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<1024>, grid, dim3(64), WF<1024>::LDS_CF * sizeof(cf) + atab, st, a, p, q);
-        return true;
-    case 2048:
-        if (a.split) {
-            hipLaunchKernelGGL(pv_pmix_analyze_split_kernel, grid, dim3(WF2048S::LANES),
-                               WF2048S::LDS_CF * sizeof(cf) + atab + 64, st, a, p, q);
-        } else {
-            static unsigned long long big = 0;
-            allow_big_lds_dev(pv_pmix_analyze_wave_kernel<2048>, big);
-            hipLaunchKernelGGL(pv_pmix_analyze_wave_kernel<2048>, grid, dim3(64), WF<2048>::LDS_CF * sizeof(cf) + atab,
-                               st, a, p, q);
-        }
-        return true;
-    default: return false;
+struct PmixAnalyzeSet { // trailing arguments p, q
+    const PoolLaunch &p;
+    const PoolParams *q;
+    template <int NC, bool kBigLds> void wave(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
+        launch_maybe_big_lds<pv_pmix_analyze_wave_kernel<NC>, kBigLds>(grid, dim3(64), lds, st, a, p, q);
     }
+    void split(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
+        hipLaunchKernelGGL(pv_pmix_analyze_split_kernel, grid, dim3(WF2048S::LANES), lds, st, a, p, q);
+    }
+};
+bool launch_pmix_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
+    return launch_slot_analyze(PmixAnalyzeSet{p, q}, a, p, st);
 }
 
 // phase-locked mode: match + rotation chain, one workgroup per (channel, slot)
@@ -4489,9 +4431,7 @@ __global__ __launch_bounds__(1024) void pv_pmix_phase_kernel(const MatchArgs m, 
 
 bool launch_pmix_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
     if (!pool_phase_supported(a.hs, a.PKP)) return false;
-    static unsigned long long big = 0;
-    allow_big_lds_dev(pv_pmix_phase_kernel<kPoolSeqDepth>, big);
-    hipLaunchKernelGGL(pv_pmix_phase_kernel<kPoolSeqDepth>, dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
+    launch_big_lds<pv_pmix_phase_kernel<kPoolSeqDepth>>(dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
                        pool_phase_lds(a.hs, a.PKP), st, m, a, p, q);
     return true;
 }
@@ -4561,73 +4501,21 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     pool_synth_chain_role<NC, kPlainCore, kRes, kFast>(sv, cv, blockIdx.x, smem_raw);
 }
 
-template <int NC, int kPlainCore>
-static bool launch_pmix_synth_chain_res(const SynthArgs &s, const ChainArgs &c_in, const PoolLaunch &p,
-                                        const PoolParams *q, hipStream_t st, bool launch) {
-    const bool use_fast = kPlainCore >= 0 && c_in.fast;
-    const int kMaxThreads = use_fast ? pool_chain_max_threads(NC, kPlainCore, true) : pool_chain_max_threads(NC, kPlainCore, false);
-    ChainArgs c = c_in;
-    if (64 * c.waves > kMaxThreads) c.waves = kMaxThreads / 64;
-    if (c.waves < 1) return false;
-    const size_t lds = chain_lds_bytes(c, NC);
-    if (!launch) return true;
-    const dim3 grid(c.rows, p.nslots), block(64 * c.waves);
-    static unsigned long long m0 = 0, m1 = 0, f0 = 0, f1 = 0;
-    if constexpr (kPlainCore >= 0) {
-        if (c.fast) {
-            if (!c.resample) {
-                allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, true>, f0);
-                hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, true>), grid, block, lds, st, s, c, p, q);
-            } else {
-                allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, true>, f1);
-                hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, true>), grid, block, lds, st, s, c, p, q);
-            }
-            return true;
-        }
+struct PmixChainSet { // grid (rows, slots); trailing arguments p, q
+    const SynthArgs &s;
+    const PoolLaunch &p;
+    const PoolParams *q;
+    hipStream_t st;
+    static constexpr int max_threads(int NC, int kPlainCore, bool kFast) { return pool_chain_max_threads(NC, kPlainCore, kFast); }
+    static bool fit_waves(ChainArgs &c, int max_threads) { return slot_chain_fit_waves(c, max_threads); }
+    template <int NC, int kPlainCore, int kRes, bool kFast> void launch(const ChainArgs &c, dim3 block, size_t lds) const {
+        launch_big_lds<pv_pmix_synth_chain_kernel<NC, kPlainCore, kRes, kFast>>(dim3(c.rows, p.nslots), block, lds, st, s, c, p, q);
     }
-    if (!c.resample) {
-        allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, false>, m0);
-        hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 0, false>), grid, block, lds, st, s, c, p, q);
-    } else {
-        allow_big_lds_dev(pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, false>, m1);
-        hipLaunchKernelGGL((pv_pmix_synth_chain_kernel<NC, kPlainCore, 1, false>), grid, block, lds, st, s, c, p, q);
-    }
-    return true;
-}
-
-// the same choice of specialisation as launch_pool_synth_chain (s.do_freq_comp: the launch's variant)
+};
+// (s.do_freq_comp: the launch's variant)
 bool launch_pmix_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q,
                              hipStream_t st, bool launch) {
-    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
-    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                           !synth_generic_only() && s.coremode == 1;
-    if (s.tb.nc == 256) {
-        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<256, 1>(s, c, p, q, st, launch);
-        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<256, 0>(s, c, p, q, st, launch);
-        if (plain) return launch_pmix_synth_chain_res<256, 2>(s, c, p, q, st, launch);
-        return launch_pmix_synth_chain_res<256, -1>(s, c, p, q, st, launch);
-    }
-    if (s.tb.nc == 512) {
-        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<512, 1>(s, c, p, q, st, launch);
-        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<512, 0>(s, c, p, q, st, launch);
-        if (plain) return launch_pmix_synth_chain_res<512, 2>(s, c, p, q, st, launch);
-        return launch_pmix_synth_chain_res<512, -1>(s, c, p, q, st, launch);
-    }
-    if (s.tb.nc == 1024) {
-        if (fc_locked) return launch_pmix_synth_chain_res<1024, 3>(s, c, p, q, st, launch);
-        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<1024, 1>(s, c, p, q, st, launch);
-        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<1024, 0>(s, c, p, q, st, launch);
-        if (plain) return launch_pmix_synth_chain_res<1024, 2>(s, c, p, q, st, launch);
-        return launch_pmix_synth_chain_res<1024, -1>(s, c, p, q, st, launch);
-    }
-    if (s.tb.nc == 2048) {
-        if (plain && s.coremode == 1) return launch_pmix_synth_chain_res<2048, 1>(s, c, p, q, st, launch);
-        if (plain && s.coremode == 0) return launch_pmix_synth_chain_res<2048, 0>(s, c, p, q, st, launch);
-        if (plain) return launch_pmix_synth_chain_res<2048, 2>(s, c, p, q, st, launch);
-        return launch_pmix_synth_chain_res<2048, -1>(s, c, p, q, st, launch);
-    }
-    return false;
+    return launch_chain(PmixChainSet{s, p, q, st}, s, s.tb.nc, c, launch);
 }
 
 // resampling: grid (tiles, row groups, slots); the launch's slots share interp and fast
@@ -4662,29 +4550,20 @@ __global__ __launch_bounds__(kTileOut) void pv_pmix_resample_fast_kernel(const R
     pool_resample_fast_role<kRes, kPoolResFastRows>(v, blockIdx.x, blockIdx.y, smem_raw);
 }
 
-bool launch_pmix_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch) {
-    const int NR = a.fast ? kPoolResFastRows : kResRows;
-    const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
-    if (lds > 160 * 1024 - 512) return false;
-    if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
-    const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
-    static unsigned long long m1 = 0, m2 = 0, f1 = 0, f2 = 0;
-    if (a.fast) {
-        if (a.interp) {
-            allow_big_lds_dev(pv_pmix_resample_fast_kernel<2>, f2);
-            hipLaunchKernelGGL(pv_pmix_resample_fast_kernel<2>, grid, dim3(kTileOut), lds, st, a, p, q);
-        } else {
-            allow_big_lds_dev(pv_pmix_resample_fast_kernel<1>, f1);
-            hipLaunchKernelGGL(pv_pmix_resample_fast_kernel<1>, grid, dim3(kTileOut), lds, st, a, p, q);
-        }
-    } else if (a.interp) {
-        allow_big_lds_dev(pv_pmix_resample_kernel<2>, m2);
-        hipLaunchKernelGGL(pv_pmix_resample_kernel<2>, grid, dim3(kTileOut), lds, st, a, p, q);
-    } else {
-        allow_big_lds_dev(pv_pmix_resample_kernel<1>, m1);
-        hipLaunchKernelGGL(pv_pmix_resample_kernel<1>, grid, dim3(kTileOut), lds, st, a, p, q);
+struct PmixResampleSet { // trailing arguments p, q
+    const PoolLaunch &p;
+    const PoolParams *q;
+    template <int kRes, int NR> void fast(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {
+        static_assert(NR == kPoolResFastRows, "the kernel's row count");
+        launch_big_lds<pv_pmix_resample_fast_kernel<kRes>>(grid, dim3(kTileOut), lds, st, a, p, q);
     }
-    return true;
+    template <int kRes> void exact(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {
+        launch_big_lds<pv_pmix_resample_kernel<kRes>>(grid, dim3(kTileOut), lds, st, a, p, q);
+    }
+};
+bool launch_pmix_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch) {
+    return a.fast ? launch_slot_resample<PmixResampleSet, true, kPoolResFastRows>({p, q}, a, p, st, launch)
+                  : launch_slot_resample<PmixResampleSet, false, kResRows>({p, q}, a, p, st, launch);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -4735,32 +4614,19 @@ __global__ __launch_bounds__(128) void pv_mb_analyze_split_kernel(const AnalyzeA
                                                               reinterpret_cast<cf *>(smem_raw));
 }
 
-bool launch_mb_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, const MbSlot *m, hipStream_t st) {
-    const dim3 grid(a.rows * p.max_tn, p.nslots);
-    const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
-    switch (a.tb.nc) {
-    case 256:
-        hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<256>, grid, dim3(64), WF<256>::LDS_CF * sizeof(cf) + atab, st, a, p, q, m);
-        return true;
-    case 512:
-        hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<512>, grid, dim3(64), WF<512>::LDS_CF * sizeof(cf) + atab, st, a, p, q, m);
-        return true;
-    case 1024:
-        hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<1024>, grid, dim3(64), WF<1024>::LDS_CF * sizeof(cf) + atab, st, a, p, q, m);
-        return true;
-    case 2048:
-        if (a.split) {
-            hipLaunchKernelGGL(pv_mb_analyze_split_kernel, grid, dim3(WF2048S::LANES),
-                               WF2048S::LDS_CF * sizeof(cf) + atab + 64, st, a, p, q, m);
-        } else {
-            static unsigned long long big = 0;
-            allow_big_lds_dev(pv_mb_analyze_wave_kernel<2048>, big);
-            hipLaunchKernelGGL(pv_mb_analyze_wave_kernel<2048>, grid, dim3(64), WF<2048>::LDS_CF * sizeof(cf) + atab,
-                               st, a, p, q, m);
-        }
-        return true;
-    default: return false;
+struct MbAnalyzeSet { // trailing arguments p, q, m
+    const PoolLaunch &p;
+    const PoolParams *q;
+    const MbSlot *m;
+    template <int NC, bool kBigLds> void wave(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
+        launch_maybe_big_lds<pv_mb_analyze_wave_kernel<NC>, kBigLds>(grid, dim3(64), lds, st, a, p, q, m);
     }
+    void split(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
+        hipLaunchKernelGGL(pv_mb_analyze_split_kernel, grid, dim3(WF2048S::LANES), lds, st, a, p, q, m);
+    }
+};
+bool launch_mb_analyze(const AnalyzeArgs &a, const PoolLaunch &p, const PoolParams *q, const MbSlot *m, hipStream_t st) {
+    return launch_slot_analyze(MbAnalyzeSet{p, q, m}, a, p, st);
 }
 
 // phase-locked mode, parallel part: four waves, one step of the slot each; grid (steps / 4, C, slots)
@@ -4819,10 +4685,8 @@ static size_t mb_seq_lds(const SeqArgs &a) {
     return ((seq_lds_bytes(a) + 15) & ~(size_t)15) + (size_t)kMbSeqDepth * seq_threads(a.PKP) * sizeof(PeakRec);
 }
 bool launch_mb_seq(const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
-    if (a.PKP > seq_threads(a.PKP) || mb_seq_lds(a) > 160 * 1024 - 512) return false;
-    static unsigned long long big = 0;
-    allow_big_lds_dev(pv_mb_seq_kernel<kMbSeqDepth>, big);
-    hipLaunchKernelGGL(pv_mb_seq_kernel<kMbSeqDepth>, dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)), mb_seq_lds(a), st, a, p, q);
+    if (a.PKP > seq_threads(a.PKP) || mb_seq_lds(a) > kMaxDynLds) return false;
+    launch_big_lds<pv_mb_seq_kernel<kMbSeqDepth>>(dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)), mb_seq_lds(a), st, a, p, q);
     return true;
 }
 
@@ -4872,66 +4736,25 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     pool_synth_chain_role<NC, kPlainCore, kRes, kFast>(sv, cv, blockIdx.x, smem_raw, run, run == runs - 1);
 }
 
-template <int NC, int kPlainCore>
-static bool launch_mb_synth_chain_res(const SynthArgs &s, const ChainArgs &c_in, const PoolLaunch &p, const PoolParams *q,
-                                      const MbSlot *m, int max_runs, hipStream_t st, bool launch) {
-    const bool use_fast = kPlainCore >= 0 && c_in.fast;
-    const int kMaxThreads = use_fast ? pool_chain_max_threads(NC, kPlainCore, true) : pool_chain_max_threads(NC, kPlainCore, false);
-    ChainArgs c = c_in;
-    if (64 * c.waves > kMaxThreads) c.waves = kMaxThreads / 64;
-    if (c.waves < 1) return false;
-    const size_t lds = chain_lds_bytes(c, NC);
-    if (!launch) return true;
-    const dim3 grid(c.rows, max_runs, p.nslots), block(64 * c.waves);
-    static unsigned long long m0 = 0, m1 = 0, f0 = 0, f1 = 0;
-    if constexpr (kPlainCore >= 0) {
-        if (c.fast) {
-            if (!c.resample) {
-                allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 0, true>, f0);
-                hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 0, true>), grid, block, lds, st, s, c, p, q, m);
-            } else {
-                allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 1, true>, f1);
-                hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 1, true>), grid, block, lds, st, s, c, p, q, m);
-            }
-            return true;
-        }
+struct MbChainSet { // grid (rows, max_runs, slots); trailing arguments p, q, m
+    const SynthArgs &s;
+    const PoolLaunch &p;
+    const PoolParams *q;
+    const MbSlot *m;
+    int max_runs;
+    hipStream_t st;
+    static constexpr int max_threads(int NC, int kPlainCore, bool kFast) { return pool_chain_max_threads(NC, kPlainCore, kFast); }
+    static bool fit_waves(ChainArgs &c, int max_threads) { return slot_chain_fit_waves(c, max_threads); }
+    template <int NC, int kPlainCore, int kRes, bool kFast> void launch(const ChainArgs &c, dim3 block, size_t lds) const {
+        launch_big_lds<pv_mb_synth_chain_kernel<NC, kPlainCore, kRes, kFast>>(dim3(c.rows, max_runs, p.nslots), block, lds, st, s, c,
+                                                                              p, q, m);
     }
-    if (!c.resample) {
-        allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 0, false>, m0);
-        hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 0, false>), grid, block, lds, st, s, c, p, q, m);
-    } else {
-        allow_big_lds_dev(pv_mb_synth_chain_kernel<NC, kPlainCore, 1, false>, m1);
-        hipLaunchKernelGGL((pv_mb_synth_chain_kernel<NC, kPlainCore, 1, false>), grid, block, lds, st, s, c, p, q, m);
-    }
-    return true;
-}
-
-template <int NC>
-static bool launch_mb_synth_chain_nc(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q,
-                                     const MbSlot *m, int max_runs, hipStream_t st, bool launch, bool plain, bool fc_locked) {
-    if constexpr (NC == 1024)
-        if (fc_locked) return launch_mb_synth_chain_res<NC, 3>(s, c, p, q, m, max_runs, st, launch);
-    if (plain && s.coremode == 1) return launch_mb_synth_chain_res<NC, 1>(s, c, p, q, m, max_runs, st, launch);
-    if (plain && s.coremode == 0) return launch_mb_synth_chain_res<NC, 0>(s, c, p, q, m, max_runs, st, launch);
-    if (plain) return launch_mb_synth_chain_res<NC, 2>(s, c, p, q, m, max_runs, st, launch);
-    return launch_mb_synth_chain_res<NC, -1>(s, c, p, q, m, max_runs, st, launch);
-}
-
-// the same choice of specialisation as launch_pmix_synth_chain (s.do_freq_comp: the launch's variant)
+};
+// (s.do_freq_comp: the launch's variant)
 bool launch_mb_synth_chain(const SynthArgs &s, const ChainArgs &c, const PoolLaunch &p, const PoolParams *q, const MbSlot *m,
                            int max_runs, hipStream_t st, bool launch) {
-    const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                       !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
-    const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
-                           !synth_generic_only() && s.coremode == 1;
-    if (max_runs < 1 || max_runs > 65535) return false;
-    switch (s.tb.nc) {
-    case 256: return launch_mb_synth_chain_nc<256>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
-    case 512: return launch_mb_synth_chain_nc<512>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
-    case 1024: return launch_mb_synth_chain_nc<1024>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
-    case 2048: return launch_mb_synth_chain_nc<2048>(s, c, p, q, m, max_runs, st, launch, plain, fc_locked);
-    default: return false;
-    }
+    if (max_runs < 1 || max_runs > 65535) return false; // (the grid's y)
+    return launch_chain(MbChainSet{s, p, q, m, max_runs, st}, s, s.tb.nc, c, launch);
 }
 
 // resampling: grid (tiles, row groups, slots).  The pool's free-form kernel computes eight rows per workgroup, the
@@ -4946,28 +4769,18 @@ __global__ __launch_bounds__(kTileOut) void pv_mb_resample_fast_kernel(const Res
     if (!pmix_res_view(a, p, q, v)) return;
     pool_resample_fast_role<kRes, NR>(v, blockIdx.x, blockIdx.y, smem_raw);
 }
-template <int NR>
-static void launch_mb_resample_fast_rows(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
-    const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
-    const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
-    static unsigned long long f1 = 0, f2 = 0;
-    if (a.interp) {
-        allow_big_lds_dev(pv_mb_resample_fast_kernel<2, NR>, f2);
-        hipLaunchKernelGGL((pv_mb_resample_fast_kernel<2, NR>), grid, dim3(kTileOut), lds, st, a, p, q);
-    } else {
-        allow_big_lds_dev(pv_mb_resample_fast_kernel<1, NR>, f1);
-        hipLaunchKernelGGL((pv_mb_resample_fast_kernel<1, NR>), grid, dim3(kTileOut), lds, st, a, p, q);
+struct MbResampleSet { // trailing arguments p, q; the free-form kernel only
+    const PoolLaunch &p;
+    const PoolParams *q;
+    template <int kRes, int NR> void fast(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {
+        launch_big_lds<pv_mb_resample_fast_kernel<kRes, NR>>(grid, dim3(kTileOut), lds, st, a, p, q);
     }
-}
+};
 bool launch_mb_resample(const ResArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st, bool launch) {
     if (!a.fast) return launch_pmix_resample(a, p, q, st, launch); // the reference's order: four rows per workgroup
-    const int NR = a.rows <= 2 ? 2 : a.rows <= 4 ? 4 : kPoolResFastRows;
-    if ((size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR > 160 * 1024 - 512) return false;
-    if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
-    if (NR == 2) launch_mb_resample_fast_rows<2>(a, p, q, st);
-    else if (NR == 4) launch_mb_resample_fast_rows<4>(a, p, q, st);
-    else launch_mb_resample_fast_rows<kPoolResFastRows>(a, p, q, st);
-    return true;
+    if (a.rows <= 2) return launch_slot_resample<MbResampleSet, true, 2>({p, q}, a, p, st, launch);
+    if (a.rows <= 4) return launch_slot_resample<MbResampleSet, true, 4>({p, q}, a, p, st, launch);
+    return launch_slot_resample<MbResampleSet, true, kPoolResFastRows>({p, q}, a, p, st, launch);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
