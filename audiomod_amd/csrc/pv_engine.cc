@@ -107,6 +107,20 @@ template <typename T> struct DevBuf {
 #endif
         return PV_OK;
     }
+    // The same with the fill ordered on `st`, for a buffer that only `st`'s work uses: alloc()'s fill is on the default
+    // stream, which nothing orders against a non-blocking stream, so work enqueued there right away could be overtaken
+    // by it.  (Growing frees the old buffer, which waits for the device.)
+    int alloc_on(size_t count, hipStream_t st) {
+        release();
+        n = count;
+        HIPC(hipMalloc((void **)&p, (count ? count : 1) * sizeof(T)));
+#ifdef PV_POISON
+        HIPC(hipMemsetAsync(p, 0xFF, (count ? count : 1) * sizeof(T), st));
+#else
+        HIPC(hipMemsetAsync(p, 0, (count ? count : 1) * sizeof(T), st));
+#endif
+        return PV_OK;
+    }
     void swap(DevBuf &o) {
         std::swap(p, o.p);
         std::swap(n, o.n);
@@ -1331,6 +1345,8 @@ struct pv_engine {
 // images [i][2][C][AR].  Every slot keeps its own planner, overlap-add plan and accumulator half, so that it computes
 // exactly what a pv_engine fed the same calls computes.
 // ------------------------------------------------------------------------------------------
+constexpr int kPoolDescRing = 4; // descriptor blocks of pv_pool_feed_device that may be in flight at once
+
 struct pv_pool {
     Core core;
     int poisoned = 0;
@@ -1369,13 +1385,26 @@ struct pv_pool {
     std::vector<Tab> tabs;
     DevBuf<float4> d_tabs; // [capacity][tab_stride]
     size_t tab_stride = 0; // float4 per entry
-    int last_launches = 0; // kernels launched by the last pv_pool_feed
+    int last_launches = 0; // kernels launched by the last pv_pool_feed / pv_pool_feed_device
     DevBuf<float> d_in, d_stage; // device input rings [capacity * C][ring]; a call's packed new samples
     PinBuf<float> h_stage;
     const float *stage_src = nullptr; // what the ingest kernel reads: d_stage (or h_stage mapped, PV_POOL_MAPPED_INGEST)
     double last_host_us = 0, last_wait_us = 0; // the last pv_pool_feed: host work up to the wait, and the wait
-    DevBuf<char> d_desc;
-    PinBuf<char> h_desc;
+    // One pinned and one device descriptor block.  pv_pool_feed owns `sync_desc` (the previous call has finished when
+    // the next one writes it); pv_pool_feed_device returns with its launches in flight and takes the blocks of
+    // `ring_desc` in turn: `done` is recorded behind the launches that read a block, and a call that finds its block
+    // busy waits for that event -- the call kPoolDescRing calls back, a bounded wait.  `entry` is the event the call
+    // records on the caller's stream for the pool's stream to wait for.
+    struct DescBlock {
+        DevBuf<char> d;
+        PinBuf<char> h;
+        hipEvent_t entry = nullptr, done = nullptr;
+        bool busy = false;
+    };
+    DescBlock sync_desc, ring_desc[kPoolDescRing];
+    int ring_next = 0;
+    bool ring_ready = false;
+    DevBuf<float> d_arena; // int16 wire: the kernels' float output [slot][C][cnt], converted by the egress kernel
     PinBuf<float> h_out; // output arena, mapped into the device's address space (out_dev)
     float *out_dev = nullptr;
     PinBuf<uint32_t> h_flag;
@@ -1383,7 +1412,14 @@ struct pv_pool {
     uint32_t flag_seq = 0;
     bool wait_value = false; // the device supports stream memory operations: spin on a flag instead of synchronising
     ~pv_pool() {
-        if (stream) (void)hipStreamDestroy(stream);
+        if (stream) {
+            (void)hipStreamSynchronize(stream); // (device feeds may be in flight)
+            (void)hipStreamDestroy(stream);
+        }
+        for (DescBlock &b : ring_desc) {
+            if (b.entry) (void)hipEventDestroy(b.entry);
+            if (b.done) (void)hipEventDestroy(b.done);
+        }
     }
 };
 
@@ -2295,6 +2331,31 @@ static bool pool_slot_ok(const pv_pool *p, int32_t slot) {
 
 static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true);
 
+// Core::init and pool_create allocate with DevBuf::alloc, whose zero fill is on the default stream; nothing orders that
+// stream against the pool's own non-blocking one.  pv_pool_create therefore ends with a wait for the fills, so that no
+// fill can land on what a slot's first launches have written.  (Buffers that grow later are filled on the pool's
+// stream: DevBuf::alloc_on.)
+static int pool_settle() {
+    HIPC(hipStreamSynchronize(nullptr));
+    return PV_OK;
+}
+
+// Waits for every device feed in flight (the events of their descriptor blocks).  An error of their launches that shows
+// only now is reported here, to the call that drains: it poisons the pool.
+static int pool_drain(pv_pool *p) {
+    for (pv_pool::DescBlock &b : p->ring_desc) {
+        if (!b.busy) continue;
+        b.busy = false;
+        const hipError_t e = hipEventSynchronize(b.done);
+        if (e != hipSuccess) {
+            p->poisoned = hip_fail(e, "stream pool device feed", __LINE__);
+            p->poison_reason = g_last_error;
+            return p->poisoned;
+        }
+    }
+    return PV_OK;
+}
+
 // the chain kernel's largest overlap-add advance for one set of derived constants (as Core::init computes it)
 static int pool_max_adv(const Derived &d) {
     const bool fixed_shift = phase_mode(d) < 0;
@@ -2491,6 +2552,7 @@ static int pool_create(const pv_config *cfg, const pv_pool_range *range, int32_t
         p->range = pv_pool_range{cfg->pitch_semitones, cfg->pitch_semitones, cfg->time_ratio, cfg->time_ratio};
     }
     p->slots.resize((size_t)capacity);
+    if ((st = pool_settle()) != PV_OK) return st;
     *out = p.release();
     return PV_OK;
 }
@@ -2590,6 +2652,8 @@ static int pool_open_at(pv_pool *p, float time_ratio, float semis, int32_t *slot
                             t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
                         }
                 HIPC(hipSetDevice(c.device));
+                // (a free entry may still be read by the in-flight device feeds of the slot that released it)
+                if (const int ds = pool_drain(p)) return ds;
                 HIPC(hipMemcpy(p->d_tabs.p + (size_t)tab * p->tab_stride, img.data(), img.size() * sizeof(float4),
                                hipMemcpyHostToDevice));
                 p->tabs[(size_t)tab].num = d.res_num;
@@ -2829,10 +2893,25 @@ static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const P
     return PV_OK;
 }
 
-int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *const *in, const int32_t *n) {
+// What the two entry points of a feed differ in (pv_pool_feed: host pointers in, the slots' host FIFOs out, the pool's
+// own descriptor block, a wait; pv_pool_feed_device: the caller's device buffers, a block of the ring, events).
+// Planning, descriptor building, variant grouping and launching are pool_feed's, for both.
+struct PoolCall {
+    const float *const *in = nullptr; // pv_pool_feed: in[i * C + c], n[i] host floats
+    bool device = false;              // pv_pool_feed_device: ...
+    const void *d_in = nullptr;       // [count][C][in_pitch] of `wire`
+    void *d_out = nullptr;            // [count][C][out_pitch] of `wire`
+    int64_t in_pitch = 0, out_pitch = 0;
+    int wire = PV_WIRE_F32;
+    hipStream_t user = nullptr;
+    int32_t *out_frames = nullptr; // [count]: what the call delivers per slot
+};
+
+static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int32_t *n, const PoolCall &io) {
+    const float *const *in = io.in;
     g_last_error.clear();
     plan_reason_clear();
-    if (!p || count < 0 || (count > 0 && (!slots || !n))) return PV_ERR_INVALID_ARG;
+    if (!p || count < 0 || (count > 0 && (!slots || !n || (io.device && !io.out_frames)))) return PV_ERR_INVALID_ARG;
     if (p->poisoned) {
         g_last_error = "pool unusable after an earlier failure: " + p->poison_reason;
         return p->poisoned;
@@ -2844,7 +2923,13 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
         for (int32_t i = 0; i < count; ++i) {
             const int32_t s = slots[i];
             const char *bad = !pool_slot_ok(p, s) ? "is not open" : seen[(size_t)s] ? "is listed twice" : n[i] < 0 ? "has a negative size" : nullptr;
-            if (!bad && n[i] > 0) {
+            if (!bad && io.device) {
+                const pv_pool::Slot &sl = p->slots[(size_t)s];
+                if (!sl.outq.empty() && sl.outq[0].size() > sl.outq_head)
+                    bad = "still holds output of pv_pool_feed: retrieve it first";
+                else if (n[i] > io.in_pitch) bad = "has more frames than the input pitch";
+                else if (n[i] > 0 && !io.d_in) bad = "has no input";
+            } else if (!bad && n[i] > 0) {
                 if (!in) bad = "has no input";
                 else
                     for (int ch = 0; ch < C && !bad; ++ch)
@@ -2864,16 +2949,36 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
     std::vector<std::vector<SliceRec>> fresh((size_t)count);
     {
         std::vector<Planner::State> before((size_t)count);
+        auto undo = [&](int32_t upto) {
+            for (int32_t j = 0; j <= upto; ++j) p->slots[(size_t)slots[j]].planner->restore(before[(size_t)j]);
+        };
         for (int32_t i = 0; i < count; ++i) {
             Planner &pl = *p->slots[(size_t)slots[i]].planner;
             before[(size_t)i] = pl.save();
             const int st = pl.feed(n[i], fresh[(size_t)i]);
             if (st != PV_OK) {
-                for (int32_t j = 0; j <= i; ++j) p->slots[(size_t)slots[j]].planner->restore(before[(size_t)j]);
+                undo(i);
                 g_last_error = "stream pool: slot " + std::to_string(slots[i]) + ": " +
                                (g_last_error.empty() ? std::string(plan_reason()) : g_last_error);
                 return st;
             }
+        }
+        // the device feed delivers everything the call makes available (nothing was pending before it: checked above);
+        // the retrieve is booked now, the samples follow in stream order
+        // (every count is checked before the first is written: a refusal leaves the caller's array as it was)
+        for (int32_t i = 0; i < count && io.device; ++i) {
+            const int32_t got = p->slots[(size_t)slots[i]].planner->available();
+            if (got > io.out_pitch || (got > 0 && !io.d_out)) {
+                undo(count - 1);
+                g_last_error = "stream pool: slot " + std::to_string(slots[i]) +
+                               (got > io.out_pitch ? " returns " + std::to_string(got) + " frames, more than the output pitch"
+                                                   : std::string(" has no output buffer"));
+                return PV_ERR_INVALID_ARG;
+            }
+        }
+        for (int32_t i = 0; i < count && io.device; ++i) {
+            Planner &pl = *p->slots[(size_t)slots[i]].planner;
+            io.out_frames[i] = pl.retrieve(pl.available());
         }
     }
     // from here on device state and host bookkeeping move together; a failure poisons the pool
@@ -2886,16 +2991,45 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
         const hipError_t e = hipSetDevice(c.device);
         if (e != hipSuccess) return fail(hip_fail(e, "hipSetDevice", __LINE__));
     }
-    // 2. the call's new samples, packed [slot][C][n] (one copy)
+    int st;
+    // The call's descriptor block.  pv_pool_feed: its own, after every device feed in flight has finished (their
+    // output and any late error of theirs come first).  pv_pool_feed_device: the ring's next, once the call that used
+    // it last has finished.
+    pv_pool::DescBlock *blk = &p->sync_desc;
+    if (!io.device) {
+        if ((st = pool_drain(p)) != PV_OK) return st;
+    } else {
+        if (!p->ring_ready) { // (everything a device feed allocates in the common case, at the first one)
+            for (pv_pool::DescBlock &b : p->ring_desc) {
+                if ((st = b.h.alloc(256 * 1024)) != PV_OK || (st = b.d.alloc_on(256 * 1024, p->stream)) != PV_OK) return fail(st);
+                hipError_t e = hipEventCreateWithFlags(&b.entry, hipEventDisableTiming);
+                if (e == hipSuccess) e = hipEventCreateWithFlags(&b.done, hipEventDisableTiming);
+                if (e != hipSuccess) return fail(hip_fail(e, "descriptor ring events", __LINE__));
+            }
+            p->ring_ready = true;
+        }
+        blk = &p->ring_desc[p->ring_next];
+        p->ring_next = (p->ring_next + 1) % kPoolDescRing;
+        if (blk->busy) {
+            blk->busy = false;
+            const hipError_t e = hipEventSynchronize(blk->done);
+            if (e != hipSuccess) return fail(hip_fail(e, "stream pool device feed", __LINE__));
+        }
+    }
+    // 2. where the call's new samples are read and its output is written.  pv_pool_feed: the samples packed
+    // [slot][C][n] into the staging buffer (one copy), the output packed [slot][C][cnt] in the mapped host arena.
+    // pv_pool_feed_device: the caller's buffers as they are (int16 output: packed in a device arena, converted after
+    // the launches).
+    const bool to_caller = io.device && io.wire == PV_WIRE_F32; // the kernels write the caller's rows themselves
     std::vector<int64_t> stage_off((size_t)count), out_base((size_t)count), out_cnt((size_t)count), k0((size_t)count);
     std::vector<int64_t> call_base((size_t)count);
     size_t stage_total = 0, out_total = 0;
     int groups = 0;
     for (int32_t i = 0; i < count; ++i) {
-        stage_off[(size_t)i] = (int64_t)stage_total;
+        stage_off[(size_t)i] = io.device ? (int64_t)i * C * io.in_pitch : (int64_t)stage_total;
         stage_total += (size_t)C * n[i];
         const std::vector<SliceRec> &f = fresh[(size_t)i];
-        out_base[(size_t)i] = (int64_t)out_total;
+        out_base[(size_t)i] = to_caller ? (int64_t)i * C * io.out_pitch : (int64_t)out_total;
         out_cnt[(size_t)i] = f.empty() ? 0 : f.back().K0 + f.back().cnt - f.front().K0;
         k0[(size_t)i] = f.empty() ? 0 : f.front().K0;
         out_total += (size_t)C * out_cnt[(size_t)i];
@@ -2903,33 +3037,50 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
         if (g > groups) groups = g;
         call_base[(size_t)i] = p->slots[(size_t)slots[i]].fed;
     }
-    int st;
-    if (stage_total > p->h_stage.n) {
-        size_t capn = p->h_stage.n ? p->h_stage.n : 1 << 16;
-        while (capn < stage_total) capn *= 2;
-        if ((st = p->h_stage.alloc(capn)) != PV_OK) return fail(st);
+    const void *ingest_src = io.d_in;
+    float *launch_out = static_cast<float *>(io.d_out);
+    if (io.device) {
+        if (!to_caller) {
+            if (out_total > p->d_arena.n) {
+                size_t capn = p->d_arena.n ? p->d_arena.n : 1 << 16;
+                while (capn < out_total) capn *= 2;
+                // (the calls in flight still use the old arena)
+                const hipError_t e = hipStreamSynchronize(p->stream);
+                if (e != hipSuccess) return fail(hip_fail(e, "stream pool device feed", __LINE__));
+                if ((st = p->d_arena.alloc_on(capn, p->stream)) != PV_OK) return fail(st);
+            }
+            launch_out = p->d_arena.p;
+        }
+    } else {
+        if (stage_total > p->h_stage.n) {
+            size_t capn = p->h_stage.n ? p->h_stage.n : 1 << 16;
+            while (capn < stage_total) capn *= 2;
+            if ((st = p->h_stage.alloc(capn)) != PV_OK) return fail(st);
 #ifdef PV_POOL_MAPPED_INGEST // (measurement build: the ingest kernel reads the page-locked staging over the bus)
-        void *sp = nullptr;
-        const hipError_t e = hipHostGetDevicePointer(&sp, p->h_stage.p, 0);
-        if (e != hipSuccess) return fail(hip_fail(e, "staging mapping", __LINE__));
-        p->stage_src = static_cast<float *>(sp);
+            void *sp = nullptr;
+            const hipError_t e = hipHostGetDevicePointer(&sp, p->h_stage.p, 0);
+            if (e != hipSuccess) return fail(hip_fail(e, "staging mapping", __LINE__));
+            p->stage_src = static_cast<float *>(sp);
 #else
-        if ((st = p->d_stage.alloc(capn)) != PV_OK) return fail(st);
-        p->stage_src = p->d_stage.p;
+            if ((st = p->d_stage.alloc_on(capn, p->stream)) != PV_OK) return fail(st);
+            p->stage_src = p->d_stage.p;
 #endif
-    }
-    for (int32_t i = 0; i < count; ++i)
-        for (int ch = 0; ch < C; ++ch)
-            if (n[i] > 0)
-                memcpy(p->h_stage.p + stage_off[(size_t)i] + (size_t)ch * n[i], in[(size_t)i * C + ch], (size_t)n[i] * sizeof(float));
-    if (out_total > p->h_out.n) {
-        size_t capn = p->h_out.n ? p->h_out.n : 1 << 16;
-        while (capn < out_total) capn *= 2;
-        if ((st = p->h_out.alloc(capn)) != PV_OK) return fail(st);
-        void *op = nullptr;
-        const hipError_t e = hipHostGetDevicePointer(&op, p->h_out.p, 0);
-        if (e != hipSuccess) return fail(hip_fail(e, "output arena mapping", __LINE__));
-        p->out_dev = static_cast<float *>(op);
+        }
+        for (int32_t i = 0; i < count; ++i)
+            for (int ch = 0; ch < C; ++ch)
+                if (n[i] > 0)
+                    memcpy(p->h_stage.p + stage_off[(size_t)i] + (size_t)ch * n[i], in[(size_t)i * C + ch], (size_t)n[i] * sizeof(float));
+        if (out_total > p->h_out.n) {
+            size_t capn = p->h_out.n ? p->h_out.n : 1 << 16;
+            while (capn < out_total) capn *= 2;
+            if ((st = p->h_out.alloc(capn)) != PV_OK) return fail(st);
+            void *op = nullptr;
+            const hipError_t e = hipHostGetDevicePointer(&op, p->h_out.p, 0);
+            if (e != hipSuccess) return fail(hip_fail(e, "output arena mapping", __LINE__));
+            p->out_dev = static_cast<float *>(op);
+        }
+        ingest_src = p->stage_src;
+        launch_out = p->out_dev;
     }
     // 3. descriptors of every group, one block: per group its PoolSlot table and ingest list, per slot its phase
     // increments, run list, run offsets, denominators and resampling tiles
@@ -2963,7 +3114,7 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
         if (upto <= sl.uploaded) return;
         PoolIngest e{};
         e.src_off = stage_off[(size_t)i] + (sl.uploaded - call_base[(size_t)i]);
-        e.src_pitch = n[i];
+        e.src_pitch = io.device ? io.in_pitch : n[i];
         e.pos = sl.uploaded;
         e.n = (int32_t)(upto - sl.uploaded);
         e.row0 = slots[i] * C;
@@ -3024,7 +3175,7 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
             ps.res_off = put(res_tiles.data(), res_tiles.size() * sizeof(ResTile));
             ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
             ps.out_off = out_base[(size_t)i] + (ka - k0[(size_t)i]);
-            ps.out_stride_row = out_cnt[(size_t)i];
+            ps.out_stride_row = to_caller ? io.out_pitch : out_cnt[(size_t)i];
             ps.k_base = ka;
             table.push_back(ps);
             if (Tn > g.max_tn) g.max_tn = Tn;
@@ -3090,45 +3241,87 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
         g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
     }
     for (int32_t i = 0; i < count; ++i) p->slots[(size_t)slots[i]].slices += (int64_t)fresh[(size_t)i].size();
-    if (blob.size() > p->h_desc.n) {
-        size_t capn = p->h_desc.n ? p->h_desc.n : 256 * 1024;
-        while (capn < blob.size()) capn *= 2;
-        if ((st = p->h_desc.alloc(capn)) != PV_OK || (st = p->d_desc.alloc(capn)) != PV_OK) return fail(st);
+    // int16 output: what the egress kernel converts, per entry
+    int64_t egress_off = 0;
+    int negress = 0, max_egress = 0;
+    if (io.device && !to_caller) {
+        std::vector<PoolEgress> eg;
+        for (int32_t i = 0; i < count; ++i) {
+            const int64_t cnt = out_cnt[(size_t)i];
+            if (cnt <= 0) continue;
+            eg.push_back(PoolEgress{out_base[(size_t)i], cnt, (int64_t)i * C * io.out_pitch, io.out_pitch, (int32_t)cnt, 0});
+            if (cnt > max_egress) max_egress = (int)cnt;
+        }
+        negress = (int)eg.size();
+        egress_off = put(eg.data(), eg.size() * sizeof(PoolEgress));
     }
-    memcpy(p->h_desc.p, blob.data(), blob.size());
-    // 4. two copies and the launches; the previous call has finished with both staging buffers
+    if (blob.size() > blk->h.n) {
+        size_t capn = blk->h.n ? blk->h.n : 256 * 1024;
+        while (capn < blob.size()) capn *= 2;
+        if ((st = blk->h.alloc(capn)) != PV_OK || (st = blk->d.alloc_on(capn, p->stream)) != PV_OK) return fail(st);
+    }
+    memcpy(blk->h.p, blob.data(), blob.size());
+    char *const d_desc = blk->d.p;
+    // 4. the copies and the launches.  pv_pool_feed: the previous call has finished with both staging buffers.
+    // pv_pool_feed_device: the pool's stream first waits for what the caller's stream holds now (the producer of d_in,
+    // the last reader of d_out).
     hipError_t ce = hipSuccess;
+    if (io.device) {
+        ce = hipEventRecord(blk->entry, io.user);
+        if (ce == hipSuccess) ce = hipStreamWaitEvent(p->stream, blk->entry, 0);
+        if (ce != hipSuccess) return fail(hip_fail(ce, "stream pool entry event", __LINE__));
+    }
 #ifndef PV_POOL_MAPPED_INGEST
-    if (stage_total)
+    if (stage_total && !io.device)
         ce = hipMemcpyAsync(p->d_stage.p, p->h_stage.p, stage_total * sizeof(float), hipMemcpyHostToDevice, p->stream);
     if (ce != hipSuccess) return fail(hip_fail(ce, "input upload", __LINE__));
 #endif
-    ce = hipMemcpyAsync(p->d_desc.p, p->h_desc.p, blob.size(), hipMemcpyHostToDevice, p->stream);
+    ce = hipMemcpyAsync(d_desc, blk->h.p, blob.size(), hipMemcpyHostToDevice, p->stream);
     if (ce != hipSuccess) return fail(hip_fail(ce, "descriptor upload", __LINE__));
     int nlaunch = 0;
     const int cm = phase_mode(c.d);
     for (int gi = 0; gi <= groups; ++gi) {
         const Group &g = grp[(size_t)gi];
-        launch_pool_ingest(p->stage_src, p->d_in.p, p->ring, C, reinterpret_cast<const PoolIngest *>(p->d_desc.p + g.ingest_off),
+        launch_pool_ingest(ingest_src, io.wire, p->d_in.p, p->ring, C, reinterpret_cast<const PoolIngest *>(d_desc + g.ingest_off),
                            g.ningest, g.max_in, p->stream);
         if (g.ningest > 0 && g.max_in > 0) ++nlaunch;
         const hipError_t ie = hipGetLastError();
         if (ie != hipSuccess) return fail(hip_fail(ie, "input ingest", __LINE__));
         if (gi == groups || g.nslots == 0) continue;
         PoolLaunch pl{};
-        pl.slots = reinterpret_cast<const PoolSlot *>(p->d_desc.p + g.table_off);
-        pl.desc = p->d_desc.p;
-        pl.out = p->out_dev;
+        pl.slots = reinterpret_cast<const PoolSlot *>(d_desc + g.table_off);
+        pl.desc = d_desc;
+        pl.out = launch_out;
         pl.nslots = g.nslots;
         pl.max_tn = g.max_tn;
         pl.max_tiles = g.max_tiles;
         if (p->mixed) {
-            const PoolParams *q = reinterpret_cast<const PoolParams *>(p->d_desc.p + params_off[(size_t)gi]);
+            const PoolParams *q = reinterpret_cast<const PoolParams *>(d_desc + params_off[(size_t)gi]);
             if ((st = pool_mix_launch_group(p, pl, q, vruns[(size_t)gi], &nlaunch)) != PV_OK) return fail(st);
         } else {
             if ((st = pool_launch_group(p, pl)) != PV_OK) return fail(st);
             nlaunch += 2 + (cm == 0 || cm == 1 ? 1 : 0) + (c.d.resample && pl.max_tiles > 0 ? 1 : 0);
         }
+    }
+    if (io.device) {
+        // 5'. int16: the arena into the caller's buffer; then the block's event, which the caller's stream waits for
+        if (negress > 0) {
+            launch_pool_egress_i16(p->d_arena.p, static_cast<int16_t *>(io.d_out), C,
+                                   reinterpret_cast<const PoolEgress *>(d_desc + egress_off), negress, max_egress, p->stream);
+            ++nlaunch;
+            const hipError_t ee = hipGetLastError();
+            if (ee != hipSuccess) return fail(hip_fail(ee, "int16 egress", __LINE__));
+        }
+        p->last_launches = nlaunch;
+        ce = hipEventRecord(blk->done, p->stream);
+        if (ce == hipSuccess) {
+            blk->busy = true;
+            ce = hipStreamWaitEvent(io.user, blk->done, 0);
+        }
+        if (ce != hipSuccess) return fail(hip_fail(ce, "stream pool exit event", __LINE__));
+        p->last_host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count();
+        p->last_wait_us = 0;
+        return PV_OK;
     }
     p->last_launches = nlaunch;
     // 5. wait: a sequence number behind the launches, spun on with a wall-clock bound (or a stream synchronisation
@@ -3176,6 +3369,61 @@ int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *c
             sl.outq[(size_t)ch].insert(sl.outq[(size_t)ch].end(), src, src + cnt);
         }
     }
+    return PV_OK;
+}
+
+int pv_pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const float *const *in, const int32_t *n) {
+    PoolCall io;
+    io.in = in;
+    return pool_feed(p, count, slots, n, io);
+}
+
+int pv_pool_feed_device(pv_pool *p, int32_t count, const int32_t *slots, const int32_t *n, const void *d_in,
+                        int64_t in_pitch, void *d_out, int64_t out_pitch, int32_t wire, int32_t *out_frames,
+                        void *hip_stream) {
+    if (p && (wire != PV_WIRE_F32 && wire != PV_WIRE_I16)) {
+        g_last_error = "stream pool: unknown wire " + std::to_string(wire);
+        return PV_ERR_INVALID_ARG;
+    }
+    if (p && (in_pitch < 0 || out_pitch < 0)) {
+        g_last_error = "stream pool: negative pitch";
+        return PV_ERR_INVALID_ARG;
+    }
+    PoolCall io;
+    io.device = true;
+    io.d_in = d_in, io.d_out = d_out;
+    io.in_pitch = in_pitch, io.out_pitch = out_pitch;
+    io.wire = wire;
+    io.user = static_cast<hipStream_t>(hip_stream);
+    io.out_frames = out_frames;
+    return pool_feed(p, count, slots, n, io);
+}
+
+int pv_pool_plan_feed(pv_pool *p, int32_t count, const int32_t *slots, const int32_t *n, int32_t *out_frames) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p || count < 0 || (count > 0 && (!slots || !n || !out_frames))) return PV_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < count; ++i)
+        if (!pool_slot_ok(p, slots[i]) || n[i] < 0) {
+            g_last_error = "stream pool: slot " + std::to_string(slots[i]) + (n[i] < 0 ? " has a negative size" : " is not open");
+            return PV_ERR_INVALID_ARG;
+        }
+    std::vector<SliceRec> scratch;
+    std::vector<int32_t> frames((size_t)count); // (written to the caller's array only when every slot has planned)
+    for (int32_t i = 0; i < count; ++i) {
+        Planner &pl = *p->slots[(size_t)slots[i]].planner;
+        const Planner::State before = pl.save();
+        scratch.clear();
+        const int st = pl.feed(n[i], scratch);
+        frames[(size_t)i] = pl.available();
+        pl.restore(before);
+        if (st != PV_OK) {
+            g_last_error = "stream pool: slot " + std::to_string(slots[i]) + ": " +
+                           (g_last_error.empty() ? std::string(plan_reason()) : g_last_error);
+            return st;
+        }
+    }
+    for (int32_t i = 0; i < count; ++i) out_frames[i] = frames[(size_t)i];
     return PV_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "audiomod_pv.h"
 #include "pv_atan2f.h"
 #include "pv_plan.h"
+#include "pv_wire.h"
 
 namespace {
 
@@ -41,14 +42,7 @@ __global__ void pv_f32_to_i16(const float *__restrict__ in, int16_t *__restrict_
 // each of the two instructions covers half of every line the wave touches, the other covers the rest right behind it).
 // The last, partial eight of a row go sample by sample.  A row takes bpr = ceil(width / 2048) workgroups; the grid is
 // one-dimensional (rows x bpr workgroups), so the row count is not bound by the 65 535 of a grid's second dimension.
-// The expressions are the flat kernels'.
-__device__ __forceinline__ float pv_wire_i16_to_f32(int16_t v) { return (float)v * (1.0f / 32768.0f); }
-__device__ __forceinline__ int16_t pv_wire_f32_to_i16(float x) {
-    float v = x * 32768.0f;
-    if (v > 32767.0f) v = 32767.0f;
-    else if (v < -32768.0f) v = -32768.0f;
-    return (int16_t)(int)v;
-}
+// The expressions are the flat kernels' (pv_wire.h: shared with the stream pool's ingest and egress kernels).
 __global__ __launch_bounds__(256) void pv_rows_i16_to_f32(const int16_t *__restrict__ in, float *__restrict__ out,
                                                           int rows, int64_t width, int64_t pitch, unsigned bpr) {
     const int row = (int)(blockIdx.x / bpr);

@@ -332,8 +332,17 @@ struct PoolIngest {
     int64_t src_off, src_pitch, pos;
     int32_t n, row0;
 };
-void launch_pool_ingest(const float *src, float *ring, int ring_len, int C, const PoolIngest *ents, int nents,
+// wire: the element type of src (PV_WIRE_F32: float, PV_WIRE_I16: int16_t, converted as the WAV reader does)
+void launch_pool_ingest(const void *src, int wire, float *ring, int ring_len, int C, const PoolIngest *ents, int nents,
                         int max_n, hipStream_t st);
+// int16 egress of pv_pool_feed_device: channel c of an entry is n floats at arena[src_off + c * src_pitch], converted as
+// the WAV writer does into the caller's int16 buffer at dst[dst_off + c * dst_pitch]
+struct PoolEgress {
+    int64_t src_off, src_pitch, dst_off, dst_pitch;
+    int32_t n, pad;
+};
+void launch_pool_egress_i16(const float *arena, int16_t *dst, int C, const PoolEgress *ents, int nents, int max_n,
+                            hipStream_t st);
 // Each returns false (launching nothing) when the configuration has no per-slot kernel or it does not fit;
 // launch = false: only that check (pv_pool_create asks it once).
 bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st);

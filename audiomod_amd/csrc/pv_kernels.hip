@@ -29,6 +29,8 @@
 #include "pv_atan2f.h"
 #include "pv_sincos.h"
 #include "pv_wavefft.h"
+#include "pv_wire.h"
+#include "audiomod_pv.h" // PV_WIRE_*
 
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -4079,19 +4081,54 @@ __device__ __forceinline__ void pool_resample_fast_role(const ResArgs &a, const 
         if (r < nr) out[(int64_t)r * a.out_stride_row] = acc[r];
 }
 
-__global__ __launch_bounds__(256) void pv_pool_ingest_kernel(const float *__restrict__ src, float *__restrict__ ring,
-                                                             const int ring_len, const PoolIngest *__restrict__ ents) {
+// input ingest (PoolIngest): one lane per sample, grid (ceil(max n / 256), C, entries); the source is the pool's packed
+// staging buffer or, for pv_pool_feed_device, the caller's pitched device buffer of either wire type (converted on load)
+__device__ __forceinline__ float pool_wire_load(float v) { return v; }
+__device__ __forceinline__ float pool_wire_load(int16_t v) { return pv_wire_i16_to_f32(v); }
+template <typename T>
+__device__ __forceinline__ void pool_ingest(const T *__restrict__ src, float *__restrict__ ring, const int ring_len,
+                                            const PoolIngest *__restrict__ ents) {
     const PoolIngest e = ents[blockIdx.z];
     const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
     if (i >= e.n) return;
-    ring[(int64_t)(e.row0 + c) * ring_len + ((e.pos + i) & (int64_t)(ring_len - 1))] = src[e.src_off + c * e.src_pitch + i];
+    ring[(int64_t)(e.row0 + c) * ring_len + ((e.pos + i) & (int64_t)(ring_len - 1))] =
+        pool_wire_load(src[e.src_off + c * e.src_pitch + i]);
+}
+__global__ __launch_bounds__(256) void pv_pool_ingest_kernel(const float *__restrict__ src, float *__restrict__ ring,
+                                                             const int ring_len, const PoolIngest *__restrict__ ents) {
+    pool_ingest(src, ring, ring_len, ents);
+}
+__global__ __launch_bounds__(256) void pv_pool_ingest_i16_kernel(const int16_t *__restrict__ src, float *__restrict__ ring,
+                                                                 const int ring_len, const PoolIngest *__restrict__ ents) {
+    pool_ingest(src, ring, ring_len, ents);
 }
 
-void launch_pool_ingest(const float *src, float *ring, int ring_len, int C, const PoolIngest *ents, int nents,
+void launch_pool_ingest(const void *src, int wire, float *ring, int ring_len, int C, const PoolIngest *ents, int nents,
                         int max_n, hipStream_t st) {
     if (nents <= 0 || max_n <= 0) return;
-    hipLaunchKernelGGL(pv_pool_ingest_kernel, dim3((max_n + 255) / 256, C, nents), dim3(256), 0, st, src, ring,
-                       ring_len, ents);
+    const dim3 grid((max_n + 255) / 256, C, nents);
+    if (wire == PV_WIRE_I16)
+        hipLaunchKernelGGL(pv_pool_ingest_i16_kernel, grid, dim3(256), 0, st, static_cast<const int16_t *>(src), ring,
+                           ring_len, ents);
+    else
+        hipLaunchKernelGGL(pv_pool_ingest_kernel, grid, dim3(256), 0, st, static_cast<const float *>(src), ring, ring_len,
+                           ents);
+}
+
+// int16 egress (PoolEgress): one lane per sample, neighbouring lanes write neighbouring int16 (a wave covers 128
+// contiguous bytes of a row; rows of an arbitrary pitch start on 2-byte boundaries only, so nothing wider is assumed)
+__global__ __launch_bounds__(256) void pv_pool_egress_i16_kernel(const float *__restrict__ arena, int16_t *__restrict__ dst,
+                                                                 const PoolEgress *__restrict__ ents) {
+    const PoolEgress e = ents[blockIdx.z];
+    const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    if (i >= e.n) return;
+    dst[e.dst_off + c * e.dst_pitch + i] = pv_wire_f32_to_i16(arena[e.src_off + c * e.src_pitch + i]);
+}
+
+void launch_pool_egress_i16(const float *arena, int16_t *dst, int C, const PoolEgress *ents, int nents, int max_n,
+                            hipStream_t st) {
+    if (nents <= 0 || max_n <= 0) return;
+    hipLaunchKernelGGL(pv_pool_egress_i16_kernel, dim3((max_n + 255) / 256, C, nents), dim3(256), 0, st, arena, dst, ents);
 }
 
 __device__ __forceinline__ AnalyzeArgs pool_view(const AnalyzeArgs &a, const PoolSlot &ps) {

@@ -160,6 +160,9 @@ def lib():
     L.pv_pool_get_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Info)]
     L.pv_pool_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.pv_pool_last_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.pv_pool_plan_feed.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_pool_feed_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     L.pv_pool_create_mixed.argtypes = [C.POINTER(Config), C.POINTER(PoolRange), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]
     L.pv_pool_open_with.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_int32)]
     i64p = C.POINTER(C.c_int64)
@@ -690,6 +693,7 @@ class StreamPool:
         self.L = lib()
         self.cfg = make_config(channels, **config)
         self.channels = channels
+        self.device = device
         self.h = C.c_void_p()
         if pitch_range is None and ratio_range is None:
             _check(self.L.pv_pool_create(C.byref(self.cfg), int(capacity), device, C.byref(self.h)), "pv_pool_create")
@@ -736,6 +740,44 @@ class StreamPool:
         _check(self.L.pv_pool_feed(self.h, len(slots), slots.ctypes.data, _pp(rows) if rows else None,
                                    n.ctypes.data), "pv_pool_feed")
 
+    def plan_feed(self, slots, n):
+        """Host only: the frames each of `slots` would have available after a feed of n[i] frames (for a slot without
+        pending output: what feed_device returns for it); changes nothing.  int32 array."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        assert slots.ndim == 1 and n.shape == slots.shape
+        out = np.zeros(len(slots), np.int32)
+        _check(self.L.pv_pool_plan_feed(self.h, len(slots), slots.ctypes.data, n.ctypes.data, out.ctypes.data),
+               "pv_pool_plan_feed")
+        return out
+
+    def feed_device(self, slots, x, n=None, out=None, stream=None):
+        """feed() and retrieve-all for `slots` with input and output on the device (pv_pool_feed_device).  x: torch
+        tensor [len(slots), channels, in_pitch], float32 or int16, on the pool's device, contiguous; entry i holds n[i]
+        frames of slots[i] from offset 0 (n defaults to the pitch).  out: [len(slots), channels, out_pitch] of x's type
+        (allocated from plan_feed when None).  Returns (out, out_frames): out_frames[i] frames of out[i] are valid, bit
+        for bit what feed() + retrieve() deliver.  Asynchronous: enqueued on `stream` (default: the current one) and
+        not waited for; x and out may be reused in stream order."""
+        import torch
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        assert slots.ndim == 1
+        assert x.is_cuda and x.device.index == self.device and x.is_contiguous() and x.dim() == 3
+        assert x.dtype in (torch.float32, torch.int16) and tuple(x.shape[:2]) == (len(slots), self.channels)
+        wire = 0 if x.dtype == torch.float32 else 1
+        n = np.full(len(slots), x.shape[2], np.int32) if n is None else np.ascontiguousarray(n, dtype=np.int32)
+        assert n.shape == slots.shape
+        if out is None:
+            pitch = max(int(self.plan_feed(slots, n).max(initial=0)), 1)
+            out = torch.empty((len(slots), self.channels, pitch), dtype=x.dtype, device=x.device)
+        assert out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == x.dtype
+        assert out.dim() == 3 and tuple(out.shape[:2]) == (len(slots), self.channels)
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        frames = np.zeros(len(slots), np.int32)
+        _check(self.L.pv_pool_feed_device(self.h, len(slots), slots.ctypes.data, n.ctypes.data, C.c_void_p(x.data_ptr()),
+                                          int(x.shape[2]), C.c_void_p(out.data_ptr()), int(out.shape[2]), wire,
+                                          frames.ctypes.data, C.c_void_p(s.cuda_stream)), "pv_pool_feed_device")
+        return out, frames
+
     def available(self, slot):
         return self.L.pv_pool_available(self.h, int(slot))
 
@@ -755,13 +797,14 @@ class StreamPool:
         return i.as_dict()
 
     def last_timing(self):
-        """(host_us, wait_us) of the last feed(): host work up to the wait for the device, and that wait."""
+        """(host_us, wait_us) of the last feed(): host work up to the wait for the device, and that wait (0 after a
+        feed_device(), which does not wait)."""
         h, w = C.c_double(), C.c_double()
         _check(self.L.pv_pool_last_timing(self.h, C.byref(h), C.byref(w)), "pv_pool_last_timing")
         return h.value, w.value
 
     def last_launches(self):
-        """Kernels launched by the last feed()."""
+        """Kernels launched by the last feed() or feed_device()."""
         n = C.c_int32(0)
         _check(self.L.pv_pool_last_launches(self.h, C.byref(n)), "pv_pool_last_launches")
         return n.value

@@ -173,10 +173,51 @@ int32_t pv_pool_available(const pv_pool *p, int32_t slot);   /* -1: not an open 
 int32_t pv_pool_retrieve(pv_pool *p, int32_t slot, float *const *out, int32_t n); /* frames copied, -1: bad slot */
 int pv_pool_get_info(const pv_pool *p, int32_t slot, pv_info *info);
 /* Diagnostics: wall-clock time of the last pv_pool_feed, split into the host's share up to the wait (planning,
- * descriptors, staging, enqueueing the launches) and the wait for the device. */
+ * descriptors, staging, enqueueing the launches) and the wait for the device.  After a pv_pool_feed_device (below),
+ * which does not wait: the call's host time and a wait of 0. */
 int pv_pool_last_timing(const pv_pool *p, double *host_us, double *wait_us);
-/* Kernels launched by the last pv_pool_feed (the input scatter included). */
+/* Kernels launched by the last pv_pool_feed or pv_pool_feed_device (the input scatter and, with int16 on the wire, the
+ * egress kernel included). */
 int pv_pool_last_launches(const pv_pool *p, int32_t *launches);
+
+/* Device-resident feed: input and output in device memory, float or int16 (PV_WIRE_F32 / PV_WIRE_I16 below), enqueued
+ * and not waited for.  For every listed slot the call is pv_pool_feed with the same samples followed by a
+ * pv_pool_retrieve of everything available: out_frames[i] is that count, written before the call returns (the count is
+ * data-independent: the slot's planner books feed and retrieve at call time); the samples written to d_out are bit for
+ * bit what that pair delivers; pv_pool_available is 0 for these slots afterwards.  Plain and mixed pools, either
+ * arithmetic setting.
+ *   d_in : [count][C][in_pitch]   entry i, channel c: n[i] valid elements from offset 0
+ *   d_out: [count][C][out_pitch]  entry i, channel c: out_frames[i] valid elements from offset 0; the rest of a row is
+ *          not written
+ *   wire : the element type of BOTH buffers, float (PV_WIRE_F32) or int16_t (PV_WIRE_I16); the pitches are in
+ *          elements and arbitrary (the kernels store sample by sample: no alignment is required of pitch or base
+ *          beyond the element's own).  int16 converts as pv_hostio does, the reference's WAV reader and writer:
+ *          in int16 * (1/32768); out saturate(x * 32768, -32768, 32767) truncated toward zero.
+ * pv_pool_plan_feed: host only -- the frames each slot would have available after a feed of n[i] frames (for a slot
+ *   without pending output: the out_frames[i] of pv_pool_feed_device); changes nothing.
+ * Order: the reads of d_in and the writes of d_out are ordered on `hip_stream` (a hipStream_t passed as void*; NULL =
+ *   the default stream) -- the pool's internal stream waits for an event recorded on hip_stream at entry, and
+ *   hip_stream waits for the pool's work at exit (the rule of pv_batch_run_span), so both buffers may be reused in
+ *   stream order as soon as the call returns.  Up to four calls are in flight; a further one first waits on the host
+ *   for the oldest to finish.  pv_pool_feed, pv_pool_open, pv_pool_close and pv_pool_destroy may be called while device
+ *   feeds are in flight (pv_pool_feed first waits for them).
+ * Host waits: the call does not synchronise, with these exceptions.  A fifth call in flight waits for the oldest (above).
+ *   A call that has to GROW one of the pool's buffers (a descriptor block, the int16 arena) frees the old one, which
+ *   waits for the device -- the caller's streams included -- and an arena is grown only after the pool's stream has
+ *   drained; the buffers start at sizes that serve a few hundred slices per call and double, so this happens a few
+ *   times in a pool's life, typically in its first calls.  New buffers are zero-filled on the pool's own stream.
+ *   pv_pool_create itself ends with a wait for the default stream (its buffers are zero-filled there).
+ * All or nothing, decided before any device call: PV_ERR_INVALID_ARG (pv_last_error() names the slot) for every refusal
+ *   of pv_pool_feed, a listed slot that still holds output of pv_pool_feed not yet retrieved, an unknown wire,
+ *   n[i] > in_pitch, a planned out_frames[i] > out_pitch, a NULL buffer where a size is positive; a planner's refusal
+ *   with the planner's status.  A refused call leaves the pool and out_frames exactly as they were (pv_pool_plan_feed
+ *   likewise writes out_frames only when it returns PV_OK).  A launch error that shows only after the call has
+ *   returned is reported, and leaves the pool unusable, when its descriptor block is next waited for: by the fourth
+ *   pv_pool_feed_device after it, by the next pv_pool_feed, or by a pv_pool_open that uploads a resampling table. */
+int pv_pool_plan_feed(pv_pool *p, int32_t count, const int32_t *slots, const int32_t *n, int32_t *out_frames);
+int pv_pool_feed_device(pv_pool *p, int32_t count, const int32_t *slots, const int32_t *n, const void *d_in,
+                        int64_t in_pitch, void *d_out, int64_t out_pitch, int32_t wire, int32_t *out_frames,
+                        void *hip_stream);
 
 /* Mixed pool: slots of one pool at different pitches and time ratios.  cfg fixes sample_rate, channels, mode, coremode,
  * fftsize and hopsize for every slot; a slot opened with pv_pool_open_with(time_ratio, pitch_semitones) is a fresh
