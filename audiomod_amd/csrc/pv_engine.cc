@@ -393,10 +393,18 @@ struct Core {
     // ... for any derived constants (the stream pool asks it per slot)
     static bool fast_capable_of(const Derived &d, bool fast_arith) {
         if (!(fast_arith && (d.fft.nc == 256 || d.fft.nc == 512 || d.fft.nc == 1024 || d.fft.nc == 2048))) return false;
+        return synth_chain_has_fast(chain_probe(d));
+    }
+    // what the fused ladder's predicate (pv_kernels.hip synth_chain_plain_core) reads, from the derived constants alone
+    static SynthArgs chain_probe(const Derived &d) {
         SynthArgs probe = synth_variant(d);
         probe.tb.nc = d.fft.nc;
         probe.whisper = d.whisper ? reinterpret_cast<const float *>(&d) : nullptr; // (only tested against null)
-        return synth_chain_has_fast(probe);
+        return probe;
+    }
+    // waves per workgroup the fused kernel of this configuration is compiled for (init sizes chain_waves below it)
+    static int chain_wave_bound(const Derived &d, bool fast_arith) {
+        return synth_chain_max_waves(chain_probe(d), fast_capable_of(d, fast_arith));
     }
     // what selects the synthesis kernel's variant, from the derived constants alone
     static SynthArgs synth_variant(const Derived &d) {
@@ -536,18 +544,12 @@ int Core::init(const pv_config &cfg, int dev, int nstreams, int chunk_slices) {
             const char *e3 = getenv("AUDIOMOD_PV_THREE_STAGE");
             three_stage = pipelined_planes && d.resample && !(e3 && atoi(e3) == 0);
         }
-        int wmax = d.fft.nc == 2048 ? 8 : ((pipelined_planes && !three_stage) ? 12 : 16);
-        {
-            // the all-modes synthesis variant is compiled for twelve waves (pv_kernels.hip pv_synth_chain_kernel)
-            const char *g = getenv("AUDIOMOD_PV_SYNTH_GENERIC"); // (tests: every mode through the all-modes variant)
-            const bool plain = !d.do_freq_comp && !d.vocoder && !d.robotic && !d.constant && !d.whisper &&
-                               !(g && atoi(g) != 0);
-            // (round 3: the FREE-FORM formant / gender kernel fits 128 registers, sixteen waves: pv_kernels.hip
-            // chain_kernel_max_threads)
-            const bool fc_fast = d.do_freq_comp && !d.vocoder && !d.robotic && !d.constant && !d.whisper && !(g && atoi(g) != 0) &&
-                                 d.cfg.coremode == 1 && d.fft.nc == 1024 && fast_capable();
-            if (!plain && !fc_fast && wmax > 12) wmax = 12;
-        }
+        // ... and no more than the kernel the ladder picks is compiled for: eight at fft 4096, twelve for the all-modes
+        // variant and the reference-order formant / gender kernel, else sixteen (pv_kernels.hip chain_kernel_max_threads;
+        // the rule is stated there, once, beside the predicate)
+        const int wmax_rung = chain_wave_bound(d, fast_arith);
+        int wmax = (pipelined_planes && !three_stage) ? 12 : 16;
+        if (wmax > wmax_rung) wmax = wmax_rung;
         if (const char *e = getenv("AUDIOMOD_PV_CHAIN_WAVES")) { // tuning knob: upper bound of waves per workgroup
             const int v = atoi(e);
             if (v >= 1 && v <= (d.fft.nc == 2048 ? 8 : 16)) wmax = v;
@@ -1448,6 +1450,63 @@ int pv_set_arithmetic(int arith) {
 }
 int pv_get_arithmetic(void) { return g_arith; }
 
+// ---- diagnostics: the launchers' census (pv_kernels.hip) and the rung a configuration gets
+static const char *const kCensusSetName[PV_CENSUS_SETS] = {"batch", "pool", "pmix", "mb"};
+static std::string g_census_file;
+static void census_append_at_exit() {
+    std::string out;
+    char line[160];
+    static const int ncs[4] = {256, 512, 1024, 2048};
+    for (int set = 0; set < PV_CENSUS_SETS; ++set) {
+        for (int nc : ncs)
+            for (int core = -1; core <= 3; ++core)
+                for (int res = 0; res < 2; ++res)
+                    for (int fast = 0; fast < 2; ++fast) {
+                        const int64_t n = chain_census_count(PV_CENSUS_CHAIN, set, nc, core, res, fast);
+                        if (n <= 0) continue;
+                        snprintf(line, sizeof line, "chain set=%s nc=%d core=%d res=%d fast=%d count=%lld\n",
+                                 kCensusSetName[set], nc, core, res, fast, (long long)n);
+                        out += line;
+                    }
+        for (int fast = 0; fast < 2; ++fast)
+            for (int interp = 0; interp < 2; ++interp) {
+                const int64_t n = chain_census_count(PV_CENSUS_RESAMPLE, set, fast, interp, 0, 0);
+                if (n <= 0) continue;
+                snprintf(line, sizeof line, "resample set=%s fast=%d interp=%d count=%lld\n", kCensusSetName[set], fast,
+                         interp, (long long)n);
+                out += line;
+            }
+        for (int nc : ncs)
+            for (int split = 0; split < 2; ++split) {
+                const int64_t n = chain_census_count(PV_CENSUS_ANALYZE, set, nc, split, 0, 0);
+                if (n <= 0) continue;
+                snprintf(line, sizeof line, "analyze set=%s nc=%d split=%d count=%lld\n", kCensusSetName[set], nc, split,
+                         (long long)n);
+                out += line;
+            }
+    }
+    if (out.empty()) return;
+    if (FILE *f = fopen(g_census_file.c_str(), "a")) { // one write per process: lines of concurrent processes stay whole
+        fwrite(out.data(), 1, out.size(), f);
+        fclose(f);
+    }
+}
+static const bool g_census_from_env = [] {
+    const char *e = getenv("AUDIOMOD_PV_CHAIN_CENSUS");
+    if (!e || !*e) return false;
+    g_census_file = e;
+    chain_census_enable(true);
+    atexit(census_append_at_exit);
+    return true;
+}();
+int pv_debug_chain_census(int on) {
+    chain_census_enable(on != 0);
+    return PV_OK;
+}
+int64_t pv_debug_chain_census_count(int kind, int set, int a, int b, int c, int d) {
+    return chain_census_count(kind, set, a, b, c, d);
+}
+
 const char *pv_last_error(void) { return g_last_error.empty() ? plan_reason() : g_last_error.c_str(); }
 
 int pv_device_count(void) { return count_gfx950(); }
@@ -1481,6 +1540,23 @@ int pv_plan_simulate(const pv_config *cfg, const int32_t *n, int32_t ncalls, int
     }
     if (nslices) *nslices = (int64_t)sl.size();
     if (info) fill_info(d, (int64_t)sl.size(), info);
+    return PV_OK;
+}
+
+int pv_debug_chain_rung(const pv_config *cfg, int arith, pv_chain_rung *out) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!cfg || !out || (arith != PV_ARITH_FAST && arith != PV_ARITH_EXACT)) return PV_ERR_INVALID_ARG;
+    Derived d;
+    const int st = derive(*cfg, d);
+    if (st != PV_OK) return st;
+    const bool fast_arith = arith == PV_ARITH_FAST;
+    out->nc = d.fft.nc;
+    out->plain_core = synth_chain_plain_core(Core::chain_probe(d));
+    out->resample = d.resample ? 1 : 0;
+    out->fast = Core::fast_capable_of(d, fast_arith) ? 1 : 0; // ChainArgs::fast, which an all-modes launch ignores
+    out->wave_bound = Core::chain_wave_bound(d, fast_arith);
+    out->reciprocal_wden = Core::fast_capable_of(d, fast_arith) ? 1 : 0; // Core::fast_chain() on the fused path
     return PV_OK;
 }
 

@@ -245,6 +245,20 @@ struct ChainArgs {
     int fast; // host-side only: pick the free-form (PV_ARITH_FAST) kernel where one exists; wden then holds reciprocals
 };
 bool synth_chain_has_fast(const SynthArgs &s);
+// The rung of launch_chain's ladder a configuration gets (s: what Core::synth_variant fills, plus tb.nc and whisper):
+// the predicate's value and the launch bounds, in waves, of the kernel the ladder picks for it -- per kernel set,
+// `fast` being ChainArgs::fast.  Sizes without a wave transform have no fused synthesis kernel; for them the bound is
+// the one Core::init always used with pv_frames_chain_kernel (sixteen waves for a plain configuration, else twelve).
+int synth_chain_plain_core(const SynthArgs &s);
+int synth_chain_max_waves(const SynthArgs &s, bool fast);
+
+// Diagnostics: a process-wide census of what the launchers chose (include/audiomod_pv.h pv_debug_chain_census*).
+// Off by default; a launch then tests one static flag and nothing else.
+enum { PV_CENSUS_SETS = 4 }; // PV_CENSUS_SET_BATCH / POOL / PMIX / MB of the C ABI
+void chain_census_enable(bool on); // clears the table either way
+// kind: PV_CENSUS_CHAIN (a = NC, b = kPlainCore, c = kRes, d = kFast), PV_CENSUS_RESAMPLE (a = fast, b = interpolated),
+// PV_CENSUS_ANALYZE (a = NC, b = split); -1 for a key that does not exist
+int64_t chain_census_count(int kind, int set, int a, int b, int c, int d);
 
 // pv_resample_kernel: one workgroup = 256 outputs of two rows
 struct ResTile {

@@ -33,6 +33,7 @@
 #include "audiomod_pv.h" // PV_WIRE_*
 
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdlib>
 
 namespace pv {
@@ -3254,9 +3255,54 @@ size_t chain_lds_bytes(const ChainArgs &a, int nc_wave) {
 // --- Where a fused kernel is chosen (all four sets: this batch kernel and the pool / pmix / mb slot-table kernels) ---
 static bool chain_nc_has_wave(int nc) { return nc == 256 || nc == 512 || nc == 1024 || nc == 2048; }
 
+// Diagnostics: the census of the launchers' choices (pv_kernels.h).  Fixed tables of relaxed atomic counters: a launch
+// with the census off tests g_census_on and nothing else; with it on it adds one to one counter (no lock, no
+// allocation either way).
+static std::atomic<bool> g_census_on{false};
+static constexpr int kCensusNc = 4, kCensusCore = 5; // NC 256 ... 2048; kPlainCore -1 ... 3
+static std::atomic<uint64_t> g_census_chain[PV_CENSUS_SETS][kCensusNc][kCensusCore][2][2];
+static std::atomic<uint64_t> g_census_res[PV_CENSUS_SETS][2][2];
+static std::atomic<uint64_t> g_census_ana[PV_CENSUS_SETS][kCensusNc][2];
+static int census_nc_index(int nc) { return nc == 256 ? 0 : nc == 512 ? 1 : nc == 1024 ? 2 : nc == 2048 ? 3 : -1; }
+static inline void census_chain(int set, int nc, int plain_core, int res, bool fast) {
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    g_census_chain[set][census_nc_index(nc)][plain_core + 1][res][fast ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+}
+static inline void census_resample(int set, bool fast, bool interp) {
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    g_census_res[set][fast ? 1 : 0][interp ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+}
+static inline void census_analyze(int set, int nc, bool split) {
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    g_census_ana[set][census_nc_index(nc)][split ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+}
+void chain_census_enable(bool on) {
+    g_census_on.store(false, std::memory_order_relaxed);
+    for (auto &a : g_census_chain) for (auto &b : a) for (auto &c : b) for (auto &d : c) for (auto &e : d) e.store(0, std::memory_order_relaxed);
+    for (auto &a : g_census_res) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
+    for (auto &a : g_census_ana) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
+    g_census_on.store(on, std::memory_order_relaxed);
+}
+int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
+    if (set < 0 || set >= PV_CENSUS_SETS) return -1;
+    const auto flag = [](int v) { return v == 0 || v == 1; };
+    switch (kind) {
+    case 0:
+        if (census_nc_index(a) < 0 || b < -1 || b > 3 || !flag(c) || !flag(d)) return -1;
+        return (int64_t)g_census_chain[set][census_nc_index(a)][b + 1][c][d].load(std::memory_order_relaxed);
+    case 1:
+        if (!flag(a) || !flag(b)) return -1;
+        return (int64_t)g_census_res[set][a][b].load(std::memory_order_relaxed);
+    case 2:
+        if (census_nc_index(a) < 0 || !flag(b)) return -1;
+        return (int64_t)g_census_ana[set][census_nc_index(a)][b].load(std::memory_order_relaxed);
+    default: return -1;
+    }
+}
+
 // The specialisation (kPlainCore) a configuration gets: 0 / 1 / 2 = the plain kernel of that core mode, 3 = frequency
 // compensation with the phase-locked core (formant / gender modes; nc 1024, that is fft 2048, only), -1 = the all-modes kernel.
-static int synth_chain_plain_core(const SynthArgs &s) {
+int synth_chain_plain_core(const SynthArgs &s) {
     const bool plain = !s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
                        !synth_generic_only() && s.coremode >= 0 && s.coremode <= 2;
     const bool fc_locked = s.do_freq_comp && s.voc_band_len < 0 && !s.robotic && !s.passthru && !s.whisper &&
@@ -3275,13 +3321,21 @@ bool synth_chain_has_fast(const SynthArgs &s) { return chain_nc_has_wave(s.tb.nc
 //   Set::max_threads(NC, kPlainCore, kFast)                  the launch bounds the kernel is compiled for;
 //   Set::fit_waves(c, max_threads)                           what a launch wider than that does (false: no launch).
 // launch == false: the checks only.
+// (only the specialisations have a free-form twin: an all-modes launch is kFast = false whatever c.fast says)
+static constexpr bool chain_uses_fast(int plain_core, bool fast) { return plain_core >= 0 && fast; }
+int synth_chain_max_waves(const SynthArgs &s, bool fast) {
+    const int plain_core = synth_chain_plain_core(s);
+    if (!chain_nc_has_wave(s.tb.nc)) return plain_core >= 0 ? 16 : 12;
+    return chain_kernel_max_threads(s.tb.nc, plain_core, chain_uses_fast(plain_core, fast)) / 64;
+}
 template <class Set, int NC, int kPlainCore> static bool launch_chain_variant(const Set &set, const ChainArgs &c_in, bool launch) {
-    const bool use_fast = kPlainCore >= 0 && c_in.fast;
+    const bool use_fast = chain_uses_fast(kPlainCore, c_in.fast);
     const int max_threads = use_fast ? Set::max_threads(NC, kPlainCore, true) : Set::max_threads(NC, kPlainCore, false);
     ChainArgs c = c_in;
     if (!Set::fit_waves(c, max_threads)) return false;
     const size_t lds = chain_lds_bytes(c, NC);
     if (!launch) return true;
+    census_chain(Set::census_set, NC, kPlainCore, c.resample ? 1 : 0, use_fast);
     const dim3 block(64 * c.waves);
     if constexpr (kPlainCore >= 0) { // the specialisations have a free-form (PV_ARITH_FAST) twin
         if (c.fast) {
@@ -3317,6 +3371,7 @@ template <class Set> static bool launch_chain(const Set &set, const SynthArgs &s
 }
 
 struct BatchChainSet { // grid (rows, runs); no trailing arguments
+    static constexpr int census_set = 0;
     const SynthArgs &s;
     hipStream_t st;
     static constexpr int max_threads(int NC, int kPlainCore, bool kFast) { return chain_kernel_max_threads(NC, kPlainCore, kFast); }
@@ -4169,6 +4224,7 @@ __global__ __launch_bounds__(128) void pv_pool_analyze_split_kernel(const Analyz
 template <class Set> static bool launch_slot_analyze(const Set &set, const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st) {
     const dim3 grid(a.rows * p.max_tn, p.nslots);
     const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
+    if (census_nc_index(a.tb.nc) >= 0) census_analyze(Set::census_set, a.tb.nc, a.tb.nc == 2048 && a.split);
     switch (a.tb.nc) {
     case 256: set.template wave<256, false>(grid, WF<256>::LDS_CF * sizeof(cf) + atab, st, a); return true;
     case 512: set.template wave<512, false>(grid, WF<512>::LDS_CF * sizeof(cf) + atab, st, a); return true;
@@ -4181,6 +4237,7 @@ template <class Set> static bool launch_slot_analyze(const Set &set, const Analy
     }
 }
 struct PoolAnalyzeSet { // trailing argument p
+    static constexpr int census_set = 1;
     const PoolLaunch &p;
     template <int NC, bool kBigLds> void wave(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
         launch_maybe_big_lds<pv_pool_analyze_wave_kernel<NC>, kBigLds>(grid, dim3(64), lds, st, a, p);
@@ -4309,6 +4366,7 @@ static bool slot_chain_fit_waves(ChainArgs &c, int max_threads) {
     return c.waves >= 1;
 }
 struct PoolChainSet { // grid (rows, slots); trailing argument p
+    static constexpr int census_set = 1;
     const SynthArgs &s;
     const PoolLaunch &p;
     hipStream_t st;
@@ -4360,6 +4418,7 @@ static bool launch_slot_resample(const Set &set, const ResArgs &a, const PoolLau
     const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
     if (lds > kMaxDynLds) return false;
     if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
+    census_resample(Set::census_set, kFast, a.interp != 0);
     const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
     if constexpr (kFast) {
         if (a.interp) set.template fast<2, NR>(grid, lds, st, a);
@@ -4372,6 +4431,7 @@ static bool launch_slot_resample(const Set &set, const ResArgs &a, const PoolLau
 }
 
 struct PoolResampleSet { // trailing argument p
+    static constexpr int census_set = 1;
     const PoolLaunch &p;
     template <int kRes, int NR> void fast(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {
         static_assert(NR == kPoolResFastRows, "the kernel's row count");
@@ -4416,6 +4476,7 @@ __global__ __launch_bounds__(128) void pv_pmix_analyze_split_kernel(const Analyz
 }
 
 struct PmixAnalyzeSet { // trailing arguments p, q
+    static constexpr int census_set = 2;
     const PoolLaunch &p;
     const PoolParams *q;
     template <int NC, bool kBigLds> void wave(dim3 grid, size_t lds, hipStream_t st, const AnalyzeArgs &a) const {
@@ -4539,6 +4600,7 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
 }
 
 struct PmixChainSet { // grid (rows, slots); trailing arguments p, q
+    static constexpr int census_set = 2;
     const SynthArgs &s;
     const PoolLaunch &p;
     const PoolParams *q;
@@ -4588,6 +4650,7 @@ __global__ __launch_bounds__(kTileOut) void pv_pmix_resample_fast_kernel(const R
 }
 
 struct PmixResampleSet { // trailing arguments p, q
+    static constexpr int census_set = 2;
     const PoolLaunch &p;
     const PoolParams *q;
     template <int kRes, int NR> void fast(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {
@@ -4652,6 +4715,7 @@ __global__ __launch_bounds__(128) void pv_mb_analyze_split_kernel(const AnalyzeA
 }
 
 struct MbAnalyzeSet { // trailing arguments p, q, m
+    static constexpr int census_set = 3;
     const PoolLaunch &p;
     const PoolParams *q;
     const MbSlot *m;
@@ -4774,6 +4838,7 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
 }
 
 struct MbChainSet { // grid (rows, max_runs, slots); trailing arguments p, q, m
+    static constexpr int census_set = 3;
     const SynthArgs &s;
     const PoolLaunch &p;
     const PoolParams *q;
@@ -4807,6 +4872,7 @@ __global__ __launch_bounds__(kTileOut) void pv_mb_resample_fast_kernel(const Res
     pool_resample_fast_role<kRes, NR>(v, blockIdx.x, blockIdx.y, smem_raw);
 }
 struct MbResampleSet { // trailing arguments p, q; the free-form kernel only
+    static constexpr int census_set = 3;
     const PoolLaunch &p;
     const PoolParams *q;
     template <int kRes, int NR> void fast(dim3 grid, size_t lds, hipStream_t st, const ResArgs &a) const {

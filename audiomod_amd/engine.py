@@ -70,6 +70,11 @@ class PoolRange(C.Structure):
                 ("max_time_ratio", C.c_float)]
 
 
+class ChainRung(C.Structure):
+    _fields_ = [("nc", C.c_int32), ("plain_core", C.c_int32), ("resample", C.c_int32), ("fast", C.c_int32),
+                ("wave_bound", C.c_int32), ("reciprocal_wden", C.c_int32)]
+
+
 _lib = None
 
 
@@ -143,6 +148,10 @@ def lib():
     L.pv_debug_atan2f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
     L.pv_debug_polar.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
     L.pv_debug_sqrt_sweep.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int]
+    L.pv_debug_chain_census.argtypes = [C.c_int]
+    L.pv_debug_chain_census_count.argtypes = [C.c_int] * 6
+    L.pv_debug_chain_census_count.restype = C.c_int64
+    L.pv_debug_chain_rung.argtypes = [C.POINTER(Config), C.c_int, C.POINTER(ChainRung)]
     L.pv_host_alloc.argtypes = [C.c_size_t]
     L.pv_host_alloc.restype = C.c_void_p
     L.pv_host_free.argtypes = [C.c_void_p]
@@ -211,6 +220,52 @@ def set_arithmetic(arith):
 
 def get_arithmetic():
     return lib().pv_get_arithmetic()
+
+
+CENSUS_SETS = ("batch", "pool", "pmix", "mb")  # PV_CENSUS_SET_*: the four sets of the fused kernel
+CENSUS_NC = (256, 512, 1024, 2048)
+
+
+def chain_census(on=True):
+    """Clears the process-wide census of the launchers' choices (include/audiomod_pv.h pv_debug_chain_census) and
+    switches it on or off."""
+    _check(lib().pv_debug_chain_census(1 if on else 0), "pv_debug_chain_census")
+
+
+def chain_census_read():
+    """The non-zero keys of the census as three dicts: fused kernel {(set, nc, plain_core, res, fast): launches},
+    slot-table resampler {(set, fast, interpolated): launches}, slot-table analysis {(set, nc, split): launches}; `set`
+    is one of CENSUS_SETS."""
+    count = lib().pv_debug_chain_census_count
+    chain, res, ana = {}, {}, {}
+    for i, name in enumerate(CENSUS_SETS):
+        for nc in CENSUS_NC:
+            for core in (-1, 0, 1, 2, 3):
+                for r in (0, 1):
+                    for f in (0, 1):
+                        n = count(0, i, nc, core, r, f)
+                        if n > 0:
+                            chain[(name, nc, core, r, f)] = n
+            for split in (0, 1):
+                n = count(2, i, nc, split, 0, 0)
+                if n > 0:
+                    ana[(name, nc, split)] = n
+        for f in (0, 1):
+            for interp in (0, 1):
+                n = count(1, i, f, interp, 0, 0)
+                if n > 0:
+                    res[(name, f, interp)] = n
+    return chain, res, ana
+
+
+def chain_rung(arith, channels=2, **config):
+    """Host only (works without a GPU): the rung of the fused ladder a configuration gets under `arith` (ARITH_FAST /
+    ARITH_EXACT), as a dict of nc, plain_core, resample, fast, wave_bound and reciprocal_wden (include/audiomod_pv.h
+    pv_debug_chain_rung)."""
+    cfg = make_config(channels, **config)
+    r = ChainRung()
+    _check(lib().pv_debug_chain_rung(C.byref(cfg), int(arith), C.byref(r)), "pv_debug_chain_rung")
+    return {k: getattr(r, k) for k, _ in r._fields_}
 
 
 def _check(st, what):

@@ -445,6 +445,38 @@ int pv_debug_polar(const float *im, const float *re, float *phase, float *mag, i
  * [first_bits, first_bits + count): the number of mismatches and the first offending pattern. */
 int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatches, uint32_t *first_bad, int device);
 
+/* Diagnostics: a census of what the launchers chose.  The fused synthesis + overlap-add kernel exists in four sets
+ * (batch, uniform pool, mixed pool, mixed batch) of 60 instantiations each; the census counts launches per
+ * instantiation ACTUALLY launched, so a test can assert which one it ran instead of re-deriving the choice.
+ *   PV_CENSUS_CHAIN    : a = NC (fft size / 2: 256 ... 2048), b = kPlainCore (0 / 1 / 2 plain per core mode, 3 =
+ *                        frequency compensation phase-locked, -1 = all modes), c = kRes, d = kFast (the template
+ *                        argument: 0 for an all-modes launch whatever the arithmetic setting)
+ *   PV_CENSUS_RESAMPLE : slot-table resampler (pool / pmix / mb sets): a = free-form kernel, b = interpolated table
+ *   PV_CENSUS_ANALYZE  : slot-table analysis (pool / pmix / mb sets): a = NC, b = the two-wave split kernel
+ * Process-wide and off by default (a launch then tests one flag).  pv_debug_chain_census(on) clears the counts and
+ * switches counting on or off; pv_debug_chain_census_count returns a key's count, -1 for a key that does not exist.
+ * If the environment variable AUDIOMOD_PV_CHAIN_CENSUS names a file when the library is loaded, the census is on from
+ * the start and the process appends its non-zero keys to that file when it exits, one line per key (child processes
+ * inherit the variable and append too). */
+#define PV_CENSUS_CHAIN 0
+#define PV_CENSUS_RESAMPLE 1
+#define PV_CENSUS_ANALYZE 2
+#define PV_CENSUS_SET_BATCH 0
+#define PV_CENSUS_SET_POOL 1
+#define PV_CENSUS_SET_PMIX 2
+#define PV_CENSUS_SET_MB 3
+int pv_debug_chain_census(int on);
+int64_t pv_debug_chain_census_count(int kind, int set, int a, int b, int c, int d);
+/* ... and, host only (no device needed), the rung of the fused ladder that cfg would get under `arith` (PV_ARITH_*):
+ * nc, the predicate's value (kPlainCore), resample (kRes) and fast (kFast) -- by the engine's own route, not a second
+ * statement of the rule -- with what engine creation decides beside it: the upper bound of waves per workgroup it
+ * sizes the launch by, and whether it uploads the window-sum denominators as reciprocals. */
+typedef struct pv_chain_rung {
+    int32_t nc, plain_core, resample, fast;
+    int32_t wave_bound, reciprocal_wden;
+} pv_chain_rung;
+int pv_debug_chain_rung(const pv_config *cfg, int arith, pv_chain_rung *out);
+
 #define PV_WIRE_F32 0
 #define PV_WIRE_I16 1
 typedef struct pv_hostio pv_hostio;
