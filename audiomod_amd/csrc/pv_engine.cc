@@ -23,6 +23,7 @@
 #include "pv_kernels.h"
 #include "pv_wavefft.h"
 #include "pv_plan.h"
+#include "pv_snapshot.h"
 
 namespace pv {
 
@@ -1387,7 +1388,7 @@ struct pv_pool {
     std::vector<Tab> tabs;
     DevBuf<float4> d_tabs; // [capacity][tab_stride]
     size_t tab_stride = 0; // float4 per entry
-    int last_launches = 0; // kernels launched by the last pv_pool_feed / pv_pool_feed_device
+    int last_launches = 0; // kernels launched by the last feed, device feed, save or restore
     DevBuf<float> d_in, d_stage; // device input rings [capacity * C][ring]; a call's packed new samples
     PinBuf<float> h_stage;
     const float *stage_src = nullptr; // what the ingest kernel reads: d_stage (or h_stage mapped, PV_POOL_MAPPED_INGEST)
@@ -1413,6 +1414,13 @@ struct pv_pool {
     uint32_t *flag_dev = nullptr;
     uint32_t flag_seq = 0;
     bool wait_value = false; // the device supports stream memory operations: spin on a flag instead of synchronising
+    // Snapshots (pv_pool_save / pv_pool_restore): the device staging buffer the gather / scatter kernel works on, its
+    // page-locked image (one copy per call between the two), and the call's segment table, page-locked and read by the
+    // kernel through its mapping (seg_dev).  All three grow on demand.
+    DevBuf<char> d_snap;
+    PinBuf<char> h_snap;
+    PinBuf<SnapSeg> h_seg;
+    const SnapSeg *seg_dev = nullptr;
     ~pv_pool() {
         if (stream) {
             (void)hipStreamSynchronize(stream); // (device feeds may be in flight)
@@ -2668,6 +2676,149 @@ static void pool_release_tab(pv_pool *p, pv_pool::Slot &sl) {
     sl.tab = -1;
 }
 
+// A mixed pool's slot: its own constants, checked against what the pool was sized for.  Host only; changes nothing in
+// the pool.  (pv_pool_open_with and pv_pool_restore)
+static int pool_slot_constants(const pv_pool *p, float time_ratio, float semis, std::unique_ptr<Derived> &own) {
+    const Core &c = p->core;
+    own.reset(new Derived());
+    pv_config cs = c.d.cfg;
+    cs.time_ratio = time_ratio;
+    cs.pitch_semitones = semis;
+    const int st = derive(cs, *own);
+    if (st != PV_OK) {
+        if (g_last_error.empty()) g_last_error = "stream pool: the engine refuses this pitch / time ratio";
+        return st;
+    }
+    const Derived &d = *own;
+    const char *big = d.hop > p->max_hop ? "input hop" : pool_max_adv(d) > c.chain_max_adv ? "overlap-add advance" : nullptr;
+    if (!big && d.resample &&
+        (pool_res_lds_floats(d) > p->max_res_lds_floats || res_tab_bytes(d) > p->max_res_tab_bytes ||
+         (int)d.sinc.size() > p->max_sinc || (d.interp && d.oversample * (d.filt_len + 1) > p->max_tab4)))
+        big = "resampler set-up";
+    if (big) {
+        g_last_error = std::string("stream pool: this pitch / time ratio's ") + big + " exceeds what the pool was sized for";
+        return PV_ERR_UNSUPPORTED;
+    }
+    return PV_OK;
+}
+
+// A mixed pool's resampling slot: the entry of the table arena with its ratio's tables -- shared with an open slot of
+// the same ratio, or a free entry, uploaded here.  The caller counts the reference.
+static int pool_tab_acquire(pv_pool *p, const Derived &d, int *out) {
+    const Core &c = p->core;
+    int tab = -1;
+    for (size_t i = 0; i < p->tabs.size() && tab < 0; ++i)
+        if (p->tabs[i].refs > 0 && p->tabs[i].num == d.res_num && p->tabs[i].den == d.res_den) tab = (int)i;
+    if (tab < 0) {
+        for (size_t i = 0; i < p->tabs.size() && tab < 0; ++i)
+            if (p->tabs[i].refs == 0) tab = (int)i;
+        // (at most one entry per open slot: a free one exists)
+        std::vector<float4> img(p->tab_stride, make_float4(0, 0, 0, 0));
+        memcpy(img.data(), d.sinc.data(), d.sinc.size() * sizeof(float));
+        float4 *t4 = img.data() + (size_t)(p->max_sinc + 3) / 4;
+        if (d.interp) // (as Core::init expands them)
+            for (int off = 0; off < d.oversample; ++off)
+                for (int j = 0; j < d.filt_len; ++j) {
+                    const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
+                    t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+                }
+        HIPC(hipSetDevice(c.device));
+        // (a free entry may still be read by the in-flight device feeds of the slot that released it)
+        if (const int ds = pool_drain(p)) return ds;
+        HIPC(hipMemcpy(p->d_tabs.p + (size_t)tab * p->tab_stride, img.data(), img.size() * sizeof(float4),
+                       hipMemcpyHostToDevice));
+        p->tabs[(size_t)tab].num = d.res_num;
+        p->tabs[(size_t)tab].den = d.res_den;
+    }
+    *out = tab;
+    return PV_OK;
+}
+
+// Makes slot s an open stream of the given constants with no history (own: a mixed pool's slot's, else null).
+static void pool_slot_begin(pv_pool *p, int32_t s, std::unique_ptr<Derived> own, int tab) {
+    Core &c = p->core;
+    pv_pool::Slot &sl = p->slots[(size_t)s];
+    sl.own_d = std::move(own);
+    sl.d = sl.own_d ? sl.own_d.get() : &c.d;
+    sl.fast = Core::fast_capable_of(*sl.d, c.fast_arith);
+    sl.tab = tab;
+    if (tab >= 0) ++p->tabs[(size_t)tab].refs;
+    sl.lds_floats = sl.d->resample ? pool_res_lds_floats(*sl.d) : 0;
+    sl.tab_bytes = res_tab_bytes(*sl.d);
+    sl.planner.reset(new Planner(*sl.d));
+    sl.chain.reset(new ChainBuilder(*sl.d, c.chain_AR, c.chain_smask));
+    sl.fed = sl.uploaded = sl.slices = 0;
+    sl.acc_half = 0;
+    sl.outq.assign((size_t)c.C, std::vector<float>());
+    sl.outq_head = 0;
+    sl.open = true;
+}
+
+// ---- snapshots (audiomod_pv.h "Stream pool snapshots"; the blob's format: pv_snapshot.h)
+// The pool's side of a blob header: what every slot of this pool shares -- configuration, arithmetic setting and the
+// geometry of the per-row buffers, from the pool's own values.
+static void pool_snap_geometry(const pv_pool *p, snap::Header &h) {
+    const Core &c = p->core;
+    h.sample_rate = c.d.cfg.sample_rate;
+    h.channels = c.C;
+    h.mode = c.d.cfg.mode;
+    h.coremode = c.d.cfg.coremode;
+    h.fftsize = c.d.cfg.fftsize;
+    h.hopsize = c.d.cfg.hopsize;
+    h.arith = c.fast_arith ? PV_ARITH_FAST : PV_ARITH_EXACT;
+    h.phase_stage = phase_mode(c.d);
+    h.N = c.d.N;
+    h.hs = c.d.hs;
+    h.ring = p->ring;
+    h.TR = c.TR;
+    h.HP = c.HP;
+    h.PKP = c.PKP;
+    h.AR = c.chain_AR;
+    h.stream_len = (c.stream.p || p->mix_stream.p) ? c.chain_smask + 1 : 0;
+}
+// the pool's buffer behind a blob's directory entry, and its size in bytes; slot s owns bytes
+// [s * seg_bytes, (s + 1) * seg_bytes) of it (rows [s*C, (s+1)*C) of a [rows][...] buffer, image s of [slot][2][C][AR])
+static char *pool_snap_buffer(const pv_pool *p, int buf, size_t *bytes) {
+    const Core &c = p->core;
+#define PV_SNAP_BUF(b) return *bytes = (b).n * sizeof(*(b).p), reinterpret_cast<char *>((b).p)
+    switch (buf) {
+    case snap::kBufIn: PV_SNAP_BUF(p->d_in);
+    case snap::kBufMag: PV_SNAP_BUF(c.mag);
+    case snap::kBufPhase: PV_SNAP_BUF(c.phase);
+    case snap::kBufOutphase: PV_SNAP_BUF(c.outphase);
+    case snap::kBufPeaks: PV_SNAP_BUF(c.peaks);
+    case snap::kBufNpk: PV_SNAP_BUF(c.npk);
+    case snap::kBufRecs: PV_SNAP_BUF(c.recs);
+    case snap::kBufModes: PV_SNAP_BUF(c.modes);
+    case snap::kBufRot: PV_SNAP_BUF(c.rot);
+    case snap::kBufStPp: PV_SNAP_BUF(c.st_pp);
+    case snap::kBufStPo: PV_SNAP_BUF(c.st_po);
+    case snap::kBufStRot: PV_SNAP_BUF(c.st_rot);
+    case snap::kBufStKind: PV_SNAP_BUF(c.st_kind);
+    case snap::kBufAcc: PV_SNAP_BUF(c.st_acc);
+    case snap::kBufStream:
+        if (c.stream.p) PV_SNAP_BUF(c.stream);
+        PV_SNAP_BUF(p->mix_stream);
+    default: *bytes = 0; return nullptr;
+    }
+#undef PV_SNAP_BUF
+}
+// The directory a blob of this pool has must be the pool's buffers exactly: every entry's buffer exists and holds
+// `cap` slots of the entry's size.  (A disagreement would be a bug in seg_bytes; checked before any launch, because
+// the kernel takes its bounds from these sizes.)
+static int pool_snap_check_buffers(const pv_pool *p, const snap::Header &h) {
+    for (int b = 0; b < snap::kBufCount; ++b) {
+        size_t have = 0;
+        const char *base = pool_snap_buffer(p, b, &have);
+        const int64_t per = snap::seg_bytes(h, b);
+        if ((per != 0) != (base != nullptr) || (base && (size_t)per * (size_t)p->cap != have) || (per & 3)) {
+            g_last_error = "stream pool: internal: snapshot directory entry " + std::to_string(b) + " does not match the pool's buffer";
+            return PV_ERR_UNSUPPORTED;
+        }
+    }
+    return PV_OK;
+}
+
 static int pool_open_at(pv_pool *p, float time_ratio, float semis, int32_t *slot) {
     g_last_error.clear();
     plan_reason_clear();
@@ -2692,86 +2843,31 @@ static int pool_open_at(pv_pool *p, float time_ratio, float semis, int32_t *slot
     std::unique_ptr<Derived> own;
     int tab = -1;
     if (p->mixed) {
-        own.reset(new Derived());
-        pv_config cs = c.d.cfg;
-        cs.time_ratio = time_ratio;
-        cs.pitch_semitones = semis;
-        const int st = derive(cs, *own);
-        if (st != PV_OK) {
-            if (g_last_error.empty()) g_last_error = "stream pool: the engine refuses this pitch / time ratio";
-            return st;
-        }
-        const Derived &d = *own;
-        const char *big = d.hop > p->max_hop ? "input hop" : pool_max_adv(d) > c.chain_max_adv ? "overlap-add advance" : nullptr;
-        if (!big && d.resample &&
-            (pool_res_lds_floats(d) > p->max_res_lds_floats || res_tab_bytes(d) > p->max_res_tab_bytes ||
-             (int)d.sinc.size() > p->max_sinc || (d.interp && d.oversample * (d.filt_len + 1) > p->max_tab4)))
-            big = "resampler set-up";
-        if (big) {
-            g_last_error = std::string("stream pool: this pitch / time ratio's ") + big + " exceeds what the pool was sized for";
-            return PV_ERR_UNSUPPORTED;
-        }
-        if (d.resample) { // the ratio's tables: shared with an open slot of the same ratio, or uploaded into a free entry
-            for (size_t i = 0; i < p->tabs.size() && tab < 0; ++i)
-                if (p->tabs[i].refs > 0 && p->tabs[i].num == d.res_num && p->tabs[i].den == d.res_den) tab = (int)i;
-            if (tab < 0) {
-                for (size_t i = 0; i < p->tabs.size() && tab < 0; ++i)
-                    if (p->tabs[i].refs == 0) tab = (int)i;
-                // (at most one entry per open slot: a free one exists)
-                std::vector<float4> img(p->tab_stride, make_float4(0, 0, 0, 0));
-                memcpy(img.data(), d.sinc.data(), d.sinc.size() * sizeof(float));
-                float4 *t4 = img.data() + (size_t)(p->max_sinc + 3) / 4;
-                if (d.interp) // (as Core::init expands them)
-                    for (int off = 0; off < d.oversample; ++off)
-                        for (int j = 0; j < d.filt_len; ++j) {
-                            const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
-                            t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
-                        }
-                HIPC(hipSetDevice(c.device));
-                // (a free entry may still be read by the in-flight device feeds of the slot that released it)
-                if (const int ds = pool_drain(p)) return ds;
-                HIPC(hipMemcpy(p->d_tabs.p + (size_t)tab * p->tab_stride, img.data(), img.size() * sizeof(float4),
-                               hipMemcpyHostToDevice));
-                p->tabs[(size_t)tab].num = d.res_num;
-                p->tabs[(size_t)tab].den = d.res_den;
-            }
-        }
+        int st = pool_slot_constants(p, time_ratio, semis, own);
+        if (st != PV_OK) return st;
+        if (own->resample && (st = pool_tab_acquire(p, *own, &tab)) != PV_OK) return st;
     }
     HIPC(hipSetDevice(c.device));
-    // a fresh stream: what pv_create and Core::reset_state zero, for the slot's rows only (stream-ordered before its
-    // first launch)
-    const size_t r0 = (size_t)s * c.C, nr = (size_t)c.C;
-    auto clear = [&](void *base, size_t elem, size_t pitch) -> int {
-        if (!base) return PV_OK;
-        HIPC(hipMemsetAsync(static_cast<char *>(base) + r0 * pitch * elem, 0, nr * pitch * elem, p->stream));
-        return PV_OK;
-    };
+    // A fresh stream: the slot's rows of EVERY buffer the kernels carry between calls are zeroed (stream-ordered before
+    // its first launch).  A stream's continuation reads only what pv_create and Core::reset_state zero -- the input
+    // ring, st_pp, st_po, st_kind, the accumulator images -- and what the stream itself has written; the other rows are
+    // cleared so that what a slot holds is a function of its own stream's history alone, whoever used the slot before
+    // (a snapshot copies whole rows: pv_pool_save).
     int st = PV_OK;
-    if (st == PV_OK) st = clear(p->d_in.p, sizeof(float), (size_t)p->ring);
-    if (st == PV_OK) st = clear(c.st_pp.p, sizeof(float), (size_t)c.d.hs);
-    if (st == PV_OK) st = clear(c.st_po.p, sizeof(float), (size_t)c.d.hs);
-    if (st == PV_OK) st = clear(c.st_kind.p, sizeof(int32_t), 1);
-    if (st == PV_OK) st = clear(c.st_acc.p, sizeof(float), 2 * (size_t)c.chain_AR); // [slot][2][C][AR]
+    for (int b = 0; b < snap::kBufCount && st == PV_OK; ++b) {
+        size_t have = 0;
+        char *base = pool_snap_buffer(p, b, &have);
+        const size_t per = base ? have / (size_t)p->cap : 0;
+        if (!per) continue;
+        const hipError_t e = hipMemsetAsync(base + (size_t)s * per, 0, per, p->stream);
+        if (e != hipSuccess) st = hip_fail(e, "hipMemsetAsync", __LINE__);
+    }
     if (st != PV_OK) {
         p->poisoned = st;
         p->poison_reason = g_last_error;
         return st;
     }
-    pv_pool::Slot &sl = p->slots[(size_t)s];
-    sl.own_d = std::move(own);
-    sl.d = sl.own_d ? sl.own_d.get() : &c.d;
-    sl.fast = Core::fast_capable_of(*sl.d, c.fast_arith);
-    sl.tab = tab;
-    if (tab >= 0) ++p->tabs[(size_t)tab].refs;
-    sl.lds_floats = sl.d->resample ? pool_res_lds_floats(*sl.d) : 0;
-    sl.tab_bytes = res_tab_bytes(*sl.d);
-    sl.planner.reset(new Planner(*sl.d));
-    sl.chain.reset(new ChainBuilder(*sl.d, c.chain_AR, c.chain_smask));
-    sl.fed = sl.uploaded = sl.slices = 0;
-    sl.acc_half = 0;
-    sl.outq.assign((size_t)c.C, std::vector<float>());
-    sl.outq_head = 0;
-    sl.open = true;
+    pool_slot_begin(p, s, std::move(own), tab);
     *slot = s;
     return PV_OK;
 }
@@ -3500,6 +3596,324 @@ int pv_pool_plan_feed(pv_pool *p, int32_t count, const int32_t *slots, const int
         }
     }
     for (int32_t i = 0; i < count; ++i) out_frames[i] = frames[(size_t)i];
+    return PV_OK;
+}
+
+// ---------------------------------------------------------------- stream pool snapshots
+static int64_t pool_slot_pending(const pv_pool::Slot &sl) {
+    return sl.outq.empty() ? 0 : (int64_t)(sl.outq[0].size() - sl.outq_head);
+}
+// the header of the slot's blob as pv_pool_save would write it now, sizes included (the host state itself:
+// snap::encode_head)
+static void pool_snap_header(const pv_pool *p, const pv_pool::Slot &sl, snap::Header &h) {
+    h = snap::Header{};
+    pool_snap_geometry(p, h);
+    h.time_ratio = sl.d->cfg.time_ratio;
+    h.pitch_semitones = sl.d->cfg.pitch_semitones;
+    snap::fill_sizes(h, (int32_t)sl.chain->live.size(), pool_slot_pending(sl));
+}
+// the first field in which a blob's pool differs from this one (nullptr: none).  Both sides are pools' own derived
+// values, not creation arguments.
+static const char *pool_snap_mismatch(const snap::Header &blob, const snap::Header &pool) {
+#define PV_SNAP_FIELD(f, name) \
+    if (blob.f != pool.f) return name
+    PV_SNAP_FIELD(sample_rate, "sample rate");
+    PV_SNAP_FIELD(channels, "channels");
+    PV_SNAP_FIELD(mode, "mode");
+    PV_SNAP_FIELD(coremode, "coremode");
+    PV_SNAP_FIELD(N, "FFT size");
+    PV_SNAP_FIELD(hopsize, "hop setting");
+    PV_SNAP_FIELD(arith, "arithmetic setting");
+    PV_SNAP_FIELD(phase_stage, "phase stage");
+    PV_SNAP_FIELD(hs, "half spectrum");
+    PV_SNAP_FIELD(ring, "input-ring length");
+    PV_SNAP_FIELD(TR, "plane-ring slots (TR)");
+    PV_SNAP_FIELD(HP, "plane pitch (HP)");
+    PV_SNAP_FIELD(PKP, "peak-list pitch (PKP)");
+    PV_SNAP_FIELD(AR, "accumulator-ring length");
+    PV_SNAP_FIELD(stream_len, "stream-ring length");
+#undef PV_SNAP_FIELD
+    return nullptr;
+}
+
+// room for a call's staging (device and page-locked image) and segment table; a failed allocation leaves the pool as
+// usable as it was
+static int pool_snap_reserve(pv_pool *p, size_t stage_bytes, size_t nsegs) {
+    int st;
+    if (stage_bytes > p->d_snap.n || stage_bytes > p->h_snap.n) {
+        size_t capn = p->d_snap.n ? p->d_snap.n : (size_t)1 << 20;
+        while (capn < stage_bytes) capn *= 2;
+        if ((st = p->d_snap.alloc_on(capn, p->stream)) != PV_OK) {
+            p->d_snap.release();
+            return st;
+        }
+        if ((st = p->h_snap.alloc(capn)) != PV_OK) {
+            p->h_snap.n = 0;
+            return st;
+        }
+    }
+    if (nsegs > p->h_seg.n || !p->seg_dev) {
+        size_t capn = p->h_seg.n ? p->h_seg.n : 256;
+        while (capn < nsegs) capn *= 2;
+        p->seg_dev = nullptr;
+        if ((st = p->h_seg.alloc(capn)) != PV_OK) {
+            p->h_seg.n = 0;
+            return st;
+        }
+        void *dp = nullptr;
+        HIPC(hipHostGetDevicePointer(&dp, p->h_seg.p, 0));
+        p->seg_dev = static_cast<const SnapSeg *>(dp);
+    }
+    return PV_OK;
+}
+
+// The call's segment table: entry i of `slot_of` is staged at i * snap::device_bytes(h), its buffers in directory
+// order, each padded to 16 bytes -- a blob's payload as it is.  Returns the number of segments; *parts: workgroups per
+// segment (about 64 KB each, and about 4096 workgroups in all at the most).
+static int pool_snap_table(pv_pool *p, const snap::Header &h, const std::vector<int32_t> &slot_of, int *parts) {
+    int n = 0;
+    int64_t largest = 0;
+    const int64_t dev = snap::device_bytes(h);
+    for (size_t i = 0; i < slot_of.size(); ++i) {
+        int64_t off = (int64_t)i * dev;
+        for (int b = 0; b < snap::kBufCount; ++b)
+            if (const int64_t per = snap::seg_bytes(h, b)) {
+                p->h_seg.p[n++] = SnapSeg{b, 0, (int64_t)slot_of[i] * per, off, per};
+                off += snap::pad16(per);
+                if (per > largest) largest = per;
+            }
+    }
+    int w = (int)std::min<int64_t>(64, (largest + 65535) / 65536);
+    while (w > 1 && (int64_t)w * n > 4096) w /= 2;
+    *parts = w < 1 ? 1 : w;
+    return n;
+}
+static SnapArgs pool_snap_args(const pv_pool *p, bool to_stage) {
+    SnapArgs a{};
+    for (int b = 0; b < snap::kBufCount; ++b) {
+        size_t have;
+        a.bufs[b] = pool_snap_buffer(p, b, &have);
+    }
+    a.segs = p->seg_dev;
+    a.stage = p->d_snap.p;
+    a.to_stage = to_stage ? 1 : 0;
+    return a;
+}
+static_assert(snap::kBufCount <= kSnapBufs, "SnapArgs holds every buffer of a blob");
+
+int64_t pv_pool_snapshot_bytes(const pv_pool *p, int32_t slot) {
+    if (!pool_slot_ok(p, slot)) return -1;
+    snap::Header h;
+    pool_snap_header(p, p->slots[(size_t)slot], h);
+    return (int64_t)h.total_bytes;
+}
+
+int pv_pool_save(pv_pool *p, int32_t count, const int32_t *slots, void *const *blobs, const int64_t *capacity,
+                 int64_t *bytes) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p || count < 0 || (count > 0 && (!slots || !blobs || !capacity || !bytes))) {
+        g_last_error = "stream pool save: a NULL argument";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (p->poisoned) {
+        g_last_error = "pool unusable after an earlier failure: " + p->poison_reason;
+        return p->poisoned;
+    }
+    Core &c = p->core;
+    std::vector<snap::Header> hd((size_t)count);
+    {
+        std::vector<char> seen((size_t)p->cap, 0);
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t s = slots[i];
+            std::string bad = !pool_slot_ok(p, s) ? "is not open" : seen[(size_t)s] ? "is listed twice" : !blobs[i] ? "has no blob" : "";
+            if (bad.empty()) {
+                pool_snap_header(p, p->slots[(size_t)s], hd[(size_t)i]);
+                if (capacity[i] < (int64_t)hd[(size_t)i].total_bytes)
+                    bad = "needs " + std::to_string(hd[(size_t)i].total_bytes) + " bytes, the blob has " + std::to_string(capacity[i]);
+            }
+            if (!bad.empty()) {
+                g_last_error = "stream pool save: slot " + std::to_string(s) + " " + bad;
+                return PV_ERR_INVALID_ARG;
+            }
+            seen[(size_t)s] = 1;
+        }
+    }
+    if (count == 0) return PV_OK;
+    int st;
+    if ((st = pool_snap_check_buffers(p, hd[0])) != PV_OK) return st;
+    HIPC(hipSetDevice(c.device));
+    if ((st = pool_drain(p)) != PV_OK) return st; // (the device feeds in flight come first, as for pv_pool_feed)
+    const int64_t dev = snap::device_bytes(hd[0]);
+    if ((st = pool_snap_reserve(p, (size_t)dev * (size_t)count, (size_t)count * snap::kBufCount)) != PV_OK) return st;
+    auto fail = [&](int code) {
+        p->poisoned = code;
+        p->poison_reason = g_last_error.empty() ? pv_strerror(code) : g_last_error;
+        return code;
+    };
+    int parts = 1;
+    const int nsegs = pool_snap_table(p, hd[0], std::vector<int32_t>(slots, slots + count), &parts);
+    launch_pool_snapshot(pool_snap_args(p, true), nsegs, parts, p->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(p->h_snap.p, p->d_snap.p, (size_t)dev * (size_t)count, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) return fail(hip_fail(e, "stream pool save", __LINE__));
+    p->last_launches = 1;
+    for (int32_t i = 0; i < count; ++i) {
+        const pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+        snap::Header &h = hd[(size_t)i];
+        snap::HostState hs;
+        hs.plan = sl.planner->save();
+        hs.fed = sl.fed, hs.uploaded = sl.uploaded, hs.slices = sl.slices;
+        hs.acc_half = sl.acc_half;
+        hs.any_upper_skip = sl.chain->any_upper_skip;
+        for (const ChainBuilder::Live &f : sl.chain->live) hs.live.push_back(snap::LiveFrame{f.P, f.flags, 0});
+        std::vector<const float *> pend((size_t)c.C, nullptr);
+        for (int ch = 0; ch < c.C && !sl.outq.empty(); ++ch) pend[(size_t)ch] = sl.outq[(size_t)ch].data() + sl.outq_head;
+        uint8_t *blob = static_cast<uint8_t *>(blobs[i]);
+        snap::encode_head(h, hs, pend.data(), pool_slot_pending(sl), blob);
+        uint8_t *q = blob + snap::payload_offset(h);
+        memcpy(q, p->h_snap.p + (size_t)i * (size_t)dev, (size_t)dev);
+        for (int b = 0; b < snap::kBufCount; ++b) // (the padding between segments is zeros whatever the staging held)
+            if (const int64_t per = snap::seg_bytes(h, b)) {
+                memset(q + per, 0, (size_t)(snap::pad16(per) - per));
+                q += snap::pad16(per);
+            }
+        snap::seal(blob, h);
+    }
+    for (int32_t i = 0; i < count; ++i) bytes[i] = (int64_t)hd[(size_t)i].total_bytes;
+    return PV_OK;
+}
+
+int pv_pool_restore(pv_pool *p, int32_t count, const void *const *blobs, const int64_t *bytes, int32_t *slots) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p || count < 0 || (count > 0 && (!blobs || !bytes || !slots))) {
+        g_last_error = "stream pool restore: a NULL argument";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (p->poisoned) {
+        g_last_error = "pool unusable after an earlier failure: " + p->poison_reason;
+        return p->poisoned;
+    }
+    if (count == 0) return PV_OK;
+    Core &c = p->core;
+    // 1. everything that can refuse, on the host: the blobs, the pool's compatibility, the slots' constants, free slots
+    std::vector<snap::Header> hd((size_t)count);
+    std::vector<std::unique_ptr<Derived>> own((size_t)count);
+    snap::Header geo{};
+    pool_snap_geometry(p, geo);
+    for (int32_t i = 0; i < count; ++i) {
+        snap::Header &h = hd[(size_t)i];
+        const std::string who = "stream pool restore: blob " + std::to_string(i) + ": ";
+        if (const char *why = snap::validate(blobs[i], bytes[i], &h)) {
+            g_last_error = who + why;
+            return PV_ERR_INVALID_ARG;
+        }
+        if (const char *field = pool_snap_mismatch(h, geo)) {
+            g_last_error = who + "this pool cannot host it: its " + field + " differs";
+            return PV_ERR_INVALID_ARG;
+        }
+        if (!pool_in_range(p->range, h.time_ratio, h.pitch_semitones)) {
+            g_last_error = who + (p->mixed ? "its pitch / time ratio lies outside the pool's range"
+                                           : "a pool from pv_pool_create takes only its configuration's pitch / time ratio");
+            return PV_ERR_INVALID_ARG;
+        }
+        if (p->mixed) {
+            const int st = pool_slot_constants(p, h.time_ratio, h.pitch_semitones, own[(size_t)i]);
+            if (st != PV_OK) {
+                g_last_error = who + g_last_error;
+                return st;
+            }
+        }
+    }
+    std::vector<int32_t> dst;
+    for (int32_t s = 0; s < p->cap && (int32_t)dst.size() < count; ++s)
+        if (!p->slots[(size_t)s].open) dst.push_back(s);
+    if ((int32_t)dst.size() < count) {
+        g_last_error = "stream pool restore: " + std::to_string(count) + " blobs, " + std::to_string(dst.size()) + " free slots";
+        return PV_ERR_INVALID_ARG;
+    }
+    int st;
+    if ((st = pool_snap_check_buffers(p, hd[0])) != PV_OK) return st;
+    // 2. the device side
+    HIPC(hipSetDevice(c.device));
+    if ((st = pool_drain(p)) != PV_OK) return st;
+    const int64_t dev = snap::device_bytes(hd[0]); // (the same for every blob: it follows from the geometry)
+    if ((st = pool_snap_reserve(p, (size_t)dev * (size_t)count, (size_t)count * snap::kBufCount)) != PV_OK) return st;
+    // a mixed pool's table arena, as pv_pool_open_with: each entry is held from here on, so that two blobs of one new
+    // ratio share it
+    std::vector<int> tab((size_t)count, -1);
+    for (int32_t i = 0; i < count; ++i)
+        if (own[(size_t)i] && own[(size_t)i]->resample) {
+            if ((st = pool_tab_acquire(p, *own[(size_t)i], &tab[(size_t)i])) != PV_OK) {
+                for (int32_t j = 0; j < i; ++j)
+                    if (tab[(size_t)j] >= 0) --p->tabs[(size_t)tab[(size_t)j]].refs;
+                return st;
+            }
+            ++p->tabs[(size_t)tab[(size_t)i]].refs;
+        }
+    for (int32_t i = 0; i < count; ++i)
+        memcpy(p->h_snap.p + (size_t)i * (size_t)dev, static_cast<const uint8_t *>(blobs[i]) + snap::payload_offset(hd[(size_t)i]),
+               (size_t)dev);
+    auto fail = [&](int code) {
+        p->poisoned = code;
+        p->poison_reason = g_last_error.empty() ? pv_strerror(code) : g_last_error;
+        return code;
+    };
+    int parts = 1;
+    const int nsegs = pool_snap_table(p, hd[0], dst, &parts);
+    hipError_t e = hipMemcpyAsync(p->d_snap.p, p->h_snap.p, (size_t)dev * (size_t)count, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) {
+        launch_pool_snapshot(pool_snap_args(p, false), nsegs, parts, p->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) return fail(hip_fail(e, "stream pool restore", __LINE__));
+    p->last_launches = 1;
+    // 3. the slots' host state
+    for (int32_t i = 0; i < count; ++i) {
+        const snap::Header &h = hd[(size_t)i];
+        if (tab[(size_t)i] >= 0) --p->tabs[(size_t)tab[(size_t)i]].refs; // (pool_slot_begin counts it for the slot)
+        pool_slot_begin(p, dst[(size_t)i], std::move(own[(size_t)i]), tab[(size_t)i]);
+        pv_pool::Slot &sl = p->slots[(size_t)dst[(size_t)i]];
+        snap::HostState hs;
+        snap::decode_host(blobs[i], h, hs);
+        sl.planner->restore(hs.plan);
+        for (const snap::LiveFrame &f : hs.live) sl.chain->live.push_back(ChainBuilder::Live{f.P, f.flags});
+        sl.chain->any_upper_skip = hs.any_upper_skip;
+        sl.fed = hs.fed, sl.uploaded = hs.uploaded, sl.slices = hs.slices;
+        sl.acc_half = hs.acc_half;
+        for (int ch = 0; ch < c.C && h.pending > 0; ++ch) {
+            sl.outq[(size_t)ch].resize((size_t)h.pending);
+            memcpy(sl.outq[(size_t)ch].data(), snap::pending_of(blobs[i], h, ch), (size_t)h.pending * sizeof(float));
+        }
+    }
+    for (int32_t i = 0; i < count; ++i) slots[i] = dst[(size_t)i];
+    return PV_OK;
+}
+
+int pv_pool_blob_info(const void *blob, int64_t bytes, pv_pool_blob_desc *info) {
+    g_last_error.clear();
+    snap::Header h;
+    if (!info) {
+        g_last_error = "stream pool blob: no result structure";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (const char *why = snap::validate(blob, bytes, &h)) {
+        g_last_error = std::string("stream pool blob: ") + why;
+        return PV_ERR_INVALID_ARG;
+    }
+    *info = pv_pool_blob_desc{};
+    info->version = (int32_t)h.version;
+    info->arithmetic = h.arith;
+    info->cfg = pv_config{h.sample_rate, h.channels, h.time_ratio, h.pitch_semitones, h.mode, h.coremode, h.fftsize, h.hopsize};
+    info->time_ratio = h.time_ratio;
+    info->pitch_semitones = h.pitch_semitones;
+    info->slices = h.slices;
+    info->pending_frames = h.pending;
+    info->payload_bytes = snap::device_bytes(h);
+    info->total_bytes = (int64_t)h.total_bytes;
     return PV_OK;
 }
 

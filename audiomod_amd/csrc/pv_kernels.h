@@ -357,6 +357,23 @@ struct PoolEgress {
 };
 void launch_pool_egress_i16(const float *arena, int16_t *dst, int C, const PoolEgress *ents, int nents, int max_n,
                             hipStream_t st);
+// Snapshots (pv_pool_save / pv_pool_restore): one launch moves a table of segments between the pool's per-row buffers
+// and one contiguous staging buffer.  A segment is `bytes` bytes (a multiple of 4) at bufs[buf] + buf_off on the one side
+// and at stage + stage_off on the other; to_stage != 0 gathers into the staging buffer, 0 scatters out of it.  16-byte
+// copies where both addresses and the length are multiples of 16, else 4-byte ones.  grid (segments, parts): the parts
+// of a segment stride through it together.  The table may live in mapped host memory (each workgroup reads one entry).
+constexpr int kSnapBufs = 16;
+struct SnapSeg {
+    int32_t buf, pad;
+    int64_t buf_off, stage_off, bytes;
+};
+struct SnapArgs {
+    char *bufs[kSnapBufs];
+    const SnapSeg *segs;
+    char *stage;
+    int to_stage;
+};
+void launch_pool_snapshot(const SnapArgs &a, int nsegs, int parts, hipStream_t st);
 // Each returns false (launching nothing) when the configuration has no per-slot kernel or it does not fit;
 // launch = false: only that check (pv_pool_create asks it once).
 bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st);

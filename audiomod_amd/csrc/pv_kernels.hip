@@ -4186,6 +4186,29 @@ void launch_pool_egress_i16(const float *arena, int16_t *dst, int C, const PoolE
     hipLaunchKernelGGL(pv_pool_egress_i16_kernel, dim3((max_n + 255) / 256, C, nents), dim3(256), 0, st, arena, dst, ents);
 }
 
+// snapshot gather / scatter (SnapSeg): pure streaming, no arithmetic and no LDS; workgroup (x, y) is part y of segment x
+__global__ __launch_bounds__(256) void pv_pool_snapshot_kernel(const SnapArgs a) {
+    const SnapSeg s = a.segs[blockIdx.x];
+    char *const b = a.bufs[s.buf] + s.buf_off, *const g = a.stage + s.stage_off;
+    const char *__restrict__ src = a.to_stage ? b : g;
+    char *__restrict__ dst = a.to_stage ? g : b;
+    const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nt = (int64_t)gridDim.y * 256;
+    if ((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)s.bytes) & 15) == 0) {
+        const float4 *__restrict__ s4 = reinterpret_cast<const float4 *>(src);
+        float4 *__restrict__ d4 = reinterpret_cast<float4 *>(dst);
+        for (int64_t i = tid; i < (s.bytes >> 4); i += nt) d4[i] = s4[i];
+    } else {
+        const uint32_t *__restrict__ s1 = reinterpret_cast<const uint32_t *>(src);
+        uint32_t *__restrict__ d1 = reinterpret_cast<uint32_t *>(dst);
+        for (int64_t i = tid; i < (s.bytes >> 2); i += nt) d1[i] = s1[i];
+    }
+}
+
+void launch_pool_snapshot(const SnapArgs &a, int nsegs, int parts, hipStream_t st) {
+    if (nsegs <= 0) return;
+    hipLaunchKernelGGL(pv_pool_snapshot_kernel, dim3(nsegs, parts < 1 ? 1 : parts), dim3(256), 0, st, a);
+}
+
 __device__ __forceinline__ AnalyzeArgs pool_view(const AnalyzeArgs &a, const PoolSlot &ps) {
     AnalyzeArgs v = a;
     const int64_t r = ps.row0;

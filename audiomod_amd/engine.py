@@ -70,6 +70,12 @@ class PoolRange(C.Structure):
                 ("max_time_ratio", C.c_float)]
 
 
+class BlobDesc(C.Structure):
+    _fields_ = [("version", C.c_int32), ("arithmetic", C.c_int32), ("cfg", Config), ("time_ratio", C.c_float),
+                ("pitch_semitones", C.c_float), ("slices", C.c_int64), ("pending_frames", C.c_int64),
+                ("payload_bytes", C.c_int64), ("total_bytes", C.c_int64)]
+
+
 class ChainRung(C.Structure):
     _fields_ = [("nc", C.c_int32), ("plain_core", C.c_int32), ("resample", C.c_int32), ("fast", C.c_int32),
                 ("wave_bound", C.c_int32), ("reciprocal_wden", C.c_int32)]
@@ -174,6 +180,11 @@ def lib():
                                       C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     L.pv_pool_create_mixed.argtypes = [C.POINTER(Config), C.POINTER(PoolRange), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]
     L.pv_pool_open_with.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_int32)]
+    L.pv_pool_snapshot_bytes.argtypes = [C.c_void_p, C.c_int32]
+    L.pv_pool_snapshot_bytes.restype = C.c_int64
+    L.pv_pool_save.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_pool_restore.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_pool_blob_info.argtypes = [C.c_void_p, C.c_int64, C.POINTER(BlobDesc)]
     i64p = C.POINTER(C.c_int64)
     L.pv_mbatch_layout.argtypes = [C.POINTER(Config), C.POINTER(MixedStream), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, i64p, i64p]
@@ -735,6 +746,18 @@ class HostIO:
         self.close()
 
 
+def blob_info(blob):
+    """Host only (works without a GPU): validates a blob of StreamPool.save() and describes it (pv_pool_blob_info): format
+    version, the stream's configuration, the slot's pitch and time ratio, the arithmetic setting, slices processed,
+    frames of pending output and the payload size.  Raises PvError for anything that is not a valid blob."""
+    b = bytes(blob)
+    d = BlobDesc()
+    _check(lib().pv_pool_blob_info(C.c_char_p(b), len(b), C.byref(d)), "pv_pool_blob_info")
+    out = {k: getattr(d, k) for k, _ in d._fields_ if k != "cfg"}
+    out["cfg"] = {k: getattr(d.cfg, k) for k, _ in Config._fields_}
+    return out
+
+
 class StreamPool:
     """Up to `capacity` independent live streams of one configuration (include/audiomod_pv.h pv_pool_*).  A slot
     behaves bit for bit like a PhaseVocoder / pv_engine of the same configuration fed the same blocks; one feed()
@@ -858,8 +881,45 @@ class StreamPool:
         _check(self.L.pv_pool_last_timing(self.h, C.byref(h), C.byref(w)), "pv_pool_last_timing")
         return h.value, w.value
 
+    def snapshot_bytes(self, slot):
+        """The exact size of the slot's blob in its current state."""
+        n = self.L.pv_pool_snapshot_bytes(self.h, int(slot))
+        if n < 0:
+            raise PvError(f"pv_pool_snapshot_bytes: slot {slot} is not open")
+        return n
+
+    def save(self, slot):
+        """The slot's stream as a blob (bytes) that restore() of a compatible pool -- this one included -- continues bit
+        for bit (pv_pool_save).  A list of slots gives a list of blobs, saved with one kernel and one copy.  Leaves the
+        slots as they are."""
+        many = not np.isscalar(slot)
+        slots = np.ascontiguousarray(slot if many else [slot], dtype=np.int32)
+        cap = np.array([max(self.L.pv_pool_snapshot_bytes(self.h, int(s)), 1) for s in slots], np.int64)
+        bufs = [np.empty(int(n), np.uint8) for n in cap]
+        ptrs = (C.c_void_p * len(bufs))(*[b.ctypes.data for b in bufs])
+        got = np.zeros(len(bufs), np.int64)
+        _check(self.L.pv_pool_save(self.h, len(slots), slots.ctypes.data, ptrs, cap.ctypes.data, got.ctypes.data),
+               "pv_pool_save")
+        blobs = [b[:int(n)].tobytes() for b, n in zip(bufs, got)]
+        return blobs if many else blobs[0]
+
+    def restore(self, blob):
+        """Opens a fresh slot (the lowest free one) that continues the stream saved in `blob`; returns the slot
+        (pv_pool_restore).  A list of blobs gives a list of slots, all or none."""
+        many = not isinstance(blob, (bytes, bytearray, memoryview))
+        blobs = [bytes(b) for b in (blob if many else [blob])]
+        ptrs = (C.c_char_p * len(blobs))(*blobs)
+        sizes = np.array([len(b) for b in blobs], np.int64)
+        slots = np.full(len(blobs), -1, np.int32)
+        _check(self.L.pv_pool_restore(self.h, len(blobs), ptrs, sizes.ctypes.data, slots.ctypes.data), "pv_pool_restore")
+        return [int(s) for s in slots] if many else int(slots[0])
+
+    def fork(self, slot):
+        """A second slot of this pool with the slot's history: both return the same bits from here on."""
+        return self.restore(self.save(int(slot)))
+
     def last_launches(self):
-        """Kernels launched by the last feed() or feed_device()."""
+        """Kernels launched by the last feed() or feed_device(); 1 after a save() or restore() of any number of slots."""
         n = C.c_int32(0)
         _check(self.L.pv_pool_last_launches(self.h, C.byref(n)), "pv_pool_last_launches")
         return n.value
