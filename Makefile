@@ -35,8 +35,8 @@ SHIM := audiomod_amd/lib/shim_demo
 $(SHIM): tools/shim_demo.cc $(LIB) include/dafx/phasevocoder.h include/dafx/modbase.h
 	$(HIPCC) -O2 -std=c++17 -Iinclude -Iinclude/dafx tools/shim_demo.cc -Laudiomod_amd/lib -laudiomod_pv -Wl,-rpath,'$$ORIGIN' -o $@
 CLI := audiomod_amd/lib/audiomod-pv-exe
-$(CLI): audiomod_amd/csrc/audiomod_pv_cli.cc $(LIB) include/dafx/phasevocoder.h include/dafx/modbase.h
-	$(HIPCC) -O2 -std=c++17 -Iinclude -Iinclude/dafx audiomod_amd/csrc/audiomod_pv_cli.cc -Laudiomod_amd/lib -laudiomod_pv -Wl,-rpath,'$$ORIGIN' -o $@
+$(CLI): audiomod_amd/csrc/audiomod_pv_cli.cc audiomod_amd/csrc/pv_cli_batch.h $(LIB) include/dafx/phasevocoder.h include/dafx/modbase.h
+	$(HIPCC) -O2 -std=c++17 -Iinclude -Iinclude/dafx -Iaudiomod_amd/csrc audiomod_amd/csrc/audiomod_pv_cli.cc -Laudiomod_amd/lib -laudiomod_pv -Wl,-rpath,'$$ORIGIN' -o $@
 all: $(SHIM) $(CLI)
 
 SBENCH := audiomod_amd/lib/stream_bench

@@ -3968,6 +3968,16 @@ struct pv_mbatch {
     bool has_runs_knob = false; // AUDIOMOD_PV_CHAIN_RUNS
     int runs_knob = 0;
     double plan_us = 0, host_us = 0, device_us = 0; // the last create or redraw (pv_mbatch_last_build_timing)
+    // The PCM wire (pv_mbatch_run_pcm): nothing here exists before the first PCM run; buffers grow and never shrink.
+    struct Pcm {
+        DevBuf<float> stage;           // the run's float input, then (from out_base) its float output
+        DevBuf<pv::MbPcmJob> jobs;     // n ingest jobs, then n egress jobs
+        DevBuf<char> d_in, d_out;      // pv_mbatch_run_pcm_host's device PCM buffers
+        std::vector<int32_t> bits;     // the depths the resident job table was built for (8 ... 32, never empty then)
+        bool resident = false;         // false again after a redraw: the offsets have moved
+        int64_t out_base = 0, in_bytes = 0, out_bytes = 0;
+        int in_blocks = 0, out_blocks = 0;
+    } pcm;
 };
 
 static const char *mb_scope(const pv_config &cfg) {
@@ -4687,6 +4697,7 @@ int pv_mbatch_redraw(pv_mbatch *b, const pv_mbatch_stream *s) {
     b->s = std::move(nb->s);
     b->groups = std::move(nb->groups);
     b->in_floats = nb->in_floats, b->out_floats = nb->out_floats, b->kernel_launches = nb->kernel_launches;
+    b->pcm.resident = false; // (the next PCM run builds its job table for the new offsets)
     b->plan_us = mb_us(t_begin, t_planned), b->host_us = mb_us(t_planned, t_host), b->device_us = mb_us(t_host, t_done);
     return PV_OK;
 }
@@ -4749,6 +4760,190 @@ int pv_mbatch_run(pv_mbatch *b, const float *d_in, float *d_out, void *hip_strea
         if ((rc = mb_launch_group(b, g, d_in, d_out, st)) != PV_OK) return rc;
     HIPC(hipGetLastError());
     return PV_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- mixed batch, PCM wire (audiomod_pv.h)
+static bool mb_pcm_depth_ok(int32_t bits) { return bits == 8 || bits == 16 || bits == 24 || bits == 32; }
+
+// the arguments every PCM entry checks, before any device call
+static int mb_pcm_check(const pv_mbatch *b, const int32_t *in_bits) {
+    g_last_error.clear();
+    if (!b) {
+        g_last_error = "mixed batch PCM: null object";
+        return PV_ERR_INVALID_ARG;
+    }
+    for (size_t i = 0; in_bits && i < b->s.size(); ++i)
+        if (!mb_pcm_depth_ok(in_bits[i])) {
+            g_last_error = "mixed batch PCM: stream " + std::to_string(i) + ": " + std::to_string(in_bits[i]) +
+                           " bits per sample (8, 16, 24 or 32)";
+            return PV_ERR_INVALID_ARG;
+        }
+    return PV_OK;
+}
+
+struct MbPcmLayout {
+    std::vector<int64_t> in_off, out_off;
+    int64_t in_bytes = 0, out_bytes = 0;
+};
+static MbPcmLayout mb_pcm_layout(const pv_mbatch *b, const int32_t *in_bits) {
+    MbPcmLayout l;
+    const int64_t C = b->cfg.channels;
+    for (size_t i = 0; i < b->s.size(); ++i) {
+        l.in_off.push_back(l.in_bytes);
+        l.out_off.push_back(l.out_bytes);
+        l.in_bytes += (b->s[i].frames * C * ((in_bits ? in_bits[i] : 16) / 8) + 15) & ~(int64_t)15;
+        l.out_bytes += (b->s[i].plan.out_frames * C * 2 + 15) & ~(int64_t)15;
+    }
+    return l;
+}
+
+// The staging buffers and the job table for `in_bits`.  Nothing to do when the table for these depths is resident;
+// otherwise the device is synchronised first (an earlier run may still use what is replaced) and again afterwards
+// (the fills and the upload are on the default stream, which nothing orders against a non-blocking one).
+static int mb_pcm_prepare(pv_mbatch *b, const int32_t *in_bits) {
+    pv_mbatch::Pcm &p = b->pcm;
+    const size_t n = b->s.size();
+    std::vector<int32_t> bits(n, 16);
+    if (in_bits) bits.assign(in_bits, in_bits + n);
+    if (p.resident && bits == p.bits) return PV_OK;
+    const int C = b->cfg.channels;
+    const MbPcmLayout l = mb_pcm_layout(b, bits.data());
+    std::vector<MbPcmJob> jobs(2 * n);
+    const int64_t out_base = (b->in_floats + 63) & ~(int64_t)63;
+    int64_t blocks[2] = {0, 0};
+    for (size_t i = 0; i < n; ++i) {
+        const pv_mbatch::Stream &t = b->s[i];
+        jobs[i] = MbPcmJob{l.in_off[i], t.in_off, t.frames, C, bits[i] / 8, (int32_t)blocks[0], 0};
+        // (planar offsets count from the pointer the launch is given: the stage's input part, its output part)
+        jobs[n + i] = MbPcmJob{l.out_off[i], t.out_off, t.plan.out_frames, C, 2, (int32_t)blocks[1], 0};
+        blocks[0] += mb_pcm_blocks(t.frames, C);
+        blocks[1] += mb_pcm_blocks(t.plan.out_frames, C);
+        if (blocks[0] > 0x7fffffff || blocks[1] > 0x7fffffff) {
+            g_last_error = "mixed batch PCM: more conversion tiles than one launch's grid holds";
+            return PV_ERR_UNSUPPORTED;
+        }
+    }
+    HIPC(hipDeviceSynchronize());
+    int st;
+    const size_t need = (size_t)(out_base + b->out_floats);
+    if ((need > p.stage.n || !p.stage.p) && (st = p.stage.alloc(need)) != PV_OK) return st;
+    if ((jobs.size() > p.jobs.n || !p.jobs.p) && (st = p.jobs.alloc(jobs.size())) != PV_OK) return st;
+    p.resident = false;
+    HIPC(hipMemcpy(p.jobs.p, jobs.data(), jobs.size() * sizeof(MbPcmJob), hipMemcpyHostToDevice));
+    HIPC(hipDeviceSynchronize());
+    p.bits = bits, p.out_base = out_base, p.in_bytes = l.in_bytes, p.out_bytes = l.out_bytes;
+    p.in_blocks = (int)blocks[0], p.out_blocks = (int)blocks[1];
+    p.resident = true;
+    return PV_OK;
+}
+
+extern "C" {
+
+int pv_mbatch_pcm_layout(const pv_mbatch *b, const int32_t *in_bits, int64_t *in_byte_off, int64_t *out_byte_off,
+                         int64_t *in_bytes, int64_t *out_bytes) {
+    const int st = mb_pcm_check(b, in_bits);
+    if (st != PV_OK) return st;
+    const MbPcmLayout l = mb_pcm_layout(b, in_bits);
+    for (size_t i = 0; i < b->s.size(); ++i) {
+        if (in_byte_off) in_byte_off[i] = l.in_off[i];
+        if (out_byte_off) out_byte_off[i] = l.out_off[i];
+    }
+    if (in_bytes) *in_bytes = l.in_bytes;
+    if (out_bytes) *out_bytes = l.out_bytes;
+    return PV_OK;
+}
+
+int pv_mbatch_run_pcm(pv_mbatch *b, const int32_t *in_bits, const void *d_pcm_in, void *d_pcm_out, void *hip_stream) {
+    int st = mb_pcm_check(b, in_bits);
+    if (st != PV_OK) return st;
+    if (!d_pcm_in || (!d_pcm_out && b->out_floats > 0) || (((uintptr_t)d_pcm_in | (uintptr_t)d_pcm_out) & 15)) {
+        g_last_error = "mixed batch PCM: the PCM buffers must be non-null and 16-byte aligned";
+        return PV_ERR_INVALID_ARG;
+    }
+    HIPC(hipSetDevice(b->device));
+    if ((st = mb_pcm_prepare(b, in_bits)) != PV_OK) return st;
+    const pv_mbatch::Pcm &p = b->pcm;
+    const int n = (int)b->s.size();
+    hipStream_t hs = (hipStream_t)hip_stream;
+    launch_mb_pcm_ingest(p.jobs.p, n, p.in_blocks, d_pcm_in, p.stage.p, hs);
+    if ((st = pv_mbatch_run(b, p.stage.p, p.stage.p + p.out_base, hip_stream)) != PV_OK) return st;
+    launch_mb_pcm_egress(p.jobs.p + n, n, p.out_blocks, p.stage.p + p.out_base, d_pcm_out, hs);
+    HIPC(hipGetLastError());
+    return PV_OK;
+}
+
+int pv_mbatch_debug_pcm_kernel(pv_mbatch *b, int which, const void *d_pcm_in, void *d_pcm_out, void *hip_stream) {
+    g_last_error.clear();
+    if (!b || !b->pcm.resident || (which != 0 && which != 1) || (which == 0 ? !d_pcm_in : !d_pcm_out) ||
+        (((uintptr_t)d_pcm_in | (uintptr_t)d_pcm_out) & 15))
+        return PV_ERR_INVALID_ARG;
+    HIPC(hipSetDevice(b->device));
+    const pv_mbatch::Pcm &p = b->pcm;
+    const int n = (int)b->s.size();
+    if (which == 0) launch_mb_pcm_ingest(p.jobs.p, n, p.in_blocks, d_pcm_in, p.stage.p, (hipStream_t)hip_stream);
+    else launch_mb_pcm_egress(p.jobs.p + n, n, p.out_blocks, p.stage.p + p.out_base, d_pcm_out, (hipStream_t)hip_stream);
+    HIPC(hipGetLastError());
+    return PV_OK;
+}
+
+int pv_mbatch_run_pcm_host(pv_mbatch *b, const int32_t *in_bits, const void *h_pcm_in, void *h_pcm_out) {
+    int st = mb_pcm_check(b, in_bits);
+    if (st != PV_OK) return st;
+    if (!h_pcm_in || (!h_pcm_out && b->out_floats > 0)) {
+        g_last_error = "mixed batch PCM: null host buffer";
+        return PV_ERR_INVALID_ARG;
+    }
+    HIPC(hipSetDevice(b->device));
+    if ((st = mb_pcm_prepare(b, in_bits)) != PV_OK) return st;
+    pv_mbatch::Pcm &p = b->pcm;
+    if ((size_t)p.in_bytes > p.d_in.n || !p.d_in.p || (size_t)p.out_bytes > p.d_out.n || !p.d_out.p) {
+        HIPC(hipDeviceSynchronize());
+        if (((size_t)p.in_bytes > p.d_in.n || !p.d_in.p) && (st = p.d_in.alloc((size_t)p.in_bytes)) != PV_OK) return st;
+        if (((size_t)p.out_bytes > p.d_out.n || !p.d_out.p) && (st = p.d_out.alloc((size_t)p.out_bytes)) != PV_OK) return st;
+        HIPC(hipDeviceSynchronize());
+    }
+    HIPC(hipMemcpyAsync(p.d_in.p, h_pcm_in, (size_t)p.in_bytes, hipMemcpyHostToDevice, nullptr));
+    if ((st = pv_mbatch_run_pcm(b, in_bits, p.d_in.p, p.d_out.p, nullptr)) != PV_OK) return st;
+    if (p.out_bytes > 0) HIPC(hipMemcpyAsync(h_pcm_out, p.d_out.p, (size_t)p.out_bytes, hipMemcpyDeviceToHost, nullptr));
+    HIPC(hipStreamSynchronize(nullptr));
+    return PV_OK;
+}
+
+// one clip through a production kernel, from and to host buffers
+static int mb_pcm_debug(const void *h_src, size_t src_bytes, void *h_dst, size_t dst_bytes, int32_t bps, int32_t channels,
+                        int64_t frames, bool ingest, int device) {
+    g_last_error.clear();
+    if (channels < 1 || frames < 0 || (frames > 0 && (!h_src || !h_dst))) return PV_ERR_INVALID_ARG;
+    if (frames == 0) return PV_OK;
+    const int64_t blocks = mb_pcm_blocks(frames, channels);
+    if (blocks > 0x7fffffff) return PV_ERR_INVALID_ARG;
+    HIPC(hipSetDevice(device));
+    DevBuf<char> src, dst;
+    DevBuf<MbPcmJob> job;
+    int st;
+    if ((st = src.alloc(src_bytes)) != PV_OK || (st = dst.alloc(dst_bytes)) != PV_OK || (st = job.alloc(1)) != PV_OK) return st;
+    const MbPcmJob jb{0, 0, frames, channels, bps, 0, 0};
+    HIPC(hipMemcpy(job.p, &jb, sizeof jb, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(src.p, h_src, src_bytes, hipMemcpyHostToDevice));
+    if (ingest) launch_mb_pcm_ingest(job.p, 1, (int)blocks, src.p, reinterpret_cast<float *>(dst.p), nullptr);
+    else launch_mb_pcm_egress(job.p, 1, (int)blocks, reinterpret_cast<const float *>(src.p), dst.p, nullptr);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpy(h_dst, dst.p, dst_bytes, hipMemcpyDeviceToHost));
+    return PV_OK;
+}
+
+int pv_debug_pcm_ingest(const void *pcm, int32_t bits, int32_t channels, int64_t frames, float *planar, int device) {
+    if (!mb_pcm_depth_ok(bits)) return PV_ERR_INVALID_ARG;
+    const size_t samples = (size_t)(frames > 0 && channels > 0 ? frames * channels : 0);
+    return mb_pcm_debug(pcm, samples * (size_t)(bits / 8), planar, samples * sizeof(float), bits / 8, channels, frames, true,
+                        device);
+}
+
+int pv_debug_pcm_egress(const float *planar, int32_t channels, int64_t frames, int16_t *pcm, int device) {
+    const size_t samples = (size_t)(frames > 0 && channels > 0 ? frames * channels : 0);
+    return mb_pcm_debug(planar, samples * sizeof(float), pcm, samples * 2, 2, channels, frames, false, device);
 }
 
 } // extern "C"

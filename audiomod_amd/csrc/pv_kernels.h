@@ -455,4 +455,20 @@ int mb_build_otab_blocks(int ntiles);
 void launch_mb_build_wden(const MbWdenJob *jobs, int njobs, int nblocks, char *desc, const float *window, hipStream_t st);
 void launch_mb_build_otab(const MbOtabJob *jobs, int njobs, int nblocks, char *desc, hipStream_t st);
 
+// The PCM wire (pv_mbatch_run_pcm): interleaved little-endian PCM clips of differing length <-> the packed planar
+// float layout above, one launch each way per run.  One job per clip; a job owns the blocks from first_block up to
+// the next job's, one block per kMbPcmTile interleaved samples.  Every clip starts on a 16-byte boundary of the PCM
+// buffer (pv_mbatch_pcm_layout), whose base must itself be 16-byte aligned.
+struct MbPcmJob {
+    int64_t pcm_off;    // byte offset of the clip's [frames][channels] samples
+    int64_t planar_off; // float offset of its [channels][frames]
+    int64_t frames;
+    int32_t channels;
+    int32_t bps;        // bytes per sample on the PCM side: 1 ... 4 (ingest), 2 (egress)
+    int32_t first_block, pad;
+};
+int64_t mb_pcm_blocks(int64_t frames, int channels);
+void launch_mb_pcm_ingest(const MbPcmJob *jobs, int njobs, int nblocks, const void *pcm, float *planar, hipStream_t st);
+void launch_mb_pcm_egress(const MbPcmJob *jobs, int njobs, int nblocks, const float *planar, void *pcm, hipStream_t st);
+
 } // namespace pv

@@ -30,6 +30,7 @@
 #include "pv_sincos.h"
 #include "pv_wavefft.h"
 #include "pv_wire.h"
+#include "pv_pcm.h"
 #include "audiomod_pv.h" // PV_WIRE_*
 
 #include <hip/hip_runtime.h>
@@ -5027,5 +5028,136 @@ void launch_mb_build_otab(const MbOtabJob *jobs, int njobs, int nblocks, char *d
 }
 int mb_build_wden_blocks(int total) { return (total / 4 + kMbBuildThreads - 1) / kMbBuildThreads; }
 int mb_build_otab_blocks(int ntiles) { return (int)(((int64_t)ntiles * kTileOut / 2 + kMbBuildThreads - 1) / kMbBuildThreads); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Mixed batch, PCM wire (pv_mbatch_run_pcm): clip i's interleaved little-endian [frames][C] of 8 / 16 / 24 / 32 bits
+// to its planar float [C][frames], and planar float to interleaved int16, with pv_pcm.h's conversions.  One launch
+// each way serves every clip: block b belongs to the last job whose first_block is at or before it (mb_build_job)
+// and moves one tile of kMbPcmTile interleaved samples, counted from the clip's start, through the LDS.
+//   PCM side: a clip starts on a 16-byte boundary and a tile is a whole number of 16-sample groups (one, two, three
+//   or four 16-byte pieces at 8 / 16 / 24 / 32 bits), so every tile starts on a sample and on a 16-byte boundary: a
+//   lane moves one piece, neighbouring lanes neighbouring pieces.  Only what is left of a clip's last tile after its
+//   last whole piece goes byte by byte (ingest) or sample by sample (egress); the padding behind it is neither read
+//   nor written.
+//   Planar side: the tile's samples of channel c are frames [f_lo, f_hi) of row c, which starts wherever the tight
+//   packing puts it.  Lanes walk a row: single floats up to the first 16-byte boundary, float4 from there, single
+//   floats for the rest (as pv_pool_snapshot_kernel: wide only where address and length allow).
+// The transposition is the LDS index: the tile lies there in interleaved order (raw bytes on the way in, int16 on the
+// way out), sample (f, c) at f * C + c - s0; with an odd C a frame straddles pieces and tiles, which this never sees.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kMbPcmThreads = 256;
+constexpr int kMbPcmTile = 4096;
+static_assert(kMbPcmTile % 16 == 0, "a tile is whole 16-sample groups");
+
+// frames f with f * C + c < x, for x in [0, frames * C]
+__device__ __forceinline__ int64_t mb_pcm_rows_below(int64_t x, int c, int C) { return x <= c ? 0 : (x - c + C - 1) / C; }
+
+template <int BPS> __device__ __forceinline__ float mb_pcm_lds_load(const unsigned char *raw, int idx) {
+    if (BPS == 1) return pv_pcm_u8_to_f32(raw[idx]);
+    if (BPS == 2) return pv_pcm_i16_to_f32((int16_t)reinterpret_cast<const uint16_t *>(raw)[idx]);
+    if (BPS == 4) return pv_pcm_i32_to_f32((int32_t)reinterpret_cast<const uint32_t *>(raw)[idx]);
+    return pv_pcm_load(raw + 3 * idx, 3);
+}
+
+// the planar side of one ingest tile: samples [s0, s0 + ns) of the clip, lying in `raw`
+template <int BPS>
+__device__ __forceinline__ void mb_pcm_ingest_rows(const unsigned char *raw, float *__restrict__ dst, const int64_t frames,
+                                                   const int C, const int64_t s0, const int ns) {
+    const int tid = (int)threadIdx.x;
+    for (int c = 0; c < C; ++c) {
+        const int64_t f_lo = mb_pcm_rows_below(s0, c, C), f_hi = mb_pcm_rows_below(s0 + ns, c, C);
+        const int n = (int)(f_hi - f_lo);
+        if (n <= 0) continue;
+        float *__restrict__ row = dst + (int64_t)c * frames + f_lo;
+        const int l0 = (int)(f_lo * C + c - s0);
+        int head = (int)((0 - ((uintptr_t)row >> 2)) & 3);
+        head = head < n ? head : n;
+        const int quads = (n - head) >> 2;
+        if (tid < head) row[tid] = mb_pcm_lds_load<BPS>(raw, l0 + tid * C);
+        for (int q = tid; q < quads; q += kMbPcmThreads) {
+            const int i = head + 4 * q, l = l0 + i * C;
+            float4 v;
+            v.x = mb_pcm_lds_load<BPS>(raw, l), v.y = mb_pcm_lds_load<BPS>(raw, l + C);
+            v.z = mb_pcm_lds_load<BPS>(raw, l + 2 * C), v.w = mb_pcm_lds_load<BPS>(raw, l + 3 * C);
+            *reinterpret_cast<float4 *>(row + i) = v;
+        }
+        const int i = head + 4 * quads + tid;
+        if (i < n) row[i] = mb_pcm_lds_load<BPS>(raw, l0 + i * C);
+    }
+}
+
+__global__ __launch_bounds__(kMbPcmThreads) void pv_mb_pcm_ingest_kernel(const MbPcmJob *__restrict__ jobs, int njobs,
+                                                                        const unsigned char *__restrict__ pcm,
+                                                                        float *__restrict__ planar) {
+    __shared__ __attribute__((aligned(16))) unsigned char raw[kMbPcmTile * 4];
+    const MbPcmJob jb = mb_build_job(jobs, njobs);
+    const int C = jb.channels, bps = jb.bps, tid = (int)threadIdx.x;
+    const int64_t total = jb.frames * C;
+    const int64_t s0 = ((int64_t)blockIdx.x - jb.first_block) * kMbPcmTile;
+    if (s0 >= total) return;
+    const int ns = (int)(total - s0 < kMbPcmTile ? total - s0 : kMbPcmTile), nbytes = ns * bps;
+    const unsigned char *__restrict__ src = pcm + jb.pcm_off + s0 * bps;
+    const int pieces = nbytes >> 4;
+    for (int p = tid; p < pieces; p += kMbPcmThreads)
+        reinterpret_cast<uint4 *>(raw)[p] = reinterpret_cast<const uint4 *>(src)[p];
+    for (int b = (pieces << 4) + tid; b < nbytes; b += kMbPcmThreads) raw[b] = src[b]; // (fewer than 16 bytes)
+    __syncthreads();
+    float *__restrict__ dst = planar + jb.planar_off;
+    if (bps == 2) mb_pcm_ingest_rows<2>(raw, dst, jb.frames, C, s0, ns);
+    else if (bps == 3) mb_pcm_ingest_rows<3>(raw, dst, jb.frames, C, s0, ns);
+    else if (bps == 4) mb_pcm_ingest_rows<4>(raw, dst, jb.frames, C, s0, ns);
+    else mb_pcm_ingest_rows<1>(raw, dst, jb.frames, C, s0, ns);
+}
+
+__global__ __launch_bounds__(kMbPcmThreads) void pv_mb_pcm_egress_kernel(const MbPcmJob *__restrict__ jobs, int njobs,
+                                                                        const float *__restrict__ planar,
+                                                                        unsigned char *__restrict__ pcm) {
+    __shared__ __attribute__((aligned(16))) int16_t buf[kMbPcmTile];
+    const MbPcmJob jb = mb_build_job(jobs, njobs);
+    const int C = jb.channels, tid = (int)threadIdx.x;
+    const int64_t total = jb.frames * C;
+    const int64_t s0 = ((int64_t)blockIdx.x - jb.first_block) * kMbPcmTile;
+    if (s0 >= total) return;
+    const int ns = (int)(total - s0 < kMbPcmTile ? total - s0 : kMbPcmTile);
+    const float *__restrict__ src = planar + jb.planar_off;
+    for (int c = 0; c < C; ++c) {
+        const int64_t f_lo = mb_pcm_rows_below(s0, c, C), f_hi = mb_pcm_rows_below(s0 + ns, c, C);
+        const int n = (int)(f_hi - f_lo);
+        if (n <= 0) continue;
+        const float *__restrict__ row = src + (int64_t)c * jb.frames + f_lo;
+        const int l0 = (int)(f_lo * C + c - s0);
+        int head = (int)((0 - ((uintptr_t)row >> 2)) & 3);
+        head = head < n ? head : n;
+        const int quads = (n - head) >> 2;
+        if (tid < head) buf[l0 + tid * C] = pv_pcm_f32_to_i16(row[tid]);
+        for (int q = tid; q < quads; q += kMbPcmThreads) {
+            const int i = head + 4 * q, l = l0 + i * C;
+            const float4 v = *reinterpret_cast<const float4 *>(row + i);
+            buf[l] = pv_pcm_f32_to_i16(v.x), buf[l + C] = pv_pcm_f32_to_i16(v.y);
+            buf[l + 2 * C] = pv_pcm_f32_to_i16(v.z), buf[l + 3 * C] = pv_pcm_f32_to_i16(v.w);
+        }
+        const int i = head + 4 * quads + tid;
+        if (i < n) buf[l0 + i * C] = pv_pcm_f32_to_i16(row[i]);
+    }
+    __syncthreads();
+    unsigned char *__restrict__ dst = pcm + jb.pcm_off + s0 * 2;
+    const int pieces = ns >> 3;
+    for (int p = tid; p < pieces; p += kMbPcmThreads)
+        reinterpret_cast<uint4 *>(dst)[p] = reinterpret_cast<const uint4 *>(buf)[p];
+    const int s = (pieces << 3) + tid; // (fewer than 8 samples)
+    if (s < ns) reinterpret_cast<int16_t *>(dst)[s] = buf[s];
+}
+
+int64_t mb_pcm_blocks(int64_t frames, int channels) { return (frames * channels + kMbPcmTile - 1) / kMbPcmTile; }
+void launch_mb_pcm_ingest(const MbPcmJob *jobs, int njobs, int nblocks, const void *pcm, float *planar, hipStream_t st) {
+    if (njobs <= 0 || nblocks <= 0) return;
+    hipLaunchKernelGGL(pv_mb_pcm_ingest_kernel, dim3(nblocks), dim3(kMbPcmThreads), 0, st, jobs, njobs,
+                       static_cast<const unsigned char *>(pcm), planar);
+}
+void launch_mb_pcm_egress(const MbPcmJob *jobs, int njobs, int nblocks, const float *planar, void *pcm, hipStream_t st) {
+    if (njobs <= 0 || nblocks <= 0) return;
+    hipLaunchKernelGGL(pv_mb_pcm_egress_kernel, dim3(nblocks), dim3(kMbPcmThreads), 0, st, jobs, njobs, planar,
+                       static_cast<unsigned char *>(pcm));
+}
 
 } // namespace pv

@@ -209,6 +209,12 @@ def lib():
     L.pv_mbatch_last_build_timing.argtypes = [C.c_void_p, f64p, f64p, f64p]
     L.pv_mbatch_debug_descriptors.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int64]
     L.pv_mbatch_debug_descriptors.restype = C.c_int64
+    L.pv_mbatch_pcm_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64p, i64p]
+    L.pv_mbatch_run_pcm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_mbatch_run_pcm_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_mbatch_debug_pcm_kernel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pv_debug_pcm_ingest.argtypes =[C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int]
+    L.pv_debug_pcm_egress.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int]
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -681,6 +687,130 @@ class MixedBatch:
     def split(self, d_out):
         """[channels, out_frames_i] views of the packed output, one per stream."""
         return [d_out[o:o + self.channels * f].view(self.channels, f) for o, f in zip(self.out_offsets, self.out_frames)]
+
+    # -- the PCM wire (include/audiomod_pv.h pv_mbatch_run_pcm): clips as WAV files hold them, converted on the device
+    def _bits(self, bits):
+        """None (16 bits for every clip), one depth for all, or one per stream: the list and the C ABI's argument"""
+        n = len(self.streams)
+        if bits is None:
+            return [16] * n, None
+        lst = [int(bits)] * n if np.isscalar(bits) else [int(b) for b in bits]
+        assert len(lst) == n
+        return lst, (C.c_int32 * n)(*lst)
+
+    def pcm_layout(self, bits=None):
+        """Host only: dict of in_offsets, out_offsets (bytes, one per stream; multiples of 16) and in_bytes, out_bytes
+        for input depths `bits` (8 / 16 / 24 / 32 per stream; output is always int16)."""
+        n = len(self.streams)
+        _, arr = self._bits(bits)
+        a = [np.zeros(n, np.int64) for _ in range(2)]
+        nin, nout = C.c_int64(0), C.c_int64(0)
+        _check(self.L.pv_mbatch_pcm_layout(self.h, arr, a[0].ctypes.data, a[1].ctypes.data, C.byref(nin), C.byref(nout)),
+               "pv_mbatch_pcm_layout")
+        return dict(in_offsets=[int(x) for x in a[0]], out_offsets=[int(x) for x in a[1]], in_bytes=nin.value,
+                    out_bytes=nout.value)
+
+    def pack_pcm_host(self, clips, bits=None):
+        """The PCM input buffer as a numpy uint8 array: clips are integer arrays [frames_i][channels] -- uint8 values
+        for 8 bits, int16 for 16, sign-extended int32 for 24 and 32 -- written interleaved, little-endian, at the
+        layout's offsets (the padding between clips is zero)."""
+        lst, _ = self._bits(bits)
+        lay = self.pcm_layout(bits)
+        buf = np.zeros(lay["in_bytes"], np.uint8)
+        for (frames, _, _), x, b, off in zip(self.streams, clips, lst, lay["in_offsets"]):
+            buf[off:off + frames * self.channels * (b // 8)] = pcm_bytes(np.asarray(x).reshape(frames, self.channels), b)
+        return buf
+
+    def pack_pcm(self, clips, bits=None):
+        """pack_pcm_host's buffer as a 1-D uint8 CUDA tensor."""
+        import torch
+        return torch.from_numpy(self.pack_pcm_host(clips, bits)).to(f"cuda:{self.device}")
+
+    def alloc_pcm_out(self):
+        import torch
+        n = self.pcm_layout()["out_bytes"]
+        return torch.zeros(max(n, 16), dtype=torch.uint8, device=f"cuda:{self.device}")[:n]
+
+    def run_pcm(self, d_pcm_in, bits=None, d_pcm_out=None, stream=None):
+        """d_pcm_in: 1-D uint8 CUDA tensor in pcm_layout(bits)'s layout; returns the 1-D uint8 output tensor (int16
+        samples, split_pcm()).  Ingest kernel, the run, egress kernel on one stream.  Asynchronous."""
+        import torch
+        _, arr = self._bits(bits)
+        lay = self.pcm_layout(bits)
+        assert d_pcm_in.is_cuda and d_pcm_in.dtype == torch.uint8 and d_pcm_in.is_contiguous() and d_pcm_in.dim() == 1
+        assert d_pcm_in.numel() == lay["in_bytes"]
+        if d_pcm_out is None:
+            d_pcm_out = self.alloc_pcm_out()
+        assert d_pcm_out.is_cuda and d_pcm_out.dtype == torch.uint8 and d_pcm_out.is_contiguous() and d_pcm_out.dim() == 1
+        assert d_pcm_out.numel() == lay["out_bytes"]
+        s = stream if stream is not None else torch.cuda.current_stream(d_pcm_in.device)
+        _check(self.L.pv_mbatch_run_pcm(self.h, arr, C.c_void_p(d_pcm_in.data_ptr()), C.c_void_p(d_pcm_out.data_ptr()),
+                                        C.c_void_p(s.cuda_stream)), "pv_mbatch_run_pcm")
+        return d_pcm_out
+
+    def split_pcm(self, d_pcm_out):
+        """int16 [out_frames_i, channels] views of run_pcm's (or, for a numpy array, run_pcm_host's) output."""
+        offs = self.pcm_layout()["out_offsets"]
+        if isinstance(d_pcm_out, np.ndarray):
+            return [d_pcm_out[o:o + 2 * self.channels * f].view("<i2").reshape(f, self.channels)
+                    for o, f in zip(offs, self.out_frames)]
+        import torch
+        return [d_pcm_out[o:o + 2 * self.channels * f].view(torch.int16).view(f, self.channels)
+                for o, f in zip(offs, self.out_frames)]
+
+    def run_pcm_host(self, h_pcm_in, bits=None, h_pcm_out=None):
+        """Host buffers (numpy uint8 arrays or CPU uint8 tensors; page-locked ones are copied at PCIe rate): one copy
+        in, the run, one copy out, synchronous.  Returns h_pcm_out (a numpy array unless one was passed)."""
+        _, arr = self._bits(bits)
+        lay = self.pcm_layout(bits)
+        if h_pcm_out is None:
+            h_pcm_out = np.zeros(max(lay["out_bytes"], 1), np.uint8)[:lay["out_bytes"]]
+
+        def ptr(x, nbytes):
+            if isinstance(x, np.ndarray):
+                assert x.dtype == np.uint8 and x.flags.c_contiguous and x.size == nbytes
+                return x.ctypes.data
+            assert (not x.is_cuda) and x.is_contiguous() and x.numel() * x.element_size() == nbytes
+            return x.data_ptr()
+
+        _check(self.L.pv_mbatch_run_pcm_host(self.h, arr, C.c_void_p(ptr(h_pcm_in, lay["in_bytes"])),
+                                             C.c_void_p(ptr(h_pcm_out, lay["out_bytes"]))), "pv_mbatch_run_pcm_host")
+        return h_pcm_out
+
+
+def pcm_bytes(x, bits):
+    """Integer samples (uint8 values for 8 bits, int16 for 16, sign-extended 24- or 32-bit values otherwise) as the
+    little-endian byte string of a WAV file's data chunk, in the array's own (C) order: a flat uint8 array."""
+    x = np.ascontiguousarray(x)
+    if bits == 8:
+        return x.astype(np.uint8).reshape(-1)
+    if bits == 16:
+        return x.astype("<i2").reshape(-1).view(np.uint8)
+    b = x.astype("<i4").reshape(-1).view(np.uint8).reshape(-1, 4)
+    if bits == 24:
+        return np.ascontiguousarray(b[:, :3]).reshape(-1)
+    assert bits == 32
+    return b.reshape(-1)
+
+
+def debug_pcm_ingest(x, bits, device=0):
+    """Diagnostics: the ingest kernel on one clip.  x: integer samples [frames][channels] (see pcm_bytes); returns the
+    float32 [channels][frames] the kernel writes."""
+    x = np.asarray(x)
+    frames, ch = x.shape
+    raw = np.ascontiguousarray(pcm_bytes(x, bits))
+    out = np.zeros((ch, frames), np.float32)
+    _check(lib().pv_debug_pcm_ingest(raw.ctypes.data, bits, ch, frames, out.ctypes.data, device), "pv_debug_pcm_ingest")
+    return out
+
+
+def debug_pcm_egress(planar, device=0):
+    """Diagnostics: the egress kernel on one clip.  planar: float32 [channels][frames]; returns int16 [frames][channels]."""
+    planar = np.ascontiguousarray(planar, np.float32)
+    ch, frames = planar.shape
+    out = np.zeros((frames, ch), np.int16)
+    _check(lib().pv_debug_pcm_egress(planar.ctypes.data, ch, frames, out.ctypes.data, device), "pv_debug_pcm_egress")
+    return out
 
 
 class HostIO:

@@ -484,6 +484,46 @@ int pv_mbatch_last_build_timing(const pv_mbatch *b, double *plan_us, double *hos
 #define PV_MB_DESC_OTAB 1
 int64_t pv_mbatch_debug_descriptors(const pv_mbatch *b, int32_t stream, int which, void *out, int64_t max_bytes);
 
+/* PCM wire of the mixed batch: the clips as WAV files hold them -- interleaved little-endian PCM, [frames_i][C] of
+ * 8 (unsigned), 16, 24 or 32 bits in, [out_frames_i][C] of 16 bits out -- converted on the device by two kernels
+ * (one launch each per run, whatever the number of clips) with the reference WAV reader's and writer's conversions:
+ *   in : 8 bit (p - 128) / 128, 16 bit s / 32768, 24 bit s / 8388608, 32 bit s / 2147483648 rounded to float once
+ *   out: saturate(x * 32768, -32768, 32767) truncated toward zero
+ * so d_pcm_out holds, for every clip, the writer's conversion of what pv_mbatch_run writes for the reader's
+ * conversion of d_pcm_in, bit for bit, under either pv_set_arithmetic setting.
+ *   in_bits : [nstreams] 8, 16, 24 or 32 per clip; NULL = 16 for all.  Anything else is PV_ERR_INVALID_ARG, from
+ *             every entry below and before any device call.
+ *   pv_mbatch_pcm_layout   : host only.  Clip i's input starts at byte in_byte_off[i] and its output at
+ *                            out_byte_off[i]: clips lie in stream order, each rounded up to the next multiple of 16
+ *                            bytes, so every offset is a multiple of 16; in_bytes / out_bytes are the buffers' sizes
+ *                            (padding of the last clip included).  Every output pointer may be NULL.  The layout
+ *                            follows the object's current draw (pv_mbatch_redraw changes it).
+ *   pv_mbatch_run_pcm      : device buffers, 16-byte aligned.  Enqueues on `hip_stream`: the ingest kernel, exactly
+ *                            what pv_mbatch_run enqueues, the egress kernel; does not synchronise, and takes its
+ *                            input from whatever was enqueued on that stream before it (pv_mbatch_run's ordering).
+ *                            The kernels neither read nor write the padding bytes between clips.  The float buffers
+ *                            in between (in_floats + out_floats) and the kernels' job table belong to the object:
+ *                            made by the first PCM run, grown -- never shrunk -- when a redraw needs more.  Only a
+ *                            call that finds no table for its in_bits (the first one, one with other depths, the
+ *                            first after a redraw) or too small a buffer waits for the device and uploads; any
+ *                            other call copies nothing from the host and waits for nothing.
+ *   pv_mbatch_run_pcm_host : host buffers of in_bytes / out_bytes (page-locked, pv_host_alloc, for the copies to run
+ *                            at PCIe rate).  One copy in, the run, one copy out, one wait: synchronous, nothing
+ *                            overlaps.  The device PCM buffers belong to the object.  The copy out covers the whole
+ *                            buffer: padding bytes of h_pcm_out are overwritten (with zeros). */
+int pv_mbatch_pcm_layout(const pv_mbatch *b, const int32_t *in_bits, int64_t *in_byte_off, int64_t *out_byte_off,
+                         int64_t *in_bytes, int64_t *out_bytes);
+int pv_mbatch_run_pcm(pv_mbatch *b, const int32_t *in_bits, const void *d_pcm_in, void *d_pcm_out, void *hip_stream);
+int pv_mbatch_run_pcm_host(pv_mbatch *b, const int32_t *in_bits, const void *h_pcm_in, void *h_pcm_out);
+/* Diagnostics: the two production kernels on one clip, from and to host buffers, so that the conversions can be swept
+ * value by value: pcm is [frames][channels] (of `bits` bits on the way in, int16 on the way out), planar
+ * [channels][frames]. */
+int pv_debug_pcm_ingest(const void *pcm, int32_t bits, int32_t channels, int64_t frames, float *planar, int device);
+int pv_debug_pcm_egress(const float *planar, int32_t channels, int64_t frames, int16_t *pcm, int device);
+/* ... and one of the two kernels alone as the object's last PCM run launched it (which = 0: ingest from d_pcm_in into
+ * the object's float buffer; 1: egress from it into d_pcm_out), for timing; PV_ERR_INVALID_ARG before a PCM run. */
+int pv_mbatch_debug_pcm_kernel(pv_mbatch *b, int which, const void *d_pcm_in, void *d_pcm_out, void *hip_stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Host-staged many-stream job.  The reference's callers hold their audio in host memory (planar
  * float buffers filled from 16-bit WAV data: main/main.cc:152-162,484-491; main/wavfile.cc:733-755,
