@@ -1492,6 +1492,16 @@ static void census_append_at_exit() {
                          (long long)n);
                 out += line;
             }
+        static const char *const forms[] = {"ring", "step", "fused", "stream"};
+        static const int bs[4] = {1, 3, 4, 8};
+        for (int form = 0; form < 4; ++form)
+            for (int b : bs) {
+                const int64_t n = chain_census_count(PV_CENSUS_PHASE, set, form, b, 0, 0);
+                if (n <= 0) continue;
+                snprintf(line, sizeof line, "phase set=%s form=%s b=%d count=%lld\n", kCensusSetName[set], forms[form], b,
+                         (long long)n);
+                out += line;
+            }
     }
     if (out.empty()) return;
     if (FILE *f = fopen(g_census_file.c_str(), "a")) { // one write per process: lines of concurrent processes stay whole

@@ -1517,6 +1517,9 @@ int seq_threads(int PKP) {
 }
 __host__ __device__ size_t seq_lds_bytes(const SeqArgs &a) { return sizeof(float) * ((size_t)2 * a.PKP + a.hs) + sizeof(uint16_t) * a.PKP; }
 
+// (the census of the launchers' choices, below: a = form, b = ring depth or peaks per lane)
+static void census_phase(int set, int form, int b);
+
 void launch_seq(const SeqArgs &a, hipStream_t st) {
     const size_t lds = seq_lds_bytes(a);
     if (a.narrow && a.PKP <= 3 * 1024) {
@@ -1524,6 +1527,7 @@ void launch_seq(const SeqArgs &a, hipStream_t st) {
         // a CU beside the fused kernel's workgroup
         int nt = ((a.PKP + 2) / 3 + 63) & ~63;
         if (nt > 1024) nt = 1024;
+        census_phase(0, kPhaseFormStep, 3);
         launch_big_lds<pv_seq_kernel<3>>(dim3(a.rows), dim3(nt), lds, st, a);
         return;
     }
@@ -1542,6 +1546,7 @@ void launch_seq(const SeqArgs &a, hipStream_t st) {
     const int D = depth ? (depth <= 4 ? 4 : 8) : (a.rows <= 96 ? 8 : 4);
     const size_t ring_lds = ((lds + 15) & ~(size_t)15) + (size_t)D * nt * sizeof(PeakRec);
     if (!no_ring && a.PKP <= nt && ring_lds <= kMaxDynLds) {
+        census_phase(0, kPhaseFormRing, D);
         if (D == 4) {
             launch_big_lds<pv_seq_ring_kernel<4>>(dim3(a.rows), dim3(nt), ring_lds, st, a);
         } else {
@@ -1549,6 +1554,7 @@ void launch_seq(const SeqArgs &a, hipStream_t st) {
         }
         return;
     }
+    census_phase(0, kPhaseFormStep, 1);
     launch_big_lds<pv_seq_kernel<1>>(dim3(a.rows), dim3(nt), lds, st, a);
 }
 
@@ -1560,6 +1566,7 @@ bool launch_phase(const MatchArgs &m, const SeqArgs &a, hipStream_t st) {
     const size_t match_l = (size_t)(nt / 64) * match_wave_lds(m.hs, m.PKP);
     const size_t lds = seq_l > match_l ? seq_l : match_l;
     if (a.PKP > nt || lds > kMaxDynLds || a.narrow) return false;
+    census_phase(0, kPhaseFormFused, D);
     launch_big_lds<pv_phase_kernel<D>>(dim3(a.rows), dim3(nt), lds, st, m, a);
     return true;
 }
@@ -3264,6 +3271,8 @@ static constexpr int kCensusNc = 4, kCensusCore = 5; // NC 256 ... 2048; kPlainC
 static std::atomic<uint64_t> g_census_chain[PV_CENSUS_SETS][kCensusNc][kCensusCore][2][2];
 static std::atomic<uint64_t> g_census_res[PV_CENSUS_SETS][2][2];
 static std::atomic<uint64_t> g_census_ana[PV_CENSUS_SETS][kCensusNc][2];
+static std::atomic<uint64_t> g_census_phase[PV_CENSUS_SETS][kPhaseForms][4];
+static int census_phase_index(int b) { return b == 1 ? 0 : b == 3 ? 1 : b == 4 ? 2 : b == 8 ? 3 : -1; }
 static int census_nc_index(int nc) { return nc == 256 ? 0 : nc == 512 ? 1 : nc == 1024 ? 2 : nc == 2048 ? 3 : -1; }
 static inline void census_chain(int set, int nc, int plain_core, int res, bool fast) {
     if (!g_census_on.load(std::memory_order_relaxed)) return;
@@ -3277,11 +3286,16 @@ static inline void census_analyze(int set, int nc, bool split) {
     if (!g_census_on.load(std::memory_order_relaxed)) return;
     g_census_ana[set][census_nc_index(nc)][split ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
 }
+static void census_phase(int set, int form, int b) {
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    g_census_phase[set][form][census_phase_index(b)].fetch_add(1, std::memory_order_relaxed);
+}
 void chain_census_enable(bool on) {
     g_census_on.store(false, std::memory_order_relaxed);
     for (auto &a : g_census_chain) for (auto &b : a) for (auto &c : b) for (auto &d : c) for (auto &e : d) e.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_res) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_ana) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
+    for (auto &a : g_census_phase) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     g_census_on.store(on, std::memory_order_relaxed);
 }
 int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
@@ -3297,6 +3311,9 @@ int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
     case 2:
         if (census_nc_index(a) < 0 || !flag(b)) return -1;
         return (int64_t)g_census_ana[set][census_nc_index(a)][b].load(std::memory_order_relaxed);
+    case 3:
+        if (a < 0 || a >= kPhaseForms || census_phase_index(b) < 0) return -1;
+        return (int64_t)g_census_phase[set][a][census_phase_index(b)].load(std::memory_order_relaxed);
     default: return -1;
     }
 }
@@ -3913,6 +3930,7 @@ bool lds_starts_at_zero() {
 
 void launch_stream(const StreamArgs &s, hipStream_t st) {
     const size_t lds = stream_lds_bytes(s);
+    if (s.coremode == 1) census_phase(0, kPhaseFormStream, 1); // (seq_role<1> on the kernel's 512 threads)
     if (s.aa.tb.nc == 1024) {
         launch_big_lds<pv_stream_kernel<1024>>(dim3(1), dim3(kStreamThreads), lds, st, s);
     } else {
@@ -4318,6 +4336,7 @@ bool pool_phase_supported(int hs, int PKP) { return PKP <= seq_threads(PKP) && p
 
 bool launch_pool_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, hipStream_t st) {
     if (!pool_phase_supported(a.hs, a.PKP)) return false;
+    census_phase(1, kPhaseFormFused, kPoolSeqDepth);
     launch_big_lds<pv_pool_phase_kernel<kPoolSeqDepth>>(dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
                        pool_phase_lds(a.hs, a.PKP), st, m, a, p);
     return true;
@@ -4553,6 +4572,7 @@ __global__ __launch_bounds__(1024) void pv_pmix_phase_kernel(const MatchArgs m, 
 
 bool launch_pmix_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
     if (!pool_phase_supported(a.hs, a.PKP)) return false;
+    census_phase(2, kPhaseFormFused, kPoolSeqDepth);
     launch_big_lds<pv_pmix_phase_kernel<kPoolSeqDepth>>(dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)),
                        pool_phase_lds(a.hs, a.PKP), st, m, a, p, q);
     return true;
@@ -4811,6 +4831,7 @@ static size_t mb_seq_lds(const SeqArgs &a) {
 }
 bool launch_mb_seq(const SeqArgs &a, const PoolLaunch &p, const PoolParams *q, hipStream_t st) {
     if (a.PKP > seq_threads(a.PKP) || mb_seq_lds(a) > kMaxDynLds) return false;
+    census_phase(3, kPhaseFormRing, kMbSeqDepth);
     launch_big_lds<pv_mb_seq_kernel<kMbSeqDepth>>(dim3(a.rows, p.nslots), dim3(seq_threads(a.PKP)), mb_seq_lds(a), st, a, p, q);
     return true;
 }

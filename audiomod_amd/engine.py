@@ -275,6 +275,24 @@ def chain_census_read():
     return chain, res, ana
 
 
+PHASE_FORMS = ("ring", "step", "fused", "stream")  # PV_PHASE_FORM_*: the forms of the phase-locked stage
+
+
+def phase_census_read():
+    """The non-zero keys of the census' fourth kind, the phase-locked stage: {(set, form, b): launches} with `set` one
+    of CENSUS_SETS ("batch" counts the batch path and the single-stream engine), `form` one of PHASE_FORMS and b the
+    ring's depth (4 / 8) or, for "step" and "stream", the peaks one lane holds (1 / 3)."""
+    count = lib().pv_debug_chain_census_count
+    out = {}
+    for i, name in enumerate(CENSUS_SETS):
+        for f, form in enumerate(PHASE_FORMS):
+            for b in (1, 3, 4, 8):
+                n = count(3, i, f, b, 0, 0)
+                if n > 0:
+                    out[(name, form, b)] = n
+    return out
+
+
 def chain_rung(arith, channels=2, **config):
     """Host only (works without a GPU): the rung of the fused ladder a configuration gets under `arith` (ARITH_FAST /
     ARITH_EXACT), as a dict of nc, plain_core, resample, fast, wave_bound and reciprocal_wden (include/audiomod_pv.h

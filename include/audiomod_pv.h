@@ -555,6 +555,9 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
  *                        argument: 0 for an all-modes launch whatever the arithmetic setting)
  *   PV_CENSUS_RESAMPLE : slot-table resampler (pool / pmix / mb sets): a = free-form kernel, b = interpolated table
  *   PV_CENSUS_ANALYZE  : slot-table analysis (pool / pmix / mb sets): a = NC, b = the two-wave split kernel
+ *   PV_CENSUS_PHASE    : the phase-locked stage (core mode 1): a = form (PV_PHASE_FORM_*), b = the ring's depth (4 / 8)
+ *                        or, for the forms without a ring, the peaks one lane holds (1 / 3).  The batch set counts the
+ *                        batch path and the single-stream engine; c and d are ignored
  * Process-wide and off by default (a launch then tests one flag).  pv_debug_chain_census(on) clears the counts and
  * switches counting on or off; pv_debug_chain_census_count returns a key's count, -1 for a key that does not exist.
  * If the environment variable AUDIOMOD_PV_CHAIN_CENSUS names a file when the library is loaded, the census is on from
@@ -563,6 +566,11 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
 #define PV_CENSUS_CHAIN 0
 #define PV_CENSUS_RESAMPLE 1
 #define PV_CENSUS_ANALYZE 2
+#define PV_CENSUS_PHASE 3
+#define PV_PHASE_FORM_RING 0   /* match kernel, then the chain kernel with an LDS ring of b steps */
+#define PV_PHASE_FORM_STEP 1   /* match kernel, then the chain kernel that loads one step ahead, b peaks per lane */
+#define PV_PHASE_FORM_FUSED 2  /* match and ring chain in one launch (single-stream engine, pool, mixed pool) */
+#define PV_PHASE_FORM_STREAM 3 /* the single-launch stream kernel of the drop-in path */
 #define PV_CENSUS_SET_BATCH 0
 #define PV_CENSUS_SET_POOL 1
 #define PV_CENSUS_SET_PMIX 2

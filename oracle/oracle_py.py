@@ -60,6 +60,8 @@ def lib():
         L.pvo_set_synth_trig_nudge.restype = None
         L.pvo_get_increments.restype = C.c_long
         L.pvo_get_increments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+        L.pvo_get_phase_trace.restype = C.c_long
+        L.pvo_get_phase_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
         L.pvo_hann.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.pvo_forward_polar.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pvo_inverse_polar.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -138,10 +140,21 @@ class Oracle:
         self.L.pvo_get_increments(self.h, s.ctypes.data, p.ctypes.data, n)
         return s, p
 
+    def phase_trace(self):
+        """(peak counts, modes), one entry per (slice, channel) step of the phase-locked core mode in processing
+        order; modes: 0 init, 1 per-bin propagation, 2 locked (pv_oracle.h pvo_get_phase_trace)"""
+        n = self.L.pvo_get_phase_trace(self.h, None, None, 0)
+        k = np.zeros(n, dtype=np.int32)
+        m = np.zeros(n, dtype=np.int32)
+        self.L.pvo_get_phase_trace(self.h, k.ctypes.data, m.ctypes.data, n)
+        return k, m
 
-def run_offline(x, block=480, flush=True, **kw):
+
+def run_offline(x, block=480, flush=True, trace=False, **kw):
     """The reference CLI's offline drive loop (main/main.cc:471-510) on the oracle.
-    x: float32 [channels, frames].  Returns (out [channels, n], per-call counts)."""
+    x: float32 [channels, frames].  Returns (out [channels, n], per-call counts, info); with trace=True the info
+    carries "trace": Oracle.phase_trace() of the whole run, and "flush_step": its length before the first all-zero
+    flush block was fed."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     ch, frames = x.shape
     o = Oracle(ch, **kw)
@@ -152,6 +165,7 @@ def run_offline(x, block=480, flush=True, **kw):
         outs.append(o.retrieve(got))
         counts.append(got)
         produced += got
+    flush_step = len(o.phase_trace()[0]) if trace else 0
     if flush:
         z = np.zeros((ch, block), dtype=np.float32)
         while produced < frames:
@@ -162,6 +176,9 @@ def run_offline(x, block=480, flush=True, **kw):
             outs.append(y[:, :w])
             produced += w
     info = o.info()
+    if trace:
+        info["trace"] = o.phase_trace()
+        info["flush_step"] = flush_step
     o.close()
     return np.concatenate(outs, axis=1), counts, info
 

@@ -662,6 +662,7 @@ struct pvo {
     float *resamplebuf; size_t resamplebuf_size;
     /* record of increments for planner pinning */
     int *rec_shift, *rec_phase; long nrec, caprec;
+    int *tr_npk, *tr_mode; long ntr, captr; /* pvo_get_phase_trace */
     /* set once a slice's shift increment exceeds N: writeSlice (phasevocoderprocess.cc:1181-1190) then calls
      * memmove with (N - shiftIncrement) wrapped to a huge size_t -- undefined behaviour in the reference, only
      * reachable with a caller-chosen hop.  The oracle stops there instead of reproducing the overflow. */
@@ -825,6 +826,7 @@ void pvo_destroy(pvo *h) {
     free(h->car); free(h->gen); free(h->chord);
     free(h->ch); free(h->win); free(h->peak); free(h->prev_peak); free(h->resamplebuf);
     free(h->rec_shift); free(h->rec_phase);
+    free(h->tr_npk); free(h->tr_mode);
     free(h);
 }
 
@@ -886,6 +888,8 @@ static void modify_simple(pvo *h, chan *a, size_t phaseIncrement) {
     h->firstentry = 0;
 }
 
+static void record_trace(pvo *h, int npk, int mode);
+
 /* phasevocoderprocess.cc:574-706 */
 static void modify_locked(pvo *h, chan *a, size_t phaseIncrement) {
     const int hs = (int)h->N / 2;
@@ -900,6 +904,7 @@ static void modify_locked(pvo *h, chan *a, size_t phaseIncrement) {
             b += 1;
         }
     }
+    record_trace(h, h->npeak, h->firstentry ? 0 : (h->npeak == 0 || h->nprev_peak == 0) ? 1 : 2);
     if (h->firstentry) {
         init_bins(h, a);
     } else if (h->npeak == 0 || h->nprev_peak == 0) {
@@ -1093,6 +1098,18 @@ static void record_incr(pvo *h, size_t shift, size_t phase) {
     h->rec_shift[h->nrec] = (int)shift;
     h->rec_phase[h->nrec] = (int)phase;
     h->nrec++;
+}
+
+/* one entry per (slice, channel) step of modify_locked, in processing order: its peak count and its branch */
+static void record_trace(pvo *h, int npk, int mode) {
+    if (h->ntr == h->captr) {
+        h->captr = h->captr ? h->captr * 2 : 1024;
+        h->tr_npk = (int *)realloc(h->tr_npk, sizeof(int) * h->captr);
+        h->tr_mode = (int *)realloc(h->tr_mode, sizeof(int) * h->captr);
+    }
+    h->tr_npk[h->ntr] = npk;
+    h->tr_mode[h->ntr] = mode;
+    h->ntr++;
 }
 
 /* phasevocoderprocess.cc:236-287 + :305-376 + :412-489 */
@@ -1333,6 +1350,13 @@ long pvo_get_increments(const pvo *h, int *shift, int *phase, long max) {
     if (shift) memcpy(shift, h->rec_shift, sizeof(int) * n);
     if (phase) memcpy(phase, h->rec_phase, sizeof(int) * n);
     return h->nrec;
+}
+
+long pvo_get_phase_trace(const pvo *h, int *npk, int *mode, long max) {
+    long n = h->ntr < max ? h->ntr : max;
+    if (npk) memcpy(npk, h->tr_npk, sizeof(int) * n);
+    if (mode) memcpy(mode, h->tr_mode, sizeof(int) * n);
+    return h->ntr;
 }
 
 /* libm's atan2f over arrays (the analysis phases of the reference come from it, FFT.cc:2623-2630): what the

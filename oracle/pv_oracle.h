@@ -66,6 +66,12 @@ void pvo_get_info(const pvo *h, pvo_info *info);
 void pvo_set_synth_trig_nudge(pvo *h, float delta, unsigned seed);
 /* per-slice shift increments recorded so far (for pinning the host planner); returns count copied */
 long pvo_get_increments(const pvo *h, int *shift, int *phase, long max);
+/* per (slice, channel) step of the phase-locked core mode, in processing order (channel 0 of a slice, then channel 1):
+ * the number of peaks found, and the branch taken -- 0 first entry (init), 1 per-bin propagation (no peak now or none
+ * in the step before, which with two channels is the other channel's), 2 locked.  Returns the number of steps so far;
+ * copies at most max of them */
+enum { PVO_TRACE_INIT = 0, PVO_TRACE_PROP = 1, PVO_TRACE_LOCK = 2 };
+long pvo_get_phase_trace(const pvo *h, int *npk, int *mode, long max);
 
 /* unit-level entry points (pinned by tests/golden KATs) */
 void pvo_hann(int n, float *w, float *area);

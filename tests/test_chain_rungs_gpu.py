@@ -315,5 +315,5 @@ def test_the_census_file_receives_a_process_counts_at_exit(tmp_path):
     assert lines[0] == "kept"
     keys = sorted(l.rsplit(" ", 1)[0] for l in lines[1:])
     assert keys == ["analyze set=pool nc=1024 split=0", "chain set=pool nc=1024 core=1 res=1 fast=1",
-                    "resample set=pool fast=1 interp=1"], lines
+                    "phase set=pool form=fused b=8", "resample set=pool fast=1 interp=1"], lines
     assert all(int(l.rsplit("count=", 1)[1]) > 0 for l in lines[1:]), lines
