@@ -83,6 +83,39 @@ static int res_tab_bytes(const Derived &d) {
                        : (int)((d.sinc.size() * sizeof(float) + 15) & ~(size_t)15);
 }
 
+// LDS floats of one staged row of a resampling tile: the stream samples 256 outputs span at the configuration's input
+// step, one filter length, and the margins the kernels write past them (Core::init, pool_launch_group, the mixed
+// batch's tables: one rule)
+static int res_tile_lds_floats(const Derived &d) {
+    const double step = d.resample ? (double)d.res_num / (double)d.res_den : 1.0;
+    const int tile_span = (int)(kTileOut * step) + (d.resample ? d.filt_len : 0) + 4;
+    return (tile_span + 4 + 3) & ~3;
+}
+// What launch_resample / the uniform pool's resampler reads of a configuration to choose its kernel
+static ResArgs res_rung_probe(const Derived &d, int rows, bool fast) {
+    ResArgs ra{};
+    ra.rows = rows;
+    ra.interp = d.interp ? 1 : 0;
+    ra.filt_len = d.filt_len;
+    ra.oversample = d.oversample;
+    ra.lds_floats = res_tile_lds_floats(d);
+    ra.tab_bytes = res_tab_bytes(d);
+    ra.fast = fast ? 1 : 0;
+    return ra;
+}
+// The refusal of a pitch whose resampling kernel cannot get its LDS: the filter grows with the ratio (make_resampler),
+// and so do the table and the tile.  need: the bytes the kernel of this configuration would ask for.
+static int refuse_resample_lds(const Derived &d, size_t need, const char *kernel) {
+    char msg[384];
+    snprintf(msg, sizeof msg,
+             "pitch %+.2f semitones is above the limit: its resampling filter has %d taps (rate %d/%d, oversampling %d) and "
+             "the %s needs %zu bytes of LDS for table and tile, a workgroup has %d; the fused path resamples up to about "
+             "+46 semitones with PV_ARITH_FAST and +56 with PV_ARITH_EXACT",
+             (double)d.cfg.pitch_semitones, d.filt_len, d.res_num, d.res_den, d.oversample, kernel, need, 160 * 1024 - 512);
+    g_last_error = msg;
+    return PV_ERR_UNSUPPORTED;
+}
+
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
@@ -482,6 +515,47 @@ int Core::init(const pv_config &cfg, int dev, int nstreams, int chunk_slices) {
         g_last_error = "fftsize above 8192 is not supported by the phase kernel";
         return PV_ERR_UNSUPPORTED;
     }
+    S = nstreams;
+    C = cfg.channels;
+    rows = S * C;
+    if (rows > 65535) { // several kernels put the rows on grid.y
+        g_last_error = "more than 65535 rows (streams x channels) in one batch: split it";
+        return PV_ERR_UNSUPPORTED;
+    }
+    HP = d.hs + 8; // row pitch of the mag / phase planes (16-byte aligned rows)
+    pkmax = d.hs / 3 + 2;
+    PKP = (pkmax + 7) & ~7;
+    // frames that can overlap one OLA tile / that must stay in the ring behind the newest slice
+    const double step = d.resample ? (double)d.res_num / (double)d.res_den : 1.0;
+    const int tile_span = (int)(kTileOut * step) + (d.resample ? d.filt_len : 0) + 4;
+    ola_lds_floats = res_tile_lds_floats(d); // a multiple of 4: the gather writes the tile four samples at a time
+    otab_off = (ola_lds_floats + 3) & ~3;
+    wacc_pitch = otab_off + 2 * kTileOut;
+    lookback = (d.N + tile_span) / d.min_shift + 3;
+    use_chain = chain_wanted() && (chain_required || rows >= kChainMinRows || fast_capable());
+    if (const char *e = getenv("AUDIOMOD_PV_FUSED")) // =2: the fused path whatever the row count
+        if (atoi(e) == 2) use_chain = true;
+    if (!use_chain && (tile_span + d.N) / d.min_shift + 3 > kMaxTileFrames) {
+        if (chain_wanted()) use_chain = true; // the tile path cannot hold that many frames per tile: fused after all
+    }
+    if (!use_chain && (tile_span + d.N) / d.min_shift + 3 > kMaxTileFrames) {
+        g_last_error = "hop too small relative to the FFT size for the OLA tile";
+        return PV_ERR_UNSUPPORTED;
+    }
+    // the resampling kernel of this configuration must get its LDS: decided from the derived constants, before any
+    // device call (the mixed pool and the mixed batch check their ranges the same way)
+    if (d.resample) {
+        if (use_chain) {
+            const ResRung rr = resample_rung(res_rung_probe(d, rows, fast_chain()));
+            if (!rr.fits) return refuse_resample_lds(d, rr.lds_bytes, "resampling kernel");
+        } else {
+            OlaArgs probe{};
+            probe.tab_bytes = res_tab_bytes(d);
+            probe.lds_floats = ola_lds_floats;
+            if (ola_lds_bytes(probe, 2) > 160 * 1024 - 512)
+                return refuse_resample_lds(d, ola_lds_bytes(probe, 2), "overlap-add and resampling kernel");
+        }
+    }
     if (count_gfx950() <= 0) {
         g_last_error = "no gfx950 (MI355X) device visible: this library has no CPU fallback";
         return PV_ERR_NO_DEVICE;
@@ -499,33 +573,6 @@ int Core::init(const pv_config &cfg, int dev, int nstreams, int chunk_slices) {
     if (!lds_starts_at_zero()) {
         g_last_error = "internal: an analysis kernel was built with static LDS (its atan2f table address assumes none)";
         return PV_ERR_HIP;
-    }
-    S = nstreams;
-    C = cfg.channels;
-    rows = S * C;
-    if (rows > 65535) { // several kernels put the rows on grid.y
-        g_last_error = "more than 65535 rows (streams x channels) in one batch: split it";
-        return PV_ERR_UNSUPPORTED;
-    }
-    HP = d.hs + 8; // row pitch of the mag / phase planes (16-byte aligned rows)
-    pkmax = d.hs / 3 + 2;
-    PKP = (pkmax + 7) & ~7;
-    // frames that can overlap one OLA tile / that must stay in the ring behind the newest slice
-    const double step = d.resample ? (double)d.res_num / (double)d.res_den : 1.0;
-    const int tile_span = (int)(kTileOut * step) + (d.resample ? d.filt_len : 0) + 4;
-    ola_lds_floats = (tile_span + 4 + 3) & ~3; // a multiple of 4: the gather writes the tile four samples at a time
-    otab_off = (ola_lds_floats + 3) & ~3;
-    wacc_pitch = otab_off + 2 * kTileOut;
-    lookback = (d.N + tile_span) / d.min_shift + 3;
-    use_chain = chain_wanted() && (chain_required || rows >= kChainMinRows || fast_capable());
-    if (const char *e = getenv("AUDIOMOD_PV_FUSED")) // =2: the fused path whatever the row count
-        if (atoi(e) == 2) use_chain = true;
-    if (!use_chain && (tile_span + d.N) / d.min_shift + 3 > kMaxTileFrames) {
-        if (chain_wanted()) use_chain = true; // the tile path cannot hold that many frames per tile: fused after all
-    }
-    if (!use_chain && (tile_span + d.N) / d.min_shift + 3 > kMaxTileFrames) {
-        g_last_error = "hop too small relative to the FFT size for the OLA tile";
-        return PV_ERR_UNSUPPORTED;
     }
     if (use_chain) {
         // ring sizes and waves per workgroup of the chain kernel: as many waves (slices of a row in flight) as LDS
@@ -1460,9 +1507,16 @@ int pv_get_arithmetic(void) { return g_arith; }
 
 // ---- diagnostics: the launchers' census (pv_kernels.hip) and the rung a configuration gets
 static const char *const kCensusSetName[PV_CENSUS_SETS] = {"batch", "pool", "pmix", "mb"};
-static std::string g_census_file;
+static std::string g_census_file, g_res_census_file;
+static void census_append(const std::string &file, const std::string &out) {
+    if (file.empty() || out.empty()) return;
+    if (FILE *f = fopen(file.c_str(), "a")) { // one write per process: lines of concurrent processes stay whole
+        fwrite(out.data(), 1, out.size(), f);
+        fclose(f);
+    }
+}
 static void census_append_at_exit() {
-    std::string out;
+    std::string out, out_rungs;
     char line[160];
     static const int ncs[4] = {256, 512, 1024, 2048};
     for (int set = 0; set < PV_CENSUS_SETS; ++set) {
@@ -1484,6 +1538,16 @@ static void census_append_at_exit() {
                          interp, (long long)n);
                 out += line;
             }
+        static const char *const rungs[kResRungs] = {"ref4", "vec8", "vec16", "mfma", "vec2", "vec4"};
+        for (int rung = 0; rung < kResRungs; ++rung)
+            for (int interp = 0; interp < 2; ++interp)
+                for (int big = 0; big < 2; ++big) {
+                    const int64_t n = chain_census_count(PV_CENSUS_RESAMPLE_RUNG, set, rung, interp, big, 0);
+                    if (n <= 0) continue;
+                    snprintf(line, sizeof line, "resample_rung set=%s rung=%s interp=%d over64k=%d count=%lld\n",
+                             kCensusSetName[set], rungs[rung], interp, big, (long long)n);
+                    out_rungs += line;
+                }
         for (int nc : ncs)
             for (int split = 0; split < 2; ++split) {
                 const int64_t n = chain_census_count(PV_CENSUS_ANALYZE, set, nc, split, 0, 0);
@@ -1503,16 +1567,16 @@ static void census_append_at_exit() {
                 out += line;
             }
     }
-    if (out.empty()) return;
-    if (FILE *f = fopen(g_census_file.c_str(), "a")) { // one write per process: lines of concurrent processes stay whole
-        fwrite(out.data(), 1, out.size(), f);
-        fclose(f);
-    }
+    // (the resampling rungs go to a file of their own: what reads AUDIOMOD_PV_CHAIN_CENSUS's file keeps finding the
+    // four kinds it knows, line for line; both variables may name one file)
+    census_append(g_census_file, out);
+    census_append(g_res_census_file, out_rungs);
 }
 static const bool g_census_from_env = [] {
-    const char *e = getenv("AUDIOMOD_PV_CHAIN_CENSUS");
-    if (!e || !*e) return false;
-    g_census_file = e;
+    const char *e = getenv("AUDIOMOD_PV_CHAIN_CENSUS"), *r = getenv("AUDIOMOD_PV_RESAMPLE_CENSUS");
+    if (e && *e) g_census_file = e;
+    if (r && *r) g_res_census_file = r;
+    if (g_census_file.empty() && g_res_census_file.empty()) return false;
     chain_census_enable(true);
     atexit(census_append_at_exit);
     return true;
@@ -1576,6 +1640,33 @@ int pv_debug_chain_rung(const pv_config *cfg, int arith, pv_chain_rung *out) {
     out->wave_bound = Core::chain_wave_bound(d, fast_arith);
     out->reciprocal_wden = Core::fast_capable_of(d, fast_arith) ? 1 : 0; // Core::fast_chain() on the fused path
     return PV_OK;
+}
+
+int pv_debug_resample_rung(const pv_config *cfg, int arith, int32_t rows, pv_resample_rung *out) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!cfg || !out || rows < 1 || (arith != PV_ARITH_FAST && arith != PV_ARITH_EXACT)) return PV_ERR_INVALID_ARG;
+    Derived d;
+    const int st = derive(*cfg, d);
+    if (st != PV_OK) return st;
+    memset(out, 0, sizeof *out);
+    out->rung = -1;
+    out->resample = d.resample ? 1 : 0;
+    if (!d.resample) return PV_OK;
+    // (the fused path's resampler: ResArgs::fast is Core::fast_chain(), as res_args_uniform sets it)
+    const ResArgs ra = res_rung_probe(d, rows, Core::fast_capable_of(d, arith == PV_ARITH_FAST));
+    const ResRung rr = resample_rung(ra);
+    out->res_num = d.res_num;
+    out->res_den = d.res_den;
+    out->filt_len = d.filt_len;
+    out->oversample = d.oversample;
+    out->interp = ra.interp;
+    out->tab_bytes = ra.tab_bytes;
+    out->lds_floats = ra.lds_floats;
+    out->rung = rr.rung;
+    out->lds_bytes = (int64_t)rr.lds_bytes;
+    out->refused = rr.fits ? 0 : 1;
+    return rr.fits ? PV_OK : refuse_resample_lds(d, rr.lds_bytes, "resampling kernel");
 }
 
 int64_t pv_plan_table(const pv_config *cfg, int which, float *out, int64_t max) {
@@ -2457,11 +2548,7 @@ static int pool_max_adv(const Derived &d) {
     return (int)(m < d.N ? m + 1 : d.N);
 }
 // LDS layout of the resampling kernel for one set of derived constants (as Core::init and pool_launch_group lay it out)
-static int pool_res_lds_floats(const Derived &d) {
-    const double step = (double)d.res_num / (double)d.res_den;
-    const int tile_span = (int)(kTileOut * step) + d.filt_len + 4;
-    return (tile_span + 4 + 3) & ~3;
-}
+static int pool_res_lds_floats(const Derived &d) { return res_tile_lds_floats(d); }
 static bool pool_in_range(const pv_pool_range &r, float time_ratio, float semis) {
     return semis >= r.min_semitones && semis <= r.max_semitones && time_ratio >= r.min_time_ratio &&
            time_ratio <= r.max_time_ratio; // (false for a NaN)

@@ -258,7 +258,8 @@ enum { PV_CENSUS_SETS = 4 }; // PV_CENSUS_SET_BATCH / POOL / PMIX / MB of the C 
 void chain_census_enable(bool on); // clears the table either way
 // kind: PV_CENSUS_CHAIN (a = NC, b = kPlainCore, c = kRes, d = kFast), PV_CENSUS_RESAMPLE (a = fast, b = interpolated),
 // PV_CENSUS_ANALYZE (a = NC, b = split), PV_CENSUS_PHASE (a = form, b = ring depth 4 / 8 or, for the forms without a
-// ring, peaks per lane 1 / 3); -1 for a key that does not exist
+// ring, peaks per lane 1 / 3), PV_CENSUS_RESAMPLE_RUNG (all four sets: a = rung kResRung*, b = interpolated, c = the
+// launch asked for more than 64 KB of LDS); -1 for a key that does not exist
 // The forms of the phase-locked stage (PV_PHASE_FORM_* of the C ABI): match kernel + ring chain kernel; match kernel +
 // chain kernel that loads one step ahead (pv_seq_kernel<1>, or <3> with three peaks per lane); match and ring chain in
 // one launch; the single-launch stream kernel.  Set: launch_seq / launch_phase / launch_stream count under batch.
@@ -285,6 +286,19 @@ struct ResArgs {
     int64_t out_stride_row, k_base;
     int fast; // arithmetic free within the 1e-4 RMS contract (pv_resample_fast_kernel) instead of the reference's order
 };
+// The rungs of the resampler's ladders (PV_RES_RUNG_* of the C ABI): pv_resample_kernel (the reference's order, four
+// rows per workgroup), pv_resample_fast_kernel with 8 / 16 rows, pv_resample_mfma_kernel; the mixed batch's free-form
+// kernel also exists with 2 and 4 rows.  The slot-table sets count their kernels under the same names.
+enum { kResRungRef4 = 0, kResRungVec8 = 1, kResRungVec16 = 2, kResRungMfma = 3, kResRungVec2 = 4, kResRungVec4 = 5, kResRungs = 6 };
+// What launch_resample launches for a.rows / a.fast / a.tab_bytes / a.lds_floats (nothing else is read, no device is
+// needed): the rung, the dynamic LDS it asks for, and whether that fits a workgroup at all (kMaxDynLds).  The launcher
+// itself goes by this answer, and so does engine creation, which refuses a configuration whose rung does not fit.
+struct ResRung {
+    int rung;
+    size_t lds_bytes;
+    bool fits;
+};
+ResRung resample_rung(const ResArgs &a);
 void launch_resample(const ResArgs &a, hipStream_t st);
 bool launch_phase(const MatchArgs &m, const SeqArgs &a, hipStream_t st); // single-stream engine: match + chain in one launch
 size_t chain_lds_bytes(const ChainArgs &a, int nc_wave /* 0: frames from HBM */);
@@ -304,6 +318,7 @@ struct StreamArgs {
     OlaArgs oa;
     int coremode, cepstral;
 };
+size_t ola_lds_bytes(const OlaArgs &a, int rows_per_group); // the tile path's overlap-add + resampling kernel
 bool stream_kernel_supported(const StreamArgs &s);  // wave-FFT sizes only (nc 1024 / 2048)
 void launch_stream(const StreamArgs &s, hipStream_t st);
 

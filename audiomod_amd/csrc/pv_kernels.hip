@@ -3270,6 +3270,7 @@ static std::atomic<bool> g_census_on{false};
 static constexpr int kCensusNc = 4, kCensusCore = 5; // NC 256 ... 2048; kPlainCore -1 ... 3
 static std::atomic<uint64_t> g_census_chain[PV_CENSUS_SETS][kCensusNc][kCensusCore][2][2];
 static std::atomic<uint64_t> g_census_res[PV_CENSUS_SETS][2][2];
+static std::atomic<uint64_t> g_census_rrung[PV_CENSUS_SETS][kResRungs][2][2];
 static std::atomic<uint64_t> g_census_ana[PV_CENSUS_SETS][kCensusNc][2];
 static std::atomic<uint64_t> g_census_phase[PV_CENSUS_SETS][kPhaseForms][4];
 static int census_phase_index(int b) { return b == 1 ? 0 : b == 3 ? 1 : b == 4 ? 2 : b == 8 ? 3 : -1; }
@@ -3281,6 +3282,10 @@ static inline void census_chain(int set, int nc, int plain_core, int res, bool f
 static inline void census_resample(int set, bool fast, bool interp) {
     if (!g_census_on.load(std::memory_order_relaxed)) return;
     g_census_res[set][fast ? 1 : 0][interp ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+}
+static inline void census_resample_rung(int set, int rung, bool interp, size_t lds) {
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    g_census_rrung[set][rung][interp ? 1 : 0][lds > 64 * 1024 ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
 }
 static inline void census_analyze(int set, int nc, bool split) {
     if (!g_census_on.load(std::memory_order_relaxed)) return;
@@ -3294,6 +3299,7 @@ void chain_census_enable(bool on) {
     g_census_on.store(false, std::memory_order_relaxed);
     for (auto &a : g_census_chain) for (auto &b : a) for (auto &c : b) for (auto &d : c) for (auto &e : d) e.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_res) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
+    for (auto &a : g_census_rrung) for (auto &b : a) for (auto &c : b) for (auto &d : c) d.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_ana) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_phase) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     g_census_on.store(on, std::memory_order_relaxed);
@@ -3314,6 +3320,9 @@ int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
     case 3:
         if (a < 0 || a >= kPhaseForms || census_phase_index(b) < 0) return -1;
         return (int64_t)g_census_phase[set][a][census_phase_index(b)].load(std::memory_order_relaxed);
+    case 4:
+        if (a < 0 || a >= kResRungs || !flag(b) || !flag(c)) return -1;
+        return (int64_t)g_census_rrung[set][a][b][c].load(std::memory_order_relaxed);
     default: return -1;
     }
 }
@@ -3669,7 +3678,11 @@ __global__ __launch_bounds__(kTileOut) __attribute__((amdgpu_waves_per_eu(4))) v
     const int row0 = blockIdx.y * NR, NF = a.filt_len, ncnt = tile.n_cnt, kcnt = tile.kcnt;
     const int nr = a.rows - row0 < NR ? a.rows - row0 : NR;
     const int nrl = a.rows < NR ? a.rows : NR; // rows the launch's LDS holds
-    // (a tile too long for the padded layout -- no engine makes one -- stages at lds_floats and takes the vector loop)
+    // (a tile too long for the padded layout stages at lds_floats and takes the vector loop.  No engine makes one, at
+    // any pitch: a tile's 256 outputs span n_cnt <= floor(255 num/den) + 1 + filt_len samples, every engine sizes
+    // lds_floats = (floor(256 num/den) + filt_len + 4 + 4 + 3) & ~3 >= n_cnt + 7, and the padded stride is
+    // lds_floats - 2 (lds_floats is a multiple of 4), so n_cnt + 4 <= lds_floats - 3 < xstride.
+    // tests/test_resample_rungs_host.py holds the inequality for -60 ... +60 semitones in 0.01 steps.)
     const bool fits = ncnt + 4 <= res_mfma_xstride(a.lds_floats);
     const int xstride = fits ? res_mfma_xstride(a.lds_floats) : a.lds_floats;
     const int nstage = fits ? ncnt + 4 : ncnt;
@@ -3791,8 +3804,7 @@ __global__ __launch_bounds__(kTileOut) __attribute__((amdgpu_waves_per_eu(4))) v
 // reads, bit-identical output.  Alone it is faster, 0.255 -> 0.202 ms per launch, its four 16-byte coefficient reads per
 // sample step then being the LDS cost; beside the rotation chain, where the kernel really runs, its 64 KB of LDS per
 // workgroup and low occupancy make it slower, 0.30 -> 0.34-0.38 ms: profiles/r03/resample_elim.txt.)
-template <int NR> static void launch_resample_fast_rows(const ResArgs &a, hipStream_t st) {
-    const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * NR;
+template <int NR> static void launch_resample_fast_rows(const ResArgs &a, size_t lds, hipStream_t st) {
     const dim3 grid(a.ntiles, (a.rows + NR - 1) / NR);
     if (a.interp) {
         launch_big_lds<pv_resample_fast_kernel<2, NR>>(grid, dim3(kTileOut), lds, st, a);
@@ -3800,7 +3812,13 @@ template <int NR> static void launch_resample_fast_rows(const ResArgs &a, hipStr
         launch_big_lds<pv_resample_fast_kernel<1, NR>>(grid, dim3(kTileOut), lds, st, a);
     }
 }
-static void launch_resample_fast(const ResArgs &a, hipStream_t st) {
+// The ladder, stated once: launch_resample launches what this returns, Core::init refuses what does not fit, and
+// pv_debug_resample_rung reports it (pv_kernels.h).
+ResRung resample_rung(const ResArgs &a) {
+    const size_t fl = sizeof(float);
+    const auto rows_lds = [&](int nr) { return (size_t)a.tab_bytes + fl * (size_t)a.lds_floats * nr; };
+    const auto answer = [](int rung, size_t lds) { return ResRung{rung, lds, lds <= kMaxDynLds}; };
+    if (!a.fast) return answer(kResRungRef4, rows_lds(kResRows));
     static const int rows_env = [] { // AUDIOMOD_PV_RES_ROWS=8|16 (tuning knob)
         const char *e = getenv("AUDIOMOD_PV_RES_ROWS");
         return e ? atoi(e) : 0;
@@ -3809,37 +3827,40 @@ static void launch_resample_fast(const ResArgs &a, hipStream_t st) {
         const char *e = getenv("AUDIOMOD_PV_RES_MFMA");
         return !(e && atoi(e) == 0);
     }();
-    const size_t fl = sizeof(float);
-    if (mfma && (size_t)a.tab_bytes + fl * (size_t)a.lds_floats * kResMfmaRows <= 64 * 1024) {
+    if (mfma && rows_lds(kResMfmaRows) <= 64 * 1024) {
         // LDS: the tables, then the staged rows -- at the padded stride plus the flag words, or at lds_floats for a
         // tile that does not fit it -- never more than the vector kernel's 16 rows x lds_floats for two rows or more
         const size_t nrl = a.rows < kResMfmaRows ? a.rows : kResMfmaRows;
         const size_t padded = fl * (nrl * res_mfma_xstride(a.lds_floats) + kTileOut / 64);
-        const size_t lds = (size_t)a.tab_bytes + std::max(fl * nrl * (size_t)a.lds_floats, padded);
-        const dim3 grid(a.ntiles, (a.rows + kResMfmaRows - 1) / kResMfmaRows);
-        if (a.interp) {
-            launch_big_lds<pv_resample_mfma_kernel<2>>(grid, dim3(kTileOut), lds, st, a);
-        } else {
-            launch_big_lds<pv_resample_mfma_kernel<1>>(grid, dim3(kTileOut), lds, st, a);
-        }
-        return;
+        return answer(kResRungMfma, (size_t)a.tab_bytes + std::max(fl * nrl * (size_t)a.lds_floats, padded));
     }
     const int want = rows_env ? rows_env : kResFastRows; // (8 -> 16 rows per thread: 0.265 -> 0.255 ms per launch alone, cfg4 -7 st +3 %)
-    if (want >= 16 && a.rows >= 16 && (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * 16 <= 64 * 1024)
-        launch_resample_fast_rows<16>(a, st);
-    else
-        launch_resample_fast_rows<8>(a, st);
+    if (want >= 16 && a.rows >= 16 && rows_lds(16) <= 64 * 1024) return answer(kResRungVec16, rows_lds(16));
+    return answer(kResRungVec8, rows_lds(8));
 }
 
 void launch_resample(const ResArgs &a, hipStream_t st) {
     if (a.ntiles <= 0) return; // (a group of dropped slices completes no output)
-    if (a.fast) return launch_resample_fast(a, st);
-    const size_t lds = (size_t)a.tab_bytes + sizeof(float) * (size_t)a.lds_floats * kResRows;
-    const dim3 grid(a.ntiles, (a.rows + kResRows - 1) / kResRows);
-    if (a.interp) {
-        launch_big_lds<pv_resample_kernel<2>>(grid, dim3(kTileOut), lds, st, a);
+    const ResRung r = resample_rung(a); // (engine creation has refused what does not fit)
+    census_resample_rung(0, r.rung, a.interp != 0, r.lds_bytes);
+    if (r.rung == kResRungMfma) {
+        const dim3 grid(a.ntiles, (a.rows + kResMfmaRows - 1) / kResMfmaRows);
+        if (a.interp) {
+            launch_big_lds<pv_resample_mfma_kernel<2>>(grid, dim3(kTileOut), r.lds_bytes, st, a);
+        } else {
+            launch_big_lds<pv_resample_mfma_kernel<1>>(grid, dim3(kTileOut), r.lds_bytes, st, a);
+        }
+    } else if (r.rung == kResRungVec16) {
+        launch_resample_fast_rows<16>(a, r.lds_bytes, st);
+    } else if (r.rung == kResRungVec8) {
+        launch_resample_fast_rows<8>(a, r.lds_bytes, st);
     } else {
-        launch_big_lds<pv_resample_kernel<1>>(grid, dim3(kTileOut), lds, st, a);
+        const dim3 grid(a.ntiles, (a.rows + kResRows - 1) / kResRows);
+        if (a.interp) {
+            launch_big_lds<pv_resample_kernel<2>>(grid, dim3(kTileOut), r.lds_bytes, st, a);
+        } else {
+            launch_big_lds<pv_resample_kernel<1>>(grid, dim3(kTileOut), r.lds_bytes, st, a);
+        }
     }
 }
 
@@ -4462,6 +4483,8 @@ static bool launch_slot_resample(const Set &set, const ResArgs &a, const PoolLau
     if (lds > kMaxDynLds) return false;
     if (!launch || p.max_tiles <= 0) return true; // (max_tiles 0: dropped slices only, no output completed)
     census_resample(Set::census_set, kFast, a.interp != 0);
+    census_resample_rung(Set::census_set, !kFast ? kResRungRef4 : NR == 2 ? kResRungVec2 : NR == 4 ? kResRungVec4 : kResRungVec8,
+                         a.interp != 0, lds);
     const dim3 grid(p.max_tiles, (a.rows + NR - 1) / NR, p.nslots);
     if constexpr (kFast) {
         if (a.interp) set.template fast<2, NR>(grid, lds, st, a);

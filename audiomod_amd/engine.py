@@ -81,6 +81,12 @@ class ChainRung(C.Structure):
                 ("wave_bound", C.c_int32), ("reciprocal_wden", C.c_int32)]
 
 
+class ResampleRung(C.Structure):
+    _fields_ = [("resample", C.c_int32), ("res_num", C.c_int32), ("res_den", C.c_int32), ("filt_len", C.c_int32),
+                ("oversample", C.c_int32), ("interp", C.c_int32), ("tab_bytes", C.c_int32), ("lds_floats", C.c_int32),
+                ("rung", C.c_int32), ("refused", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
 _lib = None
 
 
@@ -158,6 +164,7 @@ def lib():
     L.pv_debug_chain_census_count.argtypes = [C.c_int] * 6
     L.pv_debug_chain_census_count.restype = C.c_int64
     L.pv_debug_chain_rung.argtypes = [C.POINTER(Config), C.c_int, C.POINTER(ChainRung)]
+    L.pv_debug_resample_rung.argtypes = [C.POINTER(Config), C.c_int, C.c_int32, C.POINTER(ResampleRung)]
     L.pv_host_alloc.argtypes = [C.c_size_t]
     L.pv_host_alloc.restype = C.c_void_p
     L.pv_host_free.argtypes = [C.c_void_p]
@@ -301,6 +308,42 @@ def chain_rung(arith, channels=2, **config):
     r = ChainRung()
     _check(lib().pv_debug_chain_rung(C.byref(cfg), int(arith), C.byref(r)), "pv_debug_chain_rung")
     return {k: getattr(r, k) for k, _ in r._fields_}
+
+
+RES_RUNGS = ("ref4", "vec8", "vec16", "mfma", "vec2", "vec4")  # PV_RES_RUNG_*: the resampling kernels
+
+
+def resample_census_read():
+    """The non-zero keys of the census' fifth kind, the resampling kernel of all four sets: {(set, rung, interpolated,
+    over_64k): launches} with `set` one of CENSUS_SETS ("batch" counts the batch path, the single-stream engine and the
+    host-staged engine), `rung` one of RES_RUNGS and over_64k whether the launch asked for more than 64 KB of LDS."""
+    count = lib().pv_debug_chain_census_count
+    out = {}
+    for i, name in enumerate(CENSUS_SETS):
+        for r, rung in enumerate(RES_RUNGS):
+            for interp in (0, 1):
+                for big in (0, 1):
+                    n = count(4, i, r, interp, big, 0)
+                    if n > 0:
+                        out[(name, rung, interp, big)] = n
+    return out
+
+
+def resample_rung(arith, rows, channels=2, **config):
+    """Host only (works without a GPU): the resampling kernel a batch of `rows` rows of a configuration gets under
+    `arith`, by the launcher's own function (include/audiomod_pv.h pv_debug_resample_rung): a dict of resample, res_num,
+    res_den, filt_len, oversample, interp, tab_bytes, lds_floats, rung (a name of RES_RUNGS, None where nothing is
+    resampled), lds_bytes, refused and, for a refused configuration, the reason engine creation gives."""
+    L = lib()
+    cfg = make_config(channels, **config)
+    r = ResampleRung()
+    st = L.pv_debug_resample_rung(C.byref(cfg), int(arith), int(rows), C.byref(r))
+    if st != 0 and not r.refused:
+        _check(st, "pv_debug_resample_rung")
+    out = {k: getattr(r, k) for k, _ in r._fields_}
+    out["rung"] = RES_RUNGS[r.rung] if r.rung >= 0 else None
+    out["reason"] = L.pv_last_error().decode() if r.refused else ""
+    return out
 
 
 def _check(st, what):

@@ -554,6 +554,9 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
  *                        frequency compensation phase-locked, -1 = all modes), c = kRes, d = kFast (the template
  *                        argument: 0 for an all-modes launch whatever the arithmetic setting)
  *   PV_CENSUS_RESAMPLE : slot-table resampler (pool / pmix / mb sets): a = free-form kernel, b = interpolated table
+ *   PV_CENSUS_RESAMPLE_RUNG : the resampling kernel of all four sets: a = the rung launched (PV_RES_RUNG_*), b =
+ *                        interpolated table, c = the launch asked for more than 64 KB of LDS.  The batch set counts the
+ *                        batch path, the single-stream engine and the host-staged engine (launch_resample)
  *   PV_CENSUS_ANALYZE  : slot-table analysis (pool / pmix / mb sets): a = NC, b = the two-wave split kernel
  *   PV_CENSUS_PHASE    : the phase-locked stage (core mode 1): a = form (PV_PHASE_FORM_*), b = the ring's depth (4 / 8)
  *                        or, for the forms without a ring, the peaks one lane holds (1 / 3).  The batch set counts the
@@ -562,11 +565,19 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
  * switches counting on or off; pv_debug_chain_census_count returns a key's count, -1 for a key that does not exist.
  * If the environment variable AUDIOMOD_PV_CHAIN_CENSUS names a file when the library is loaded, the census is on from
  * the start and the process appends its non-zero keys to that file when it exits, one line per key (child processes
- * inherit the variable and append too). */
+ * inherit the variable and append too).  The PV_CENSUS_RESAMPLE_RUNG keys go to the file that AUDIOMOD_PV_RESAMPLE_CENSUS
+ * names, in the same way (it may be the same file): the first file keeps exactly the four kinds it always had. */
 #define PV_CENSUS_CHAIN 0
 #define PV_CENSUS_RESAMPLE 1
 #define PV_CENSUS_ANALYZE 2
 #define PV_CENSUS_PHASE 3
+#define PV_CENSUS_RESAMPLE_RUNG 4
+#define PV_RES_RUNG_REF4 0  /* the reference's operation order, four rows per workgroup (PV_ARITH_EXACT) */
+#define PV_RES_RUNG_VEC8 1  /* free-form, vector ALU, eight rows per workgroup */
+#define PV_RES_RUNG_VEC16 2 /* ... sixteen rows (AUDIOMOD_PV_RES_MFMA=0 only: the matrix-core kernel fits wherever it does) */
+#define PV_RES_RUNG_MFMA 3  /* free-form, f32 matrix cores, sixteen rows: while tables + 16 rows fit 64 KB */
+#define PV_RES_RUNG_VEC2 4  /* mixed batch only: free-form with two / four rows for mono / stereo ... 4-channel streams */
+#define PV_RES_RUNG_VEC4 5
 #define PV_PHASE_FORM_RING 0   /* match kernel, then the chain kernel with an LDS ring of b steps */
 #define PV_PHASE_FORM_STEP 1   /* match kernel, then the chain kernel that loads one step ahead, b peaks per lane */
 #define PV_PHASE_FORM_FUSED 2  /* match and ring chain in one launch (single-stream engine, pool, mixed pool) */
@@ -586,6 +597,18 @@ typedef struct pv_chain_rung {
     int32_t wave_bound, reciprocal_wden;
 } pv_chain_rung;
 int pv_debug_chain_rung(const pv_config *cfg, int arith, pv_chain_rung *out);
+/* ... and, host only as well, the resampling kernel a batch of `rows` rows (streams x channels) of cfg would get under
+ * `arith`, by the launcher's own function: the Speex rate pair, filter length, oversampling and table kind, the LDS
+ * layout (table bytes, floats per staged row), and the rung (PV_RES_RUNG_*) with the LDS bytes it asks for.  A
+ * configuration that does not resample returns PV_OK with resample = 0 and rung = -1.  Where the rung's request
+ * exceeds what a workgroup can get (160 KB - 512) the fields are filled in, refused = 1, and the call returns
+ * PV_ERR_UNSUPPORTED with the reason engine creation gives in pv_last_error(). */
+typedef struct pv_resample_rung {
+    int32_t resample, res_num, res_den, filt_len, oversample, interp;
+    int32_t tab_bytes, lds_floats, rung, refused;
+    int64_t lds_bytes;
+} pv_resample_rung;
+int pv_debug_resample_rung(const pv_config *cfg, int arith, int32_t rows, pv_resample_rung *out);
 
 #define PV_WIRE_F32 0
 #define PV_WIRE_I16 1

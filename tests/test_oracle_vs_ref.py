@@ -20,6 +20,14 @@ CASES = [
     dict(semitones=4.0, block=64),
     dict(semitones=4.0, block=4800),
     dict(mode="robotic"),
+    # large pitch ratios (tests/test_resample_rungs_host.py): long filters, oversampling 4 / 2, direct tables with 256 and
+    # 512 taps, den = 4 and den = oversample = 8, and the 32-bit wrap in the oversampling rule just above 0 semitones
+    dict(semitones=24.0, fftsize=512),
+    dict(semitones=30.0, fftsize=512),
+    dict(semitones=36.0, fftsize=512),
+    dict(semitones=-24.0, fftsize=512),
+    dict(semitones=-36.0, fftsize=512),
+    dict(semitones=0.16, fftsize=512),
 ]
 
 

@@ -31,6 +31,16 @@ PITCH = {
     "-12_direct_up": (dict(semitones=-12.0), 0, True),
     "+3.7_fractional": (dict(semitones=3.7), 1, False),
     "-15.8_above_2x_up": (dict(fftsize=1024, sample_rate=16000, semitones=-15.8), 1, True),
+    # large ratios (tests/test_resample_rungs_host.py): the reference-order kernel at 256 ... 724 taps, oversampling 4, 2
+    # and 1, direct tables with 256 and 512 taps, above 64 KB of LDS (+42); up-sampling with the direct table at den = 4
+    # and den = oversample = 8; the 32-bit wrap in the oversampling rule just above zero (oversampling 4 at 64 taps)
+    "+24_direct_256_taps": (dict(fftsize=512, semitones=24.0), 0, False),
+    "+36_direct_512_taps": (dict(fftsize=512, semitones=36.0), 0, False),
+    "+40_oversample_1": (dict(fftsize=512, semitones=40.0), 1, False),
+    "+42_above_64k": (dict(fftsize=512, semitones=42.0), 1, False),
+    "-24_direct_den4": (dict(fftsize=512, semitones=-24.0), 0, True),
+    "-36_direct_den8": (dict(fftsize=512, semitones=-36.0), 0, True),
+    "+0.16_oversample_wrap": (dict(fftsize=512, semitones=0.16), 1, False),
 }
 
 

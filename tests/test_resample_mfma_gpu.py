@@ -44,6 +44,15 @@ res = {}
 # pitch: interpolated table (+4, +7, -7) and direct table (+12); down- and up-sampling
 for st in (4.0, 7.0, -7.0, 12.0):
     res["pitch%%+g" %% st] = batch(6, 2, 30000, st, 11)
+# +16.5: 164 taps, oversampling 4, 64 064 of the 65 536 bytes of LDS below which the matrix-core kernel runs -- the only
+# large-ratio regime in which the two settings of the switch still run different kernels (16 rows of 9 streams + 1)
+res["pitch+16.5"] = batch(9, 2, 6000, 16.5, 21)
+# -24: the direct table at 18 rows -- under the vector switch the only route to the 16-row vector kernel with a direct
+# table (the census says which kernel each child launched)
+E.chain_census(True)
+res["pitch-24x18"] = batch(9, 2, 6000, -24.0, 31)
+res["census-24x18"] = np.array(repr(sorted(E.resample_census_read())))
+E.chain_census(False)
 # rows per batch: partial row groups of the 16-row workgroups
 for ns, ch in ((1, 1), (1, 2), (3, 1), (17, 1), (128, 2)):
     res["rows%%d" %% (ns * ch)] = batch(ns, ch, 12000 if ns * ch > 32 else 24000, 4.0, 40 + ns)
@@ -52,6 +61,7 @@ x = signals.voice(40000, 2, seed=5)
 res["ragged+4"] = stream(x, [1, 479, 4097, 13, 9000, 480, 7, 333], 4.0)
 res["ragged-7"] = stream(x, [7, 1021, 97, 2500], -7.0)
 res["ragged+12"] = stream(x, [641, 3, 1500], 12.0)
+res["ragged+16.5"] = stream(x[:, :12000], [1, 479, 4097, 13, 480, 7, 333], 16.5)
 # an inf / NaN burst in the input
 y = signals.voice(30000, 2, seed=9)
 y[0, 12000:12040] = np.inf
@@ -81,8 +91,8 @@ def both(tmp_path_factory):
     return _run(d, "1"), _run(d, "0")
 
 
-CASES = ["pitch+4", "pitch+7", "pitch-7", "pitch+12", "rows1", "rows2", "rows3", "rows17", "rows256", "ragged+4",
-         "ragged-7", "ragged+12"]
+CASES = ["pitch+4", "pitch+7", "pitch-7", "pitch+12", "pitch+16.5", "pitch-24x18", "rows1", "rows2", "rows3", "rows17",
+         "rows256", "ragged+4", "ragged-7", "ragged+12", "ragged+16.5"]
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -92,6 +102,11 @@ def test_matrix_core_resampler_is_bit_identical(both, case):
     assert np.isfinite(v).all()
     diff = np.flatnonzero(m.view(np.uint32) != v.view(np.uint32))
     assert diff.size == 0, (case, diff.size, diff[:8])
+
+
+def test_the_two_children_ran_different_kernels(both):
+    assert str(both[0]["census-24x18"]) == repr([("batch", "mfma", 0, 0)])
+    assert str(both[1]["census-24x18"]) == repr([("batch", "vec16", 0, 0)])
 
 
 def test_matrix_core_resampler_non_finite_fallback(both):

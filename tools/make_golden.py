@@ -48,12 +48,18 @@ E2E = [
     ("stretch0.374_256_cm0", "voice2", dict(mode="time_stretch", time_ratio=0.374, fftsize=256, coremode=0, flush=False)),
     ("robotic-15.8_1024_16k_block4724", "voice2", dict(mode="robotic", fftsize=1024, sample_rate=16000, semitones=-15.8,
                                                      block=4724)),
+    # large pitch ratios (tests/test_resample_rungs_host.py): the 8-row resampler above 64 KB of LDS at 360 taps and
+    # oversampling 2; the direct table at den = oversample = 8.  Short clips: the filters are long, the outputs small
+    ("shift+30_512", "voice2_6000", dict(mode="normal_pitchshift", semitones=30.0, coremode=1, fftsize=512)),
+    ("shift-36_512", "voice2_6000", dict(mode="normal_pitchshift", semitones=-36.0, coremode=1, fftsize=512)),
 ]
 
 
 def make_signal(kind):
     if kind == "voice2":
         return signals.voice(FRAMES, 2)
+    if kind == "voice2_6000":
+        return signals.voice(6000, 2)
     if kind == "voice1":
         return signals.voice(FRAMES, 1)
     if kind == "dual":
