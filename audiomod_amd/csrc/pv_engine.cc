@@ -1336,6 +1336,7 @@ struct pv_batch {
     hipEvent_t ev_fused[4] = {}, ev_res[4] = {};
     int timing = 0; // 0 = off, n = instrument every n-th chunk
     int64_t next_span = -1; // pv_batch_run_span: the launch the next span must start with (-1: only a first span may follow)
+    int64_t tap_begin = 0, tap_end = 0; // pv_debug_batch_planes: the slices enqueued since the last launch 0
     std::vector<hipEvent_t> ev_pool; // kEvPerChunk per instrumented chunk
     std::vector<int> ev_chunk;       // chunk index of each used pool segment
     size_t ev_used = 0;
@@ -1363,6 +1364,7 @@ struct pv_engine {
     std::vector<SliceRec> recent; // slice table window; recent[0] is slice t_base
     int64_t t_base = 0;
     int64_t fed = 0, uploaded = 0;
+    int tap_n = 0; // pv_debug_planes: slices of the most recent call that launched any, at most the planes' ring
     hipStream_t stream = nullptr;
     int ring = 0; // device input ring length (power of two) per channel
     DevBuf<float> d_in, d_out, d_whisper, d_carrier;
@@ -1408,6 +1410,7 @@ struct pv_pool {
         std::unique_ptr<Planner> planner;
         std::unique_ptr<ChainBuilder> chain;
         int64_t fed = 0, uploaded = 0, slices = 0;
+        int tap_n = 0;    // pv_debug_pool_planes: slices of the slot's most recent launches, at most the planes' ring
         int acc_half = 0; // which accumulator half the slot's next launch reads
         std::vector<std::vector<float>> outq; // per channel FIFO
         size_t outq_head = 0;
@@ -2007,6 +2010,10 @@ static int batch_enqueue(pv_batch *b, const InAddr &ia, float *d_out, int64_t ou
             HIPC(hipStreamWaitEvent(st, b->ev_res[ci & 3], 0));
     if ((rc = c.take_launch_error()) != PV_OK) return rc;
     HIPC(hipGetLastError());
+    if (count > 0) { // (host bookkeeping for pv_debug_batch_planes)
+        if (first == 0) b->tap_begin = 0;
+        b->tap_end = b->chunks[nchunks - 1].t0 + b->chunks[nchunks - 1].Tn;
+    }
     return PV_OK;
 }
 
@@ -2462,6 +2469,7 @@ int pv_feed(pv_engine *e, const float *const *in, int32_t n) {
             e->t_base = keep_from;
         }
     }
+    if (t_new1 > t_new0) e->tap_n = (int)std::min<int64_t>(t_new1 - t_new0, c.TR);
     // everything fed stays needed by later slices (at most 2N unconsumed): park it in the device ring
     if (e->uploaded < e->fed || !e->direct_out) { // (direct output: the last group's flag already covered the upload)
         if ((st = upload_until(e, in, call_base, e->fed)) != PV_OK) return fail(st);
@@ -2845,6 +2853,7 @@ static void pool_slot_begin(pv_pool *p, int32_t s, std::unique_ptr<Derived> own,
     sl.planner.reset(new Planner(*sl.d));
     sl.chain.reset(new ChainBuilder(*sl.d, c.chain_AR, c.chain_smask));
     sl.fed = sl.uploaded = sl.slices = 0;
+    sl.tap_n = 0;
     sl.acc_half = 0;
     sl.outq.assign((size_t)c.C, std::vector<float>());
     sl.outq_head = 0;
@@ -3509,7 +3518,11 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         g.ningest = (int)ingest.size();
         g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
     }
-    for (int32_t i = 0; i < count; ++i) p->slots[(size_t)slots[i]].slices += (int64_t)fresh[(size_t)i].size();
+    for (int32_t i = 0; i < count; ++i) {
+        pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+        sl.slices += (int64_t)fresh[(size_t)i].size();
+        if (!fresh[(size_t)i].empty()) sl.tap_n = (int)std::min<int64_t>((int64_t)fresh[(size_t)i].size(), c.TR);
+    }
     // int16 output: what the egress kernel converts, per entry
     int64_t egress_off = 0;
     int negress = 0, max_egress = 0;
@@ -3980,6 +3993,7 @@ int pv_pool_restore(pv_pool *p, int32_t count, const void *const *blobs, const i
         for (const snap::LiveFrame &f : hs.live) sl.chain->live.push_back(ChainBuilder::Live{f.P, f.flags});
         sl.chain->any_upper_skip = hs.any_upper_skip;
         sl.fed = hs.fed, sl.uploaded = hs.uploaded, sl.slices = hs.slices;
+        sl.tap_n = 0; // (a blob carries the recurrences' state, not the planes of its last launch)
         sl.acc_half = hs.acc_half;
         for (int ch = 0; ch < c.C && h.pending > 0; ++ch) {
             sl.outq[(size_t)ch].resize((size_t)h.pending);
@@ -4058,6 +4072,7 @@ struct pv_mbatch {
     };
     std::vector<Group> groups;
     int kernel_launches = 0; // kernels per run
+    bool tap_ran = false;    // pv_debug_mbatch_planes: a run since creation or the last redraw
     // what creation fixed (a redraw re-reads neither the arithmetic setting nor the environment)
     pv_config cfg{};
     int32_t block = 0, flush = 0;
@@ -4795,6 +4810,7 @@ int pv_mbatch_redraw(pv_mbatch *b, const pv_mbatch_stream *s) {
     b->groups = std::move(nb->groups);
     b->in_floats = nb->in_floats, b->out_floats = nb->out_floats, b->kernel_launches = nb->kernel_launches;
     b->pcm.resident = false; // (the next PCM run builds its job table for the new offsets)
+    b->tap_ran = false;      // (the planes still hold the previous draw's slices)
     b->plan_us = mb_us(t_begin, t_planned), b->host_us = mb_us(t_planned, t_host), b->device_us = mb_us(t_host, t_done);
     return PV_OK;
 }
@@ -4856,6 +4872,7 @@ int pv_mbatch_run(pv_mbatch *b, const float *d_in, float *d_out, void *hip_strea
     for (const pv_mbatch::Group &g : b->groups)
         if ((rc = mb_launch_group(b, g, d_in, d_out, st)) != PV_OK) return rc;
     HIPC(hipGetLastError());
+    b->tap_ran = true;
     return PV_OK;
 }
 
@@ -5041,6 +5058,128 @@ int pv_debug_pcm_ingest(const void *pcm, int32_t bits, int32_t channels, int64_t
 int pv_debug_pcm_egress(const float *planar, int32_t channels, int64_t frames, int16_t *pcm, int device) {
     const size_t samples = (size_t)(frames > 0 && channels > 0 ? frames * channels : 0);
     return mb_pcm_debug(planar, samples * sizeof(float), pcm, samples * 2, 2, channels, frames, false, device);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- plane tap (audiomod_pv.h pv_debug_*_planes)
+// Every object's Core keeps its planes as rings [rows][TR][HP] / [rows][TR][PKP], slice t of a row in slot t % TR
+// (launch_chunk, pool_feed and the mixed batch's builder all set s0 = t0 % TR).  The tap copies one slice of one row to
+// the host after the caller has waited for the object's work; it launches nothing.
+static void plane_info_of(const Core &c, int64_t begin, int64_t end, pv_plane_info *o) {
+    memset(o, 0, sizeof *o);
+    if (end - begin > c.TR) begin = end - c.TR;
+    o->slice_begin = begin, o->slice_end = end;
+    o->hs = c.d.hs;
+    o->peak_capacity = c.pkmax;
+    o->has_peaks = c.peaks.p && c.npk.p && c.modes.p && c.rot.p ? 1 : 0;
+    o->has_chain = c.outphase.p ? 1 : 0;
+}
+
+static int read_planes(const Core &c, int64_t row, int64_t t, int64_t begin, int64_t end, float *mag, float *phase,
+                       int32_t *npk, int32_t *peaks, int32_t *mode, float *rot, float *outphase) {
+    pv_plane_info pi;
+    plane_info_of(c, begin, end, &pi);
+    if (t < pi.slice_begin || t >= pi.slice_end) {
+        g_last_error = "plane tap: slice " + std::to_string(t) + " is not held: the row's readable slices are [" +
+                       std::to_string(pi.slice_begin) + ", " + std::to_string(pi.slice_end) + ")";
+        return PV_ERR_INVALID_ARG;
+    }
+    const int64_t plane = row * c.TR + t % c.TR;
+    const size_t H = (size_t)c.d.hs + 1;
+    if (mag) HIPC(hipMemcpy(mag, c.mag.p + plane * c.HP, H * sizeof(float), hipMemcpyDeviceToHost));
+    if (phase) HIPC(hipMemcpy(phase, c.phase.p + plane * c.HP, H * sizeof(float), hipMemcpyDeviceToHost));
+    int32_t n = 0, m = kModeProp; // (core mode 0: every step is a per-bin step)
+    if (pi.has_peaks) {
+        HIPC(hipMemcpy(&n, c.npk.p + plane, sizeof n, hipMemcpyDeviceToHost));
+        HIPC(hipMemcpy(&m, c.modes.p + plane, sizeof m, hipMemcpyDeviceToHost));
+        if (n < 0 || n > c.pkmax || m < kModeInit || m > kModeLock) {
+            g_last_error = "plane tap: slice " + std::to_string(t) + " holds peak count " + std::to_string(n) +
+                           " and mode " + std::to_string(m);
+            return PV_ERR_HIP;
+        }
+        if (npk) *npk = n;
+        if (mode) *mode = m;
+        if (peaks && n > 0) {
+            std::vector<uint16_t> pk((size_t)n);
+            HIPC(hipMemcpy(pk.data(), c.peaks.p + plane * c.PKP, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            for (int32_t i = 0; i < n; ++i) peaks[i] = pk[(size_t)i];
+        }
+        if (rot && m == kModeLock && n > 0)
+            HIPC(hipMemcpy(rot, c.rot.p + plane * c.PKP, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (outphase && pi.has_chain && m != kModeLock)
+        HIPC(hipMemcpy(outphase, c.outphase.p + plane * c.HP, (size_t)c.d.hs * sizeof(float), hipMemcpyDeviceToHost));
+    return PV_OK;
+}
+
+extern "C" {
+
+int pv_debug_batch_plane_info(const pv_batch *b, pv_plane_info *info) {
+    if (!b || !info) return PV_ERR_INVALID_ARG;
+    plane_info_of(b->core, b->tap_begin, b->tap_end, info);
+    return PV_OK;
+}
+int pv_debug_batch_planes(pv_batch *b, int32_t stream, int32_t channel, int64_t slice, float *mag, float *phase,
+                          int32_t *npk, int32_t *peaks, int32_t *mode, float *rot, float *outphase) {
+    g_last_error.clear();
+    if (!b || stream < 0 || stream >= b->core.S || channel < 0 || channel >= b->core.C) return PV_ERR_INVALID_ARG;
+    HIPC(hipSetDevice(b->core.device));
+    HIPC(hipDeviceSynchronize()); // (a batch runs on its caller's stream and on streams of its own)
+    return read_planes(b->core, (int64_t)stream * b->core.C + channel, slice, b->tap_begin, b->tap_end, mag, phase, npk,
+                       peaks, mode, rot, outphase);
+}
+
+int pv_debug_plane_info(const pv_engine *e, pv_plane_info *info) {
+    if (!e || !info) return PV_ERR_INVALID_ARG;
+    const int64_t end = e->t_base + (int64_t)e->recent.size();
+    plane_info_of(e->core, end - e->tap_n, end, info);
+    return PV_OK;
+}
+int pv_debug_planes(pv_engine *e, int32_t channel, int64_t slice, float *mag, float *phase, int32_t *npk, int32_t *peaks,
+                    int32_t *mode, float *rot, float *outphase) {
+    g_last_error.clear();
+    if (!e || channel < 0 || channel >= e->core.C) return PV_ERR_INVALID_ARG;
+    if (e->poisoned) return e->poisoned;
+    HIPC(hipSetDevice(e->core.device));
+    HIPC(hipStreamSynchronize(e->stream));
+    const int64_t end = e->t_base + (int64_t)e->recent.size();
+    return read_planes(e->core, channel, slice, end - e->tap_n, end, mag, phase, npk, peaks, mode, rot, outphase);
+}
+
+int pv_debug_pool_plane_info(const pv_pool *p, int32_t slot, pv_plane_info *info) {
+    if (!pool_slot_ok(p, slot) || !info) return PV_ERR_INVALID_ARG;
+    const pv_pool::Slot &sl = p->slots[(size_t)slot];
+    plane_info_of(p->core, sl.slices - sl.tap_n, sl.slices, info);
+    return PV_OK;
+}
+int pv_debug_pool_planes(pv_pool *p, int32_t slot, int32_t channel, int64_t slice, float *mag, float *phase, int32_t *npk,
+                         int32_t *peaks, int32_t *mode, float *rot, float *outphase) {
+    g_last_error.clear();
+    if (!pool_slot_ok(p, slot) || channel < 0 || channel >= p->core.C) return PV_ERR_INVALID_ARG;
+    if (p->poisoned) return p->poisoned;
+    HIPC(hipSetDevice(p->core.device));
+    HIPC(hipStreamSynchronize(p->stream)); // (device feeds may be in flight)
+    const pv_pool::Slot &sl = p->slots[(size_t)slot];
+    return read_planes(p->core, (int64_t)slot * p->core.C + channel, slice, sl.slices - sl.tap_n, sl.slices, mag, phase, npk,
+                       peaks, mode, rot, outphase);
+}
+
+int pv_debug_mbatch_plane_info(const pv_mbatch *b, int32_t stream, pv_plane_info *info) {
+    if (!mb_index_ok(b, stream) || !info) return PV_ERR_INVALID_ARG;
+    plane_info_of(b->dev->core, 0, b->tap_ran ? (int64_t)b->s[(size_t)stream].plan.slices.size() : 0, info);
+    return PV_OK;
+}
+int pv_debug_mbatch_planes(pv_mbatch *b, int32_t stream, int32_t channel, int64_t slice, float *mag, float *phase,
+                           int32_t *npk, int32_t *peaks, int32_t *mode, float *rot, float *outphase) {
+    g_last_error.clear();
+    if (!mb_index_ok(b, stream) || channel < 0 || channel >= b->dev->core.C) return PV_ERR_INVALID_ARG;
+    const Core &c = b->dev->core;
+    HIPC(hipSetDevice(c.device));
+    HIPC(hipDeviceSynchronize()); // (a mixed batch runs on its caller's stream)
+    return read_planes(c, (int64_t)stream * c.C + channel, slice, 0,
+                       b->tap_ran ? (int64_t)b->s[(size_t)stream].plan.slices.size() : 0, mag, phase, npk, peaks, mode, rot,
+                       outphase);
 }
 
 } // extern "C"

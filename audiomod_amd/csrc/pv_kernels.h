@@ -259,11 +259,16 @@ void chain_census_enable(bool on); // clears the table either way
 // kind: PV_CENSUS_CHAIN (a = NC, b = kPlainCore, c = kRes, d = kFast), PV_CENSUS_RESAMPLE (a = fast, b = interpolated),
 // PV_CENSUS_ANALYZE (a = NC, b = split), PV_CENSUS_PHASE (a = form, b = ring depth 4 / 8 or, for the forms without a
 // ring, peaks per lane 1 / 3), PV_CENSUS_RESAMPLE_RUNG (all four sets: a = rung kResRung*, b = interpolated, c = the
-// launch asked for more than 64 KB of LDS); -1 for a key that does not exist
+// launch asked for more than 64 KB of LDS), PV_CENSUS_ANALYSIS_KERNEL (all four sets: a = kAnaKernel*, b = NC 128 ...
+// 4096); -1 for a key that does not exist
 // The forms of the phase-locked stage (PV_PHASE_FORM_* of the C ABI): match kernel + ring chain kernel; match kernel +
 // chain kernel that loads one step ahead (pv_seq_kernel<1>, or <3> with three peaks per lane); match and ring chain in
 // one launch; the single-launch stream kernel.  Set: launch_seq / launch_phase / launch_stream count under batch.
 enum { kPhaseFormRing = 0, kPhaseFormStep = 1, kPhaseFormFused = 2, kPhaseFormStream = 3, kPhaseForms = 4 };
+// Which analysis kernel a launch is (PV_ANA_KERNEL_* of the C ABI): pv_analyze_kernel; a set's wave-per-frame kernel;
+// its kernel with a frame on two waves; pv_stream_kernel, which analyses inside the single launch.  launch_analyze
+// and launch_stream count under batch, launch_slot_analyze under its set.
+enum { kAnaKernelGeneric = 0, kAnaKernelWave = 1, kAnaKernelSplit = 2, kAnaKernelStream = 3, kAnaKernels = 4 };
 int64_t chain_census_count(int kind, int set, int a, int b, int c, int d);
 
 // pv_resample_kernel: one workgroup = 256 outputs of two rows

@@ -906,7 +906,12 @@ static void launch_maybe_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t 
     else hipLaunchKernelGGL(K, grid, block, lds, st, args...);
 }
 
+// (the census of the launchers' choices, below: which analysis kernel a launch is)
+static void census_analysis_kernel(int set, int kernel, int nc);
+
 void launch_analyze(const AnalyzeArgs &a, hipStream_t st) {
+    const bool wave = a.tb.nc == 256 || a.tb.nc == 512 || a.tb.nc == 1024 || a.tb.nc == 2048;
+    census_analysis_kernel(0, !wave ? kAnaKernelGeneric : a.tb.nc == 2048 && a.split ? kAnaKernelSplit : kAnaKernelWave, a.tb.nc);
     if (a.tb.nc == 512 || a.tb.nc == 256) { // fft 1024 / 512: four passes (pv_wavefft.h WF<512>, WF<256>)
         constexpr int WPB = 1;
         const int grid = 8 * ((a.rows + 7) / 8) * ((a.Tn + WPB - 1) / WPB);
@@ -3273,6 +3278,10 @@ static std::atomic<uint64_t> g_census_res[PV_CENSUS_SETS][2][2];
 static std::atomic<uint64_t> g_census_rrung[PV_CENSUS_SETS][kResRungs][2][2];
 static std::atomic<uint64_t> g_census_ana[PV_CENSUS_SETS][kCensusNc][2];
 static std::atomic<uint64_t> g_census_phase[PV_CENSUS_SETS][kPhaseForms][4];
+static std::atomic<uint64_t> g_census_akern[PV_CENSUS_SETS][kAnaKernels][6];
+static int census_akern_nc_index(int nc) { // fft / 2 of 256 ... 8192 points
+    return nc == 128 ? 0 : nc == 256 ? 1 : nc == 512 ? 2 : nc == 1024 ? 3 : nc == 2048 ? 4 : nc == 4096 ? 5 : -1;
+}
 static int census_phase_index(int b) { return b == 1 ? 0 : b == 3 ? 1 : b == 4 ? 2 : b == 8 ? 3 : -1; }
 static int census_nc_index(int nc) { return nc == 256 ? 0 : nc == 512 ? 1 : nc == 1024 ? 2 : nc == 2048 ? 3 : -1; }
 static inline void census_chain(int set, int nc, int plain_core, int res, bool fast) {
@@ -3295,6 +3304,10 @@ static void census_phase(int set, int form, int b) {
     if (!g_census_on.load(std::memory_order_relaxed)) return;
     g_census_phase[set][form][census_phase_index(b)].fetch_add(1, std::memory_order_relaxed);
 }
+static void census_analysis_kernel(int set, int kernel, int nc) {
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    if (census_akern_nc_index(nc) >= 0) g_census_akern[set][kernel][census_akern_nc_index(nc)].fetch_add(1, std::memory_order_relaxed);
+}
 void chain_census_enable(bool on) {
     g_census_on.store(false, std::memory_order_relaxed);
     for (auto &a : g_census_chain) for (auto &b : a) for (auto &c : b) for (auto &d : c) for (auto &e : d) e.store(0, std::memory_order_relaxed);
@@ -3302,6 +3315,7 @@ void chain_census_enable(bool on) {
     for (auto &a : g_census_rrung) for (auto &b : a) for (auto &c : b) for (auto &d : c) d.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_ana) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_phase) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
+    for (auto &a : g_census_akern) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     g_census_on.store(on, std::memory_order_relaxed);
 }
 int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
@@ -3323,6 +3337,9 @@ int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
     case 4:
         if (a < 0 || a >= kResRungs || !flag(b) || !flag(c)) return -1;
         return (int64_t)g_census_rrung[set][a][b][c].load(std::memory_order_relaxed);
+    case 5:
+        if (a < 0 || a >= kAnaKernels || census_akern_nc_index(b) < 0) return -1;
+        return (int64_t)g_census_akern[set][a][census_akern_nc_index(b)].load(std::memory_order_relaxed);
     default: return -1;
     }
 }
@@ -3952,6 +3969,7 @@ bool lds_starts_at_zero() {
 void launch_stream(const StreamArgs &s, hipStream_t st) {
     const size_t lds = stream_lds_bytes(s);
     if (s.coremode == 1) census_phase(0, kPhaseFormStream, 1); // (seq_role<1> on the kernel's 512 threads)
+    census_analysis_kernel(0, kAnaKernelStream, s.aa.tb.nc);
     if (s.aa.tb.nc == 1024) {
         launch_big_lds<pv_stream_kernel<1024>>(dim3(1), dim3(kStreamThreads), lds, st, s);
     } else {
@@ -4287,7 +4305,10 @@ __global__ __launch_bounds__(128) void pv_pool_analyze_split_kernel(const Analyz
 template <class Set> static bool launch_slot_analyze(const Set &set, const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st) {
     const dim3 grid(a.rows * p.max_tn, p.nslots);
     const size_t atab = 4 * PV_ATAN_BLOB_WORDS;
-    if (census_nc_index(a.tb.nc) >= 0) census_analyze(Set::census_set, a.tb.nc, a.tb.nc == 2048 && a.split);
+    if (census_nc_index(a.tb.nc) >= 0) {
+        census_analyze(Set::census_set, a.tb.nc, a.tb.nc == 2048 && a.split);
+        census_analysis_kernel(Set::census_set, a.tb.nc == 2048 && a.split ? kAnaKernelSplit : kAnaKernelWave, a.tb.nc);
+    }
     switch (a.tb.nc) {
     case 256: set.template wave<256, false>(grid, WF<256>::LDS_CF * sizeof(cf) + atab, st, a); return true;
     case 512: set.template wave<512, false>(grid, WF<512>::LDS_CF * sizeof(cf) + atab, st, a); return true;

@@ -87,6 +87,11 @@ class ResampleRung(C.Structure):
                 ("rung", C.c_int32), ("refused", C.c_int32), ("lds_bytes", C.c_int64)]
 
 
+class PlaneInfo(C.Structure):
+    _fields_ = [("slice_begin", C.c_int64), ("slice_end", C.c_int64), ("hs", C.c_int32), ("peak_capacity", C.c_int32),
+                ("has_peaks", C.c_int32), ("has_chain", C.c_int32)]
+
+
 _lib = None
 
 
@@ -222,6 +227,12 @@ def lib():
     L.pv_mbatch_debug_pcm_kernel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pv_debug_pcm_ingest.argtypes =[C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int]
     L.pv_debug_pcm_egress.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int]
+    for name, lead in (("pv_debug_batch", [C.c_int32]), ("pv_debug", []), ("pv_debug_pool", [C.c_int32]),
+                       ("pv_debug_mbatch", [C.c_int32])):
+        # (the batch's info call takes no stream: its rows share one range)
+        getattr(L, name + "_plane_info").argtypes = [C.c_void_p] + ([] if name == "pv_debug_batch" else lead) + [
+            C.POINTER(PlaneInfo)]
+        getattr(L, name + "_planes").argtypes = [C.c_void_p] + lead + [C.c_int32, C.c_int64] + [C.c_void_p] * 7
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -310,6 +321,25 @@ def chain_rung(arith, channels=2, **config):
     return {k: getattr(r, k) for k, _ in r._fields_}
 
 
+ANALYSIS_KERNELS = ("generic", "wave", "split", "stream")  # PV_ANA_KERNEL_*
+ANALYSIS_NC = (128, 256, 512, 1024, 2048, 4096)
+
+
+def analysis_census_read():
+    """The non-zero keys of the census' sixth kind, the analysis kernel of all four sets: {(set, kernel, nc): launches}
+    with `set` one of CENSUS_SETS ("batch" counts the batch path and the single-stream engine), `kernel` one of
+    ANALYSIS_KERNELS and nc half the fft size."""
+    count = lib().pv_debug_chain_census_count
+    out = {}
+    for i, name in enumerate(CENSUS_SETS):
+        for k, kernel in enumerate(ANALYSIS_KERNELS):
+            for nc in ANALYSIS_NC:
+                n = count(5, i, k, nc, 0, 0)
+                if n > 0:
+                    out[(name, kernel, nc)] = n
+    return out
+
+
 RES_RUNGS = ("ref4", "vec8", "vec16", "mfma", "vec2", "vec4")  # PV_RES_RUNG_*: the resampling kernels
 
 
@@ -343,6 +373,35 @@ def resample_rung(arith, rows, channels=2, **config):
     out = {k: getattr(r, k) for k, _ in r._fields_}
     out["rung"] = RES_RUNGS[r.rung] if r.rung >= 0 else None
     out["reason"] = L.pv_last_error().decode() if r.refused else ""
+    return out
+
+
+STEP_INIT, STEP_PROP, STEP_LOCK = 0, 1, 2  # PV_STEP_*
+
+
+def _plane_info(name, h, lead):
+    i = PlaneInfo()
+    _check(getattr(lib(), name + "_plane_info")(h, *lead, C.byref(i)), name + "_plane_info")
+    return {k: getattr(i, k) for k, _ in i._fields_}
+
+
+def _planes(name, h, lead, info, channel, t):
+    """One slice of one row through the plane tap (include/audiomod_pv.h pv_debug_*_planes), as a dict: mag, phase
+    [hs + 1]; with a peak search npk, mode, peaks [npk] and, for a locked step, rot [npk]; with a chain, for any other
+    step, outphase [hs].  What the step does not have is None."""
+    hs, cap = info["hs"], max(info["peak_capacity"], 1)
+    mag, phase = np.zeros(hs + 1, np.float32), np.zeros(hs + 1, np.float32)
+    npk, mode = C.c_int32(-1), C.c_int32(-1)
+    peaks, rot, outphase = np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(hs, np.float32)
+    _check(getattr(lib(), name + "_planes")(h, *lead, int(channel), int(t), mag.ctypes.data, phase.ctypes.data,
+                                            C.byref(npk), peaks.ctypes.data, C.byref(mode), rot.ctypes.data,
+                                            outphase.ctypes.data), name + "_planes")
+    out = dict(mag=mag, phase=phase, npk=None, mode=None, peaks=None, rot=None, outphase=None)
+    if info["has_peaks"]:
+        n = npk.value
+        out.update(npk=n, mode=mode.value, peaks=peaks[:n].copy(), rot=rot[:n].copy() if mode.value == STEP_LOCK else None)
+    if info["has_chain"] and not (info["has_peaks"] and mode.value == STEP_LOCK):
+        out["outphase"] = outphase
     return out
 
 
@@ -441,6 +500,14 @@ class PhaseVocoder:
         i = Info()
         _check(self.L.pv_get_info(self.h, C.byref(i)), "pv_get_info")
         return i.as_dict()
+
+    def plane_info(self):
+        """Diagnostics: which slices of a row the plane tap can read now, and which planes exist (pv_plane_info)"""
+        return _plane_info("pv_debug", self.h, ())
+
+    def planes(self, channel, t):
+        """Diagnostics: slice t of a channel's planes (see _planes); waits for the engine's stream"""
+        return _planes("pv_debug", self.h, (), self.plane_info(), channel, t)
 
     # ---- offline interface (modbase_offline)
     def processInData(self, inData):
@@ -560,6 +627,14 @@ class Batch:
         i = Info()
         _check(self.L.pv_batch_get_info(self.h, C.byref(i)), "pv_batch_get_info")
         return i.as_dict()
+
+    def plane_info(self):
+        """Diagnostics: which slices of a row the plane tap can read now, and which planes exist (pv_plane_info)"""
+        return _plane_info("pv_debug_batch", self.h, ())
+
+    def planes(self, stream, channel, t):
+        """Diagnostics: slice t of the planes of a stream's channel (see _planes); waits for the device"""
+        return _planes("pv_debug_batch", self.h, (int(stream),), self.plane_info(), channel, t)
 
     def alloc_out(self):
         import torch
@@ -716,6 +791,14 @@ class MixedBatch:
         inf = Info()
         _check(self.L.pv_mbatch_get_info(self.h, int(i), C.byref(inf)), "pv_mbatch_get_info")
         return inf.as_dict()
+
+    def plane_info(self, i):
+        """Diagnostics: which slices of stream i the plane tap can read now, and which planes exist (pv_plane_info)"""
+        return _plane_info("pv_debug_mbatch", self.h, (int(i),))
+
+    def planes(self, i, channel, t):
+        """Diagnostics: slice t of the planes of stream i's channel (see _planes); waits for the device"""
+        return _planes("pv_debug_mbatch", self.h, (int(i),), self.plane_info(i), channel, t)
 
     def alloc_out(self):
         import torch
@@ -1064,6 +1147,14 @@ class StreamPool:
         i = Info()
         _check(self.L.pv_pool_get_info(self.h, int(slot), C.byref(i)), "pv_pool_get_info")
         return i.as_dict()
+
+    def plane_info(self, slot):
+        """Diagnostics: which slices of a slot the plane tap can read now, and which planes exist (pv_plane_info)"""
+        return _plane_info("pv_debug_pool", self.h, (int(slot),))
+
+    def planes(self, slot, channel, t):
+        """Diagnostics: slice t of the planes of a slot's channel (see _planes); waits for the pool's stream"""
+        return _planes("pv_debug_pool", self.h, (int(slot),), self.plane_info(slot), channel, t)
 
     def last_timing(self):
         """(host_us, wait_us) of the last feed(): host work up to the wait for the device, and that wait (0 after a

@@ -561,6 +561,10 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
  *   PV_CENSUS_PHASE    : the phase-locked stage (core mode 1): a = form (PV_PHASE_FORM_*), b = the ring's depth (4 / 8)
  *                        or, for the forms without a ring, the peaks one lane holds (1 / 3).  The batch set counts the
  *                        batch path and the single-stream engine; c and d are ignored
+ *   PV_CENSUS_ANALYSIS_KERNEL : the analysis kernel of all four sets: a = the kernel launched (PV_ANA_KERNEL_*), b = NC
+ *                        (fft size / 2: 128 ... 4096).  The batch set counts the batch path and the single-stream
+ *                        engine, the vocoder modes' carrier launch included.  Read through the call only: neither
+ *                        census file lists it.  PV_CENSUS_ANALYZE stays what it was
  * Process-wide and off by default (a launch then tests one flag).  pv_debug_chain_census(on) clears the counts and
  * switches counting on or off; pv_debug_chain_census_count returns a key's count, -1 for a key that does not exist.
  * If the environment variable AUDIOMOD_PV_CHAIN_CENSUS names a file when the library is loaded, the census is on from
@@ -572,6 +576,11 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
 #define PV_CENSUS_ANALYZE 2
 #define PV_CENSUS_PHASE 3
 #define PV_CENSUS_RESAMPLE_RUNG 4
+#define PV_CENSUS_ANALYSIS_KERNEL 5
+#define PV_ANA_KERNEL_GENERIC 0 /* pv_analyze_kernel: LDS butterflies, any size (fft 256 and 8192) */
+#define PV_ANA_KERNEL_WAVE 1    /* a frame per wave (fft 512 ... 4096): pv_analyze_wave_kernel, pv_pool_ / pv_pmix_ / pv_mb_ */
+#define PV_ANA_KERNEL_SPLIT 2   /* a 4096-point frame on two waves */
+#define PV_ANA_KERNEL_STREAM 3  /* the single-launch stream kernel of the drop-in path */
 #define PV_RES_RUNG_REF4 0  /* the reference's operation order, four rows per workgroup (PV_ARITH_EXACT) */
 #define PV_RES_RUNG_VEC8 1  /* free-form, vector ALU, eight rows per workgroup */
 #define PV_RES_RUNG_VEC16 2 /* ... sixteen rows (AUDIOMOD_PV_RES_MFMA=0 only: the matrix-core kernel fits wherever it does) */
@@ -609,6 +618,47 @@ typedef struct pv_resample_rung {
     int64_t lds_bytes;
 } pv_resample_rung;
 int pv_debug_resample_rung(const pv_config *cfg, int arith, int32_t rows, pv_resample_rung *out);
+
+/* Diagnostics: a read-only tap on the planes the analysis and the phase stage leave in device memory, for the batch,
+ * the single-stream engine, a pool slot and a mixed batch's stream.  Every object keeps them as rings over the slices
+ * of a row (one row per stream and channel); a call waits for the object's work (the engine's and the pool's own
+ * stream; the whole device for the two batch objects, which run on their caller's stream), copies one slice of one
+ * row to the host and launches nothing.
+ *   pv_debug_*_plane_info : which slices of a row can be read now, [slice_begin, slice_end) -- the slices of the
+ *       object's most recent run (batch: since launch 0, spans included; mixed batch), call that launched any (engine) or
+ *       feed that launched any for the slot (pool), as far as the ring holds them: the last ones of a longer run.  Empty
+ *       before the first run, after pv_mbatch_redraw, and for a slot just opened or restored.  hs = fft size / 2;
+ *       peak_capacity: the most peaks a step lists; has_peaks: the configuration searches peaks and has step modes
+ *       (the phase-locked core mode of the modes with a phase recurrence); has_chain: it has an output-phase plane
+ *       (core modes 0 and 1 of those modes).  Without either, only mag and phase are returned and the other pointers
+ *       are ignored.
+ *   pv_debug_*_planes : for slice `slice` of the row, into every non-null pointer:
+ *       mag, phase   hs + 1 floats each, as the analysis kernel stored them (FORMANT_CEPSTRAL shifts mag in place)
+ *       npk, mode    the step's peak count and PV_STEP_INIT / PROP / LOCK
+ *       peaks        npk bins (room for peak_capacity)
+ *       rot          a locked step's npk rotations (room for peak_capacity); untouched for any other step
+ *       outphase     hs floats for an initial or per-bin step (every step of core mode 0); untouched for a locked one
+ *     List slots beyond npk hold whatever the kernels left there and are not returned.  A slice outside the readable
+ *     range is PV_ERR_INVALID_ARG with the range in pv_last_error(); nothing is copied then. */
+#define PV_STEP_INIT 0
+#define PV_STEP_PROP 1
+#define PV_STEP_LOCK 2
+typedef struct pv_plane_info {
+    int64_t slice_begin, slice_end;
+    int32_t hs, peak_capacity, has_peaks, has_chain;
+} pv_plane_info;
+int pv_debug_batch_plane_info(const pv_batch *b, pv_plane_info *info);
+int pv_debug_batch_planes(pv_batch *b, int32_t stream, int32_t channel, int64_t slice, float *mag, float *phase,
+                          int32_t *npk, int32_t *peaks, int32_t *mode, float *rot, float *outphase);
+int pv_debug_plane_info(const pv_engine *e, pv_plane_info *info);
+int pv_debug_planes(pv_engine *e, int32_t channel, int64_t slice, float *mag, float *phase, int32_t *npk, int32_t *peaks,
+                    int32_t *mode, float *rot, float *outphase);
+int pv_debug_pool_plane_info(const pv_pool *p, int32_t slot, pv_plane_info *info);
+int pv_debug_pool_planes(pv_pool *p, int32_t slot, int32_t channel, int64_t slice, float *mag, float *phase, int32_t *npk,
+                         int32_t *peaks, int32_t *mode, float *rot, float *outphase);
+int pv_debug_mbatch_plane_info(const pv_mbatch *b, int32_t stream, pv_plane_info *info);
+int pv_debug_mbatch_planes(pv_mbatch *b, int32_t stream, int32_t channel, int64_t slice, float *mag, float *phase,
+                           int32_t *npk, int32_t *peaks, int32_t *mode, float *rot, float *outphase);
 
 #define PV_WIRE_F32 0
 #define PV_WIRE_I16 1

@@ -62,6 +62,9 @@ def lib():
         L.pvo_get_increments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
         L.pvo_get_phase_trace.restype = C.c_long
         L.pvo_get_phase_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+        L.pvo_enable_plane_trace.argtypes = [C.c_void_p]
+        L.pvo_get_plane_trace.restype = C.c_long
+        L.pvo_get_plane_trace.argtypes = [C.c_void_p, C.c_long, C.c_long] + [C.c_void_p] * 7
         L.pvo_hann.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.pvo_forward_polar.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pvo_inverse_polar.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -90,10 +93,11 @@ class Oracle:
     """Streaming handle mirroring audiomod::phasevocoder's offline + real-time drive."""
 
     def __init__(self, channels, mode="normal_pitchshift", semitones=0.0, time_ratio=1.0, coremode=1,
-                 fftsize=2048, sample_rate=48000, hopsize=0, trig_nudge=0.0, nudge_seed=1):
+                 fftsize=2048, sample_rate=48000, hopsize=0, trig_nudge=0.0, nudge_seed=1, planes=False):
         """trig_nudge (test model, pv_oracle.h pvo_set_synth_trig_nudge): every synthesis sine / cosine off by
         +-trig_nudge, signs from a generator seeded with nudge_seed; 0.0 is the reference, bit for bit.  run_offline /
-        run_realtime pass both through."""
+        run_realtime pass both through.  planes: record every step's planes for plane_trace() (pv_oracle.h
+        pvo_enable_plane_trace); off by default, and the arithmetic is the same either way."""
         self.L = lib()
         m = MODES[mode] if isinstance(mode, str) else int(mode)
         self.cfg = Config(sample_rate, channels, time_ratio, semitones, m, coremode, fftsize, hopsize)
@@ -101,6 +105,8 @@ class Oracle:
         self.channels = channels
         if trig_nudge:
             self.L.pvo_set_synth_trig_nudge(self.h, float(trig_nudge), int(nudge_seed))
+        if planes:
+            assert self.L.pvo_enable_plane_trace(self.h) == 0
 
     def close(self):
         if self.h:
@@ -149,15 +155,36 @@ class Oracle:
         self.L.pvo_get_phase_trace(self.h, k.ctypes.data, m.ctypes.data, n)
         return k, m
 
+    def plane_trace(self):
+        """The planes of every step of phase_trace(), in the same order, as a dict of arrays with one row per step
+        (pv_oracle.h pvo_get_plane_trace): re, im, mag, phase [steps, hs + 1] float32; npk, mode [steps]; peaks
+        [steps, hs + 1] int32 and rot [steps, hs + 1] (npk entries of a row count, rot only in locked steps); outphase
+        [steps, hs].  Needs Oracle(planes=True)."""
+        n = self.L.pvo_get_plane_trace(self.h, 0, 0, *([None] * 7))
+        if n < 0:
+            raise RuntimeError("the plane trace was not switched on: Oracle(planes=True)")
+        H = self.info()["fftsize"] // 2 + 1
+        f = {k: np.zeros((n, H), np.float32) for k in ("re", "im", "mag", "phase", "rot", "outphase")}
+        peaks = np.zeros((n, H), np.int32)
+        got = self.L.pvo_get_plane_trace(self.h, 0, n, f["re"].ctypes.data, f["im"].ctypes.data, f["mag"].ctypes.data,
+                                         f["phase"].ctypes.data, peaks.ctypes.data, f["rot"].ctypes.data,
+                                         f["outphase"].ctypes.data)
+        assert got == n
+        f["outphase"] = np.ascontiguousarray(f["outphase"][:, :H - 1])
+        f["peaks"] = peaks
+        f["npk"], f["mode"] = self.phase_trace()
+        return f
 
-def run_offline(x, block=480, flush=True, trace=False, **kw):
+
+def run_offline(x, block=480, flush=True, trace=False, planes=False, **kw):
     """The reference CLI's offline drive loop (main/main.cc:471-510) on the oracle.
     x: float32 [channels, frames].  Returns (out [channels, n], per-call counts, info); with trace=True the info
     carries "trace": Oracle.phase_trace() of the whole run, and "flush_step": its length before the first all-zero
-    flush block was fed."""
+    flush block was fed.  planes=True (implies trace): also "planes": Oracle.plane_trace()."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     ch, frames = x.shape
-    o = Oracle(ch, **kw)
+    trace = trace or planes
+    o = Oracle(ch, planes=planes, **kw)
     outs, counts = [], []
     produced = 0
     for i in range(0, frames, block):
@@ -179,6 +206,8 @@ def run_offline(x, block=480, flush=True, trace=False, **kw):
     if trace:
         info["trace"] = o.phase_trace()
         info["flush_step"] = flush_step
+    if planes:
+        info["planes"] = o.plane_trace()
     o.close()
     return np.concatenate(outs, axis=1), counts, info
 

@@ -663,6 +663,9 @@ struct pvo {
     /* record of increments for planner pinning */
     int *rec_shift, *rec_phase; long nrec, caprec;
     int *tr_npk, *tr_mode; long ntr, captr; /* pvo_get_phase_trace */
+    /* pvo_enable_plane_trace: per step six rows of H = N/2+1 floats (re, im, mag, phase, rot, outphase) and one of H
+     * ints (the peak list), at the step's index of the trace above */
+    int pl_on; float *pl_f; int *pl_peaks; long pl_cap;
     /* set once a slice's shift increment exceeds N: writeSlice (phasevocoderprocess.cc:1181-1190) then calls
      * memmove with (N - shiftIncrement) wrapped to a huge size_t -- undefined behaviour in the reference, only
      * reachable with a caller-chosen hop.  The oracle stops there instead of reproducing the overflow. */
@@ -827,6 +830,7 @@ void pvo_destroy(pvo *h) {
     free(h->ch); free(h->win); free(h->peak); free(h->prev_peak); free(h->resamplebuf);
     free(h->rec_shift); free(h->rec_phase);
     free(h->tr_npk); free(h->tr_mode);
+    free(h->pl_f); free(h->pl_peaks);
     free(h);
 }
 
@@ -889,6 +893,8 @@ static void modify_simple(pvo *h, chan *a, size_t phaseIncrement) {
 }
 
 static void record_trace(pvo *h, int npk, int mode);
+static float *plane_row(pvo *h, int which);
+enum { PL_RE, PL_IM, PL_MAG, PL_PHASE, PL_ROT, PL_OUT, PL_ROWS };
 
 /* phasevocoderprocess.cc:574-706 */
 static void modify_locked(pvo *h, chan *a, size_t phaseIncrement) {
@@ -905,6 +911,15 @@ static void modify_locked(pvo *h, chan *a, size_t phaseIncrement) {
         }
     }
     record_trace(h, h->npeak, h->firstentry ? 0 : (h->npeak == 0 || h->nprev_peak == 0) ? 1 : 2);
+    if (h->pl_on) { /* the step's analysis, before the branches below overwrite a->phase */
+        for (int i = 0; i <= hs; ++i) {
+            plane_row(h, PL_RE)[i] = a->fft->packed[i].r;
+            plane_row(h, PL_IM)[i] = a->fft->packed[i].i;
+        }
+        memcpy(plane_row(h, PL_MAG), a->mag, sizeof(float) * (hs + 1));
+        memcpy(plane_row(h, PL_PHASE), a->phase, sizeof(float) * (hs + 1));
+        memcpy(h->pl_peaks + (h->ntr - 1) * (long)(hs + 1), h->peak, sizeof(int) * h->npeak);
+    }
     if (h->firstentry) {
         init_bins(h, a);
     } else if (h->npeak == 0 || h->nprev_peak == 0) {
@@ -923,6 +938,7 @@ static void modify_locked(pvo *h, chan *a, size_t phaseIncrement) {
             float peak_delta_phi = pomega + pvo_princarg(a->phase[p2] - a->prev_phase[p1] - pomega);
             float peak_target_phase = pvo_princarg(a->prev_outphase[p1] + (peak_delta_phi * phaseIncrement) / h->hop);
             float rot = pvo_princarg(peak_target_phase - a->phase[p2]);
+            if (h->pl_on) plane_row(h, PL_ROT)[p] = rot;
             int bin1 = 0, bin2 = 0;
             if (h->npeak == 1) {
                 bin1 = 0; bin2 = hs;
@@ -942,6 +958,7 @@ static void modify_locked(pvo *h, chan *a, size_t phaseIncrement) {
             a->phase[i] = a->locked_phase[i];
         }
     }
+    if (h->pl_on) memcpy(plane_row(h, PL_OUT), a->prev_outphase, sizeof(float) * hs);
     memcpy(h->prev_peak, h->peak, sizeof(int) * h->npeak);
     h->nprev_peak = h->npeak;
     h->firstentry = 0;
@@ -1110,6 +1127,21 @@ static void record_trace(pvo *h, int npk, int mode) {
     h->tr_npk[h->ntr] = npk;
     h->tr_mode[h->ntr] = mode;
     h->ntr++;
+    if (h->pl_on && h->ntr > h->pl_cap) { /* (zero-filled: what a step does not write reads as 0) */
+        const long H = (long)h->N / 2 + 1, cap = h->pl_cap ? h->pl_cap * 2 : 64;
+        h->pl_f = (float *)realloc(h->pl_f, sizeof(float) * PL_ROWS * H * cap);
+        h->pl_peaks = (int *)realloc(h->pl_peaks, sizeof(int) * H * cap);
+        if (!h->pl_f || !h->pl_peaks) abort();
+        memset(h->pl_f + PL_ROWS * H * h->pl_cap, 0, sizeof(float) * PL_ROWS * H * (cap - h->pl_cap));
+        memset(h->pl_peaks + H * h->pl_cap, 0, sizeof(int) * H * (cap - h->pl_cap));
+        h->pl_cap = cap;
+    }
+}
+
+/* row `which` of the step recorded last */
+static float *plane_row(pvo *h, int which) {
+    const long H = (long)h->N / 2 + 1;
+    return h->pl_f + ((h->ntr - 1) * PL_ROWS + which) * H;
 }
 
 /* phasevocoderprocess.cc:236-287 + :305-376 + :412-489 */
@@ -1356,6 +1388,27 @@ long pvo_get_phase_trace(const pvo *h, int *npk, int *mode, long max) {
     long n = h->ntr < max ? h->ntr : max;
     if (npk) memcpy(npk, h->tr_npk, sizeof(int) * n);
     if (mode) memcpy(mode, h->tr_mode, sizeof(int) * n);
+    return h->ntr;
+}
+
+int pvo_enable_plane_trace(pvo *h) {
+    if (h->ntr != 0) return -1;
+    h->pl_on = 1;
+    return 0;
+}
+
+long pvo_get_plane_trace(const pvo *h, long first, long count, float *re, float *im, float *mag, float *phase,
+                         int *peaks, float *rot, float *outphase) {
+    if (!h->pl_on) return -1;
+    const long H = (long)h->N / 2 + 1;
+    if (first < 0 || count < 0 || first > h->ntr) return h->ntr;
+    if (count > h->ntr - first) count = h->ntr - first;
+    float *dst[PL_ROWS] = {re, im, mag, phase, rot, outphase};
+    for (long s = 0; s < count; ++s) {
+        for (int w = 0; w < PL_ROWS; ++w)
+            if (dst[w]) memcpy(dst[w] + s * H, h->pl_f + ((first + s) * PL_ROWS + w) * H, sizeof(float) * H);
+        if (peaks) memcpy(peaks + s * H, h->pl_peaks + (first + s) * H, sizeof(int) * H);
+    }
     return h->ntr;
 }
 

@@ -72,6 +72,18 @@ long pvo_get_increments(const pvo *h, int *shift, int *phase, long max);
  * copies at most max of them */
 enum { PVO_TRACE_INIT = 0, PVO_TRACE_PROP = 1, PVO_TRACE_LOCK = 2 };
 long pvo_get_phase_trace(const pvo *h, int *npk, int *mode, long max);
+/* Opt-in: the planes of every step of the trace above, H = fftsize / 2 + 1 values a row.  Switch it on before the
+ * first pvo_process (returns -1 once a step has been recorded); the arithmetic is the same either way.  Per step:
+ *   re, im    the spectrum as it is handed to the polar conversion
+ *   mag, phase  what the conversion makes of it (the analysis planes)
+ *   peaks     the peak list, npk entries (pvo_get_phase_trace), zeros behind them
+ *   rot       locked steps: the rotation of each peak's region, npk entries; zeros otherwise
+ *   outphase  the output phases the step leaves for the next one (prev_outphase), bins 0 ... H - 2; bin H - 1 is 0
+ * pvo_get_plane_trace copies steps [first, first + count) (clipped to what exists) into every non-null array, `count`
+ * rows of H each, and returns the number of steps recorded so far; -1 where the planes were never switched on. */
+int pvo_enable_plane_trace(pvo *h);
+long pvo_get_plane_trace(const pvo *h, long first, long count, float *re, float *im, float *mag, float *phase,
+                         int *peaks, float *rot, float *outphase);
 
 /* unit-level entry points (pinned by tests/golden KATs) */
 void pvo_hann(int n, float *w, float *area);

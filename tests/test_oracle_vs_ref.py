@@ -40,6 +40,27 @@ def test_offline_matches_reference(kw):
     assert bits_equal(got, want)
 
 
+# The level cases of tests/analysis_signals.py (voice times a power of two: components below 2^-48, subnormal and
+# underflowing squares, components above 2^63; a DC offset; holes) and the peak search's corner cases: where the plane
+# tests find the device and the oracle apart, this says which of the two the reference sides with.
+LEVEL_FFTS = (512, 1024, 4096)
+
+
+@pytest.mark.parametrize("fft", LEVEL_FFTS)
+@pytest.mark.parametrize("kind", ["ordinary", "mixed", "out", "subnormal", "zero", "loud", "dc", "holes", "corners",
+                                  "outer", "dcnyq", "single"])
+def test_level_and_corner_cases_match_reference(kind, fft):
+    from tests import analysis_signals as A
+    c = A.BY_NAME[f"{kind}_{fft}"]
+    for j in (0, 1):
+        x = A.streams(c.name)[j]
+        want, wc = O.ref_run(x, block=A.BLOCK, fftsize=fft, **c.cfg)
+        got, gc, _ = A.oracle(c.name, j)
+        assert list(gc) == wc
+        assert bits_equal(got, want)
+        assert np.isfinite(want).all() and (kind == "zero" or np.abs(want).max() > 0)
+
+
 def test_realtime_matches_reference():
     x = signals.noise(20000, 2)
     want, wc = O.ref_run(x, api="rt", semitones=-7.0, block=512)
