@@ -13,13 +13,15 @@
 //   audiomod-pv-exe robotic | whisper | vocoder | vocoder_chord   in.wav out.wav
 //   audiomod-pv-exe constant           in.wav out.wav      (real-time processBlock loop, main.cc:561-572)
 // Effects of the reference that are not phase-vocoder modes are not provided here.
+// An extension of this engine: time_stretch and normal_pitchshift take a trailing  --formant <semitones>, the formant
+// setting of audiomod_pv.h (0: the formants stay where they are whatever the pitch does).
 //
 // An extension of this engine: a folder of files in one process,
-//   audiomod-pv-exe batch <dafx_name> <manifest> [<amount> <coremode> <fftsize>] [--mem-gb G]
+//   audiomod-pv-exe batch <dafx_name> <manifest> [<amount> <coremode> <fftsize>] [--mem-gb G] [--formant <semitones>]
 // The manifest has one job per line, in.wav<TAB>out.wav[<TAB>amount]; every output file is byte for byte what the
 // single-file command writes for that file and amount.  Jobs of equal sample rate and channel count run together
 // through the mixed batch's PCM wire (pv_mbatch_run_pcm_host) wherever the mixed batch serves the configuration, and
-// one by one through the single-file route below where it does not.  stdout: one line per job, in manifest order,
+// one by one through the single-file route below where it does not.  --formant is one value for all jobs.  stdout: one line per job, in manifest order,
 // ok<TAB>out.wav<TAB>frames or failed<TAB>in.wav<TAB>reason.  Exit status 0, 1 if a job failed, 2 for a bad manifest.
 #include <cstdint>
 #include <cstdio>
@@ -43,7 +45,8 @@ int usage() {
     fprintf(stderr,
             "usage: audiomod-pv-exe dafx_name infile outfile <args> (dafx: constant, time_stretch, normal_pitchshift, "
             "formant_pitchshift, gender_change, vocoder, vocoder_chord, robotic, whisper)\n"
-            "       audiomod-pv-exe batch dafx_name manifest [<amount> <coremode> <fftsize>] [--mem-gb G]\n");
+            "       audiomod-pv-exe batch dafx_name manifest [<amount> <coremode> <fftsize>] [--mem-gb G] [--formant st]\n"
+            "       time_stretch and normal_pitchshift take a trailing --formant <semitones>\n");
     return -1;
 }
 
@@ -72,10 +75,33 @@ const Model *find_model(const std::string &name) {
     return nullptr;
 }
 
+// --formant <semitones>: the formant setting, for the two plain modes
+struct Formant {
+    bool on = false;
+    float semitones = 0.f;
+};
+// argv[i] is "--formant": reads its value into fx; false (with a line on stderr) for a missing or bad one, or a model
+// the setting does not apply to
+bool parse_formant(const std::string &model, int argc, char **argv, int i, Formant &fx) {
+    char *e = nullptr;
+    const double v = i + 1 < argc ? strtod(argv[i + 1], &e) : 0.0;
+    if (i + 1 >= argc || e == argv[i + 1] || *e != 0 || !(v >= -48.0 && v <= 48.0)) {
+        fprintf(stderr, "audiomod-pv-exe: --formant needs a number of semitones within +-48\n");
+        return false;
+    }
+    if (model != "time_stretch" && model != "normal_pitchshift") {
+        fprintf(stderr, "audiomod-pv-exe: --formant applies to time_stretch and normal_pitchshift only\n");
+        return false;
+    }
+    fx.on = true;
+    fx.semitones = (float)v;
+    return true;
+}
+
 // The single-file command: one fresh engine, the reference's drive loop.  args: what follows the two paths on the
 // command line.  Throws what the reader, the writer and the class throw; *written: frames written to out_path.
 int run_single(const std::string &model, const char *in_path, const char *out_path, int nargs, const char *const *args,
-               long *written) {
+               long *written, const Formant &fx) {
     WavIn in(in_path);
     const int ch = in.channels, sr = in.rate;
     const long file_length = in.frames;
@@ -102,6 +128,7 @@ int run_single(const std::string &model, const char *in_path, const char *out_pa
         fprintf(stderr, "fx not supported by the MI355X phase-vocoder driver: %s\n", model.c_str());
         return usage();
     }
+    if (fx.on) pv->setParams({{"formant_semitones", fx.semitones}});
     modbase_offline *off = pv.get();
     WavOut16 out(out_path, sr, ch);
     const int block = pvcli::block_size(sr);
@@ -180,7 +207,7 @@ std::string engine_error(int st) { return std::string(pv_strerror(st)) + ": " + 
 
 // one group (equal rate and channels) of jobs the mixed batch accepts, sub-batch by sub-batch
 void run_group_batched(const Model &model, const pv_config &cfg, std::vector<BatchJob *> &jobs, float amount, int64_t budget,
-                       int device) {
+                       int device, const Formant &fx) {
     const int C = cfg.channels, block = pvcli::block_size(cfg.sample_rate), flush = model.stretch ? 0 : 1;
     std::vector<pvcli::ClipSize> sizes;
     for (const BatchJob *j : jobs) sizes.push_back(pvcli::ClipSize{j->frames, j->out_frames, j->bits / 8});
@@ -211,6 +238,10 @@ void run_group_batched(const Model &model, const pv_config &cfg, std::vector<Bat
             mb = nullptr;
             st = pv_mbatch_create(&cfg, streams.data(), (int32_t)n, block, flush, device, &mb);
             mb_clips = n;
+        }
+        if (st == PV_OK && fx.on) { // (a re-drawn object is back to off, like a new one)
+            const std::vector<float> knob(n, fx.semitones);
+            st = pv_mbatch_set_formant(mb, knob.data());
         }
         if (st != PV_OK) {
             fail_all(engine_error(st));
@@ -276,8 +307,12 @@ int batch_main(int argc, char **argv) {
     }
     std::vector<const char *> pos;
     double mem_gb = 16.0;
+    Formant fx;
     for (int i = 4; i < argc; ++i) {
-        if (!strcmp(argv[i], "--mem-gb")) {
+        if (!strcmp(argv[i], "--formant")) {
+            if (!parse_formant(model_name, argc, argv, i, fx)) return usage();
+            ++i;
+        } else if (!strcmp(argv[i], "--mem-gb")) {
             char *e = nullptr;
             if (i + 1 >= argc || (mem_gb = strtod(argv[i + 1], &e), *e != 0) || !(mem_gb > 0) || mem_gb > 1e6) {
                 fprintf(stderr, "audiomod-pv-exe: --mem-gb needs a positive number of GiB\n");
@@ -362,14 +397,14 @@ int batch_main(int argc, char **argv) {
                 batched.push_back(&j);
             }
         }
-        if (!batched.empty()) run_group_batched(*model, cfg, batched, amount, budget, device);
+        if (!batched.empty()) run_group_batched(*model, cfg, batched, amount, budget, device, fx);
     }
     for (BatchJob &j : jobs) {
         if (j.failed || j.done || j.batch_route) continue;
         const std::string a = j.m.has_amount ? j.m.amount_text : std::string(model->takes_args ? pos[0] : "");
         const char *args[3] = {a.c_str(), model->takes_args ? pos[1] : "", model->takes_args ? pos[2] : ""};
         try {
-            const int rc = run_single(model_name, j.m.in.c_str(), j.m.out.c_str(), model->takes_args ? 3 : 0, args, &j.written);
+            const int rc = run_single(model_name, j.m.in.c_str(), j.m.out.c_str(), model->takes_args ? 3 : 0, args, &j.written, fx);
             if (rc == 0) j.done = true;
             else j.fail("the single-file route refused the job");
         } catch (const std::exception &e) {
@@ -403,8 +438,18 @@ int main(int argc, char **argv) {
         }
     }
     if (argc < 4) return usage();
+    Formant fx;
+    std::vector<const char *> args;
+    for (int i = 4; i < argc; ++i) {
+        if (!strcmp(argv[i], "--formant")) {
+            if (!parse_formant(argv[1], argc, argv, i, fx)) return usage();
+            ++i;
+        } else {
+            args.push_back(argv[i]);
+        }
+    }
     try {
-        return run_single(argv[1], argv[2], argv[3], argc - 4, argv + 4, nullptr);
+        return run_single(argv[1], argv[2], argv[3], (int)args.size(), args.data(), nullptr, fx);
     } catch (const std::exception &e) {
         fprintf(stderr, "audiomod-pv-exe: %s\n", e.what());
         return 1;

@@ -24,7 +24,7 @@ static bool served_by_process_normal(int mode) {
 
 phasevocoder::phasevocoder(int sampleRate, int numChannels, float timeratio, float pitchshift, int mode,
                            int coremode, int fftsize, int hopsize)
-    : engine_(nullptr), mode_(mode), outready_(false) {
+    : engine_(nullptr), mode_(mode), outready_(false), formant_on_(false), formant_semitones_(0.f) {
     modbase::sample_rate_ = sampleRate;
     modbase::num_channels_ = numChannels;
     modbase_offline::sample_rate_ = sampleRate;
@@ -57,6 +57,23 @@ phasevocoder::~phasevocoder() {
 // call the engine refuses leaves it untouched (pv_feed is transactional), the caller sees no new samples.
 static void report(const char *where, int st) {
     std::fprintf(stderr, "audiomod::phasevocoder (MI355X engine): %s: %s: %s\n", where, pv_strerror(st), pv_last_error());
+}
+
+void phasevocoder::setParams(std::map<std::string, float> params) {
+    const auto it = params.find("formant_semitones");
+    if (it == params.end()) return;
+    const bool on = it->second == it->second; // (NaN: off)
+    const int st = pv_set_formant(engine_, on ? 1 : 0, on ? it->second : 0.f);
+    if (st != PV_OK) {
+        report("setParams", st);
+        return;
+    }
+    formant_on_ = on;
+    formant_semitones_ = on ? it->second : 0.f;
+}
+
+void phasevocoder::getParams(std::map<std::string, float> &params) {
+    if (formant_on_) params["formant_semitones"] = formant_semitones_;
 }
 
 void phasevocoder::processInData(float *const *inData, int num_in_samples) {

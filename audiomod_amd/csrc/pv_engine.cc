@@ -11,6 +11,7 @@
 #include <cmath>
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -400,6 +401,13 @@ struct Core {
         return on;
     }
 #endif
+    // The formant setting (pv_set_formant / pv_batch_set_formant): the cepstral stage of mode FORMANT_CEPSTRAL as a
+    // run-time setting of the plain modes, with its own env_comp.  The stage runs where d.cepstral says so or where the
+    // setting is on and moves the envelope at all.
+    bool fx_on = false;
+    float fx_env_comp = 1.0f;
+    bool cepstral_on() const { return d.cepstral || (fx_on && fx_env_comp != 1.0f); }
+    float cepstral_env_comp() const { return d.cepstral ? d.env_comp : fx_env_comp; }
     mutable hipError_t launch_err = hipSuccess; // first HIP failure inside launch_chunk since take_launch_error()
     mutable int launch_err_line = 0;
     int take_launch_error() const {
@@ -1149,14 +1157,14 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
     sa.s0 = s0;
     sa.Tn = Tn;
     sa.phase_inc = d_pinc;
-    if (d.cepstral && !only_resample) {
+    if (cepstral_on() && !only_resample) {
         CepstralArgs ca{};
         ca.tb = tb;
         ca.Tn = Tn;
         ca.TR = TR;
         ca.rows = rows;
         ca.s0 = s0;
-        ca.env_comp = d.env_comp;
+        ca.env_comp = cepstral_env_comp();
         ca.inv_n = d.inv_n;
         ca.mag = mag.p;
         if (back) rec(2 * PV_K_CEPSTRAL);
@@ -1266,7 +1274,7 @@ void Core::launch_chunk(const InAddr &ia, int64_t t0, int Tn, const int32_t *d_p
     if (single_launch) {
         fused.oa = oa;
         fused.coremode = cm;
-        fused.cepstral = d.cepstral ? 1 : 0;
+        fused.cepstral = cepstral_on() ? 1 : 0;
         launch_stream(fused, st); HIPV(hipGetLastError());
     } else if (back && ntiles > 0) {
         rec(2 * PV_K_OLA_RESAMPLE);
@@ -1421,6 +1429,9 @@ struct pv_pool {
         bool fast = false;
         int tab = -1;              // mixed pool, resampling slot: its entry of the table arena
         int lds_floats = 0, tab_bytes = 0; // ... and its resampling kernel's LDS layout
+        // the formant setting (pv_pool_set_formant): host state, read when a feed builds the slot's PoolSlot
+        bool fx_on = false;
+        float fx_semitones = 0.f;
     };
     std::vector<Slot> slots;
     // Mixed pool (pv_pool_create_mixed): the range a slot's pitch / time ratio may take, and what the buffers were sized
@@ -1601,6 +1612,75 @@ const char *pv_kernel_name(int k) {
                                             "pv_prop_kernel",    "pv_synth_kernel", "pv_ola_kernel",
                                             "pv_cepstral_kernel", "pv_synth_ola_kernel"};
     return (k >= 0 && k < PV_NUM_KERNELS) ? n[k] : "";
+}
+
+// ---- the formant setting (audiomod_pv.h "Formant setting"): what every form's entry point shares
+// env_comp of a stream whose pitch scale is pitch_scale (Derived::pitch_scale) with the knob at formant_semitones:
+// the ratio made as derive() makes the pitch scale (float quotient, double pow, stored float), then a float quotient
+static float formant_env_comp_of(float pitch_scale, float formant_semitones) {
+    const float ratio = formant_semitones != 0 ? (float)std::pow(2.0, formant_semitones / 12) : 1.0f;
+    return pitch_scale / ratio;
+}
+static int formant_value_check(float formant_semitones) {
+    if (!std::isfinite(formant_semitones) || std::fabs(formant_semitones) > 48.0f) {
+        g_last_error = "formant setting: formant_semitones must be a finite number within +-48";
+        return PV_ERR_INVALID_ARG;
+    }
+    return PV_OK;
+}
+// the setting belongs to the two plain modes
+static int formant_scope_check(const pv_config &cfg) {
+    if (cfg.mode == PV_MODE_NORMAL_SHIFT || cfg.mode == PV_MODE_NORMAL_STRETCH) return PV_OK;
+    g_last_error = cfg.mode == PV_MODE_FORMANT_CEPSTRAL
+                       ? "formant setting: mode FORMANT_CEPSTRAL already fixes it (env_comp = the pitch scale)"
+                       : "formant setting: modes NORMAL_SHIFT and NORMAL_STRETCH only";
+    return PV_ERR_UNSUPPORTED;
+}
+static int core_set_formant(Core &c, int on, float formant_semitones) {
+    g_last_error.clear();
+    plan_reason_clear();
+    int st = formant_scope_check(c.d.cfg);
+    if (st == PV_OK && on) st = formant_value_check(formant_semitones);
+    if (st != PV_OK) return st;
+    if (c.d.N < 128) { // (as mode FORMANT_CEPSTRAL: the lifter keeps 60 quefrencies)
+        g_last_error = "formant setting: fftsize below 128 is not supported";
+        return PV_ERR_UNSUPPORTED;
+    }
+    c.fx_on = on != 0;
+    c.fx_env_comp = on ? formant_env_comp_of(c.d.pitch_scale, formant_semitones) : 1.0f;
+    return PV_OK;
+}
+
+int pv_formant_env_comp(float pitch_semitones, float formant_semitones, float *env_comp) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!env_comp || !std::isfinite(pitch_semitones)) return PV_ERR_INVALID_ARG;
+    const int st = formant_value_check(formant_semitones);
+    if (st != PV_OK) return st;
+    const float pitch_scale = pitch_semitones != 0 ? (float)std::pow(2.0, pitch_semitones / 12) : 1.0f; // derive()
+    *env_comp = formant_env_comp_of(pitch_scale, formant_semitones);
+    return PV_OK;
+}
+
+int pv_set_formant(pv_engine *e, int on, float formant_semitones) {
+    if (!e) return PV_ERR_INVALID_ARG;
+    return core_set_formant(e->core, on, formant_semitones);
+}
+
+int pv_batch_set_formant(pv_batch *b, int on, float formant_semitones) {
+    if (!b) return PV_ERR_INVALID_ARG;
+    Core &c = b->core;
+    const bool was_on = c.fx_on;
+    const float was_env = c.fx_env_comp;
+    const int st = core_set_formant(c, on, formant_semitones);
+    if (st != PV_OK || b->ev_used == 0) return st;
+    // (instrumented chunks enqueued so far were recorded under the old setting: folded under it)
+    const bool now_on = c.fx_on;
+    const float now_env = c.fx_env_comp;
+    c.fx_on = was_on, c.fx_env_comp = was_env;
+    (void)pv_batch_kernel_times(b, nullptr, nullptr);
+    c.fx_on = now_on, c.fx_env_comp = now_env;
+    return PV_OK;
 }
 
 int pv_plan_simulate(const pv_config *cfg, const int32_t *n, int32_t ncalls, int32_t *avail, int32_t *shift,
@@ -2121,7 +2201,7 @@ int pv_batch_kernel_times(pv_batch *b, double ms[PV_NUM_KERNELS], int64_t launch
         for (int k = 0; k < PV_NUM_KERNELS; ++k) {
             if ((k == PV_K_MATCH || k == PV_K_SEQ) && cm != 1) continue;
             if (k == PV_K_PROP && cm != 0) continue;
-            if (k == PV_K_CEPSTRAL && !d.cepstral) continue;
+            if (k == PV_K_CEPSTRAL && !b->core.cepstral_on()) continue;
             const bool fused = b->core.use_chain && b->core.wave_fft();
             if (k == PV_K_SYNTH_OLA && !fused) continue;
             if (k == PV_K_SYNTH && fused) continue;
@@ -2522,7 +2602,7 @@ static bool pool_slot_ok(const pv_pool *p, int32_t slot) {
     return p && slot >= 0 && slot < p->cap && p->slots[(size_t)slot].open;
 }
 
-static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true);
+static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true, const PoolLaunch *fx = nullptr);
 
 // Core::init and pool_create allocate with DevBuf::alloc, whose zero fill is on the default stream; nothing orders that
 // stream against the pool's own non-blocking one.  pv_pool_create therefore ends with a wait for the fills, so that no
@@ -2855,6 +2935,7 @@ static void pool_slot_begin(pv_pool *p, int32_t s, std::unique_ptr<Derived> own,
     sl.fed = sl.uploaded = sl.slices = 0;
     sl.tap_n = 0;
     sl.acc_half = 0;
+    sl.fx_on = false, sl.fx_semitones = 0.f;
     sl.outq.assign((size_t)c.C, std::vector<float>());
     sl.outq_head = 0;
     sl.open = true;
@@ -3015,6 +3096,33 @@ int pv_pool_get_info(const pv_pool *p, int32_t slot, pv_info *info) {
     return PV_OK;
 }
 
+// The slot's formant setting: host state that the next feed's descriptor building reads (pool_feed), so no device call
+// and no wait for feeds in flight -- their descriptor blocks were built before the change.
+int pv_pool_set_formant(pv_pool *p, int32_t slot, int on, float formant_semitones) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p) return PV_ERR_INVALID_ARG;
+    int st = formant_scope_check(p->core.d.cfg);
+    if (st != PV_OK) return st;
+    if (!pool_slot_ok(p, slot)) {
+        g_last_error = "stream pool: slot " + std::to_string(slot) + " is not open";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (on && (st = formant_value_check(formant_semitones)) != PV_OK) return st;
+    pv_pool::Slot &sl = p->slots[(size_t)slot];
+    sl.fx_on = on != 0;
+    sl.fx_semitones = on ? formant_semitones : 0.f;
+    return PV_OK;
+}
+
+int pv_pool_get_formant(const pv_pool *p, int32_t slot, int *on, float *formant_semitones) {
+    if (!pool_slot_ok(p, slot)) return PV_ERR_INVALID_ARG;
+    const pv_pool::Slot &sl = p->slots[(size_t)slot];
+    if (on) *on = sl.fx_on ? 1 : 0;
+    if (formant_semitones) *formant_semitones = sl.fx_semitones;
+    return PV_OK;
+}
+
 int32_t pv_pool_retrieve(pv_pool *p, int32_t slot, float *const *out, int32_t n) {
     if (!pool_slot_ok(p, slot) || n < 0 || (n > 0 && !out)) return -1;
     pv_pool::Slot &sl = p->slots[(size_t)slot];
@@ -3042,9 +3150,21 @@ static InAddr pool_ring_addr(const pv_pool *p) {
     return ia;
 }
 
+// the formant stage's block on the slot-table paths (rows = C; Tn, s0 and env_comp come from each slot's PoolSlot)
+static CepstralArgs slot_cepstral_args(const Core &c) {
+    CepstralArgs a{};
+    a.tb = c.tb;
+    a.TR = c.TR;
+    a.rows = c.C;
+    a.inv_n = c.d.inv_n;
+    a.mag = c.mag.p;
+    return a;
+}
+
 // the stages of one launch group for every slot in it (Core's argument builders with rows = C);
 // launch = false: launch nothing, only ask the launchers whether this configuration fits them (pv_pool_create)
-static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch) {
+// fx: the table of the group's slots that run the formant stage (null: none does)
+static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch, const PoolLaunch *fx) {
     const Core &c = p->core;
     const Derived &d = c.d;
     hipStream_t st = p->stream;
@@ -3072,6 +3192,10 @@ static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch
         const PropArgs pa = c.prop_args(c.C);
         if (!launch_pool_prop(pa, pl, st)) return refused("propagation");
         if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
+    }
+    if (launch && fx) {
+        if (!launch_slot_cepstral(slot_cepstral_args(c), *fx, PV_CENSUS_SET_POOL, st)) return refused("formant");
+        if ((rc = launched("pool formant launch")) != PV_OK) return rc;
     }
     const SynthArgs sa = c.synth_args(c.C);
     const ChainArgs ca = c.chain_args(c.C);
@@ -3102,7 +3226,7 @@ static size_t variant_group_end(const std::vector<VariantRun> &runs, size_t a) {
     return e;
 }
 static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const PoolParams *q,
-                                 const std::vector<VariantRun> &runs, int *nlaunch) {
+                                 const std::vector<VariantRun> &runs, int *nlaunch, const PoolLaunch *fx) {
     const Core &c = p->core;
     const Derived &d = c.d; // (only what every slot shares: sizes, mode, coremode)
     hipStream_t st = p->stream;
@@ -3130,6 +3254,10 @@ static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const P
         const PropArgs pa = c.prop_args(c.C);
         if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
         if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
+    }
+    if (fx) { // (one launch for every variant: the stage does not depend on it)
+        if (!launch_slot_cepstral(slot_cepstral_args(c), *fx, PV_CENSUS_SET_PMIX, st)) return refused("formant");
+        if ((rc = launched("pool formant launch")) != PV_OK) return rc;
     }
     float *stream = c.stream.p ? c.stream.p : p->mix_stream.p;
     for (size_t a = 0; a < runs.size();) {
@@ -3372,9 +3500,11 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
     struct Group {
         int64_t table_off, ingest_off;
         int nslots, ningest, max_tn, max_tiles, max_in;
+        int64_t fx_off; // the entries of the slots that run the formant stage, once more: that launch's table
+        int fx_nslots, fx_max_tn;
     };
     std::vector<Group> grp((size_t)groups + 1); // (+ the final ingest of what the call leaves unconsumed)
-    std::vector<PoolSlot> table;
+    std::vector<PoolSlot> table, fx_table;
     // mixed pool: per group its PoolParams table (parallel to the PoolSlot table) and variant runs
     std::vector<PoolParams> params;
     std::vector<int64_t> params_off((size_t)groups, 0);
@@ -3403,8 +3533,9 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
     for (int32_t i = 0; i < count; ++i) p->slots[(size_t)slots[i]].fed += n[i];
     for (int gi = 0; gi < groups; ++gi) {
         Group &g = grp[(size_t)gi];
-        g = Group{0, 0, 0, 0, 0, 0, 0};
+        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         table.clear();
+        fx_table.clear();
         ingest.clear();
         params.clear();
         vkey.clear();
@@ -3455,6 +3586,14 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
             ps.out_off = out_base[(size_t)i] + (ka - k0[(size_t)i]);
             ps.out_stride_row = to_caller ? io.out_pitch : out_cnt[(size_t)i];
             ps.k_base = ka;
+            if (sl.fx_on) {
+                const float env_comp = formant_env_comp_of(sd.pitch_scale, sl.fx_semitones);
+                if (env_comp != 1.0f) { // (as mode FORMANT_CEPSTRAL skips the stage at pitch scale 1)
+                    ps.env_comp = env_comp;
+                    fx_table.push_back(ps);
+                    if (Tn > g.fx_max_tn) g.fx_max_tn = Tn;
+                }
+            }
             table.push_back(ps);
             if (Tn > g.max_tn) g.max_tn = Tn;
             if (ps.res_ntiles > g.max_tiles) g.max_tiles = ps.res_ntiles;
@@ -3507,12 +3646,14 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         }
         g.nslots = (int)table.size();
         g.table_off = put(table.data(), table.size() * sizeof(PoolSlot));
+        g.fx_nslots = (int)fx_table.size();
+        g.fx_off = put(fx_table.data(), fx_table.size() * sizeof(PoolSlot));
         g.ningest = (int)ingest.size();
         g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
     }
     {
         Group &g = grp[(size_t)groups];
-        g = Group{0, 0, 0, 0, 0, 0, 0};
+        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         ingest.clear();
         for (int32_t i = 0; i < count; ++i) add_ingest(i, p->slots[(size_t)slots[i]].fed, g);
         g.ningest = (int)ingest.size();
@@ -3577,12 +3718,17 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         pl.nslots = g.nslots;
         pl.max_tn = g.max_tn;
         pl.max_tiles = g.max_tiles;
+        PoolLaunch fx = pl;
+        fx.slots = reinterpret_cast<const PoolSlot *>(d_desc + g.fx_off);
+        fx.nslots = g.fx_nslots;
+        fx.max_tn = g.fx_max_tn;
+        const PoolLaunch *const fxp = g.fx_nslots > 0 ? &fx : nullptr;
         if (p->mixed) {
             const PoolParams *q = reinterpret_cast<const PoolParams *>(d_desc + params_off[(size_t)gi]);
-            if ((st = pool_mix_launch_group(p, pl, q, vruns[(size_t)gi], &nlaunch)) != PV_OK) return fail(st);
+            if ((st = pool_mix_launch_group(p, pl, q, vruns[(size_t)gi], &nlaunch, fxp)) != PV_OK) return fail(st);
         } else {
-            if ((st = pool_launch_group(p, pl)) != PV_OK) return fail(st);
-            nlaunch += 2 + (cm == 0 || cm == 1 ? 1 : 0) + (c.d.resample && pl.max_tiles > 0 ? 1 : 0);
+            if ((st = pool_launch_group(p, pl, true, fxp)) != PV_OK) return fail(st);
+            nlaunch += 2 + (cm == 0 || cm == 1 ? 1 : 0) + (c.d.resample && pl.max_tiles > 0 ? 1 : 0) + (fxp ? 1 : 0);
         }
     }
     if (io.device) {
@@ -4062,6 +4208,7 @@ struct pv_mbatch {
         bool fast = false;
         int tab = -1, lds_floats = 0, tab_bytes = 0;
         std::vector<Span> wden, otab;
+        float env_comp = 0.f; // the formant setting (pv_mbatch_set_formant): its PoolSlot::env_comp, 0 = off
     };
     std::vector<Stream> s; // (sized once per draw: the plans' builders keep references into it)
     int64_t in_floats = 0, out_floats = 0;
@@ -4069,6 +4216,8 @@ struct pv_mbatch {
         int64_t table_off = 0, params_off = 0, mb_off = 0;
         int nslots = 0, max_tn = 0;
         std::vector<VariantRun> vr;
+        std::vector<int32_t> stream_of; // the stream of each table entry
+        int fx_slots = 0;               // entries that run the formant stage
     };
     std::vector<Group> groups;
     int kernel_launches = 0; // kernels per run
@@ -4180,7 +4329,7 @@ static int mb_plan(const pv_config *cfg, const pv_mbatch_stream *s, int32_t n, i
 
 // kernels one launch group enqueues (mb_launch_group)
 static int mb_group_kernels(const pv_mbatch::Group &g, int cm) {
-    int k = 1 + (cm == 1 ? 2 : cm == 0 ? 1 : 0);
+    int k = 1 + (cm == 1 ? 2 : cm == 0 ? 1 : 0) + (g.fx_slots > 0 ? 1 : 0);
     for (size_t a = 0; a < g.vr.size();) {
         const size_t e = variant_group_end(g.vr, a);
         ++k;
@@ -4237,6 +4386,10 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
         const PropArgs pa = c.prop_args(c.C);
         if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
         if ((rc = launched("mixed batch propagation launch")) != PV_OK) return rc;
+    }
+    if (launch && g.fx_slots > 0) { // (the whole table: the slots with the setting off leave at their entry's 0)
+        if (!launch_slot_cepstral(slot_cepstral_args(c), pl, PV_CENSUS_SET_MB, st)) return refused("formant");
+        if ((rc = launched("mixed batch formant launch")) != PV_OK) return rc;
     }
     float *stream = c.stream.p ? c.stream.p : b->dev->mix_stream.p;
     const std::vector<VariantRun> &runs = g.vr;
@@ -4593,6 +4746,7 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
             r.max_runs = std::max(r.max_runs, (int)e.ms.runs);
             gr.max_tn = std::max(gr.max_tn, (int)e.ps.Tn);
             table.push_back(e.ps), params.push_back(e.q), mbs.push_back(e.ms);
+            gr.stream_of.push_back(e.ps.row0 / C);
         }
         gr.nslots = (int)ev.size();
         gr.table_off = shift + put(table.data(), table.size() * sizeof(PoolSlot));
@@ -4873,6 +5027,49 @@ int pv_mbatch_run(pv_mbatch *b, const float *d_in, float *d_out, void *hip_strea
         if ((rc = mb_launch_group(b, g, d_in, d_out, st)) != PV_OK) return rc;
     HIPC(hipGetLastError());
     b->tap_ran = true;
+    return PV_OK;
+}
+
+// pv_mbatch_set_formant: audiomod_pv.h.  The slot tables are resident, so the setting is written into them: every check
+// first, then the device is synchronised -- an earlier run may still read the tables, as in pv_mbatch_redraw -- and the
+// env_comp field of every group's entries is patched, one strided copy per group.
+int pv_mbatch_set_formant(pv_mbatch *b, const float *formant_semitones) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!b) return PV_ERR_INVALID_ARG;
+    int st = formant_scope_check(b->cfg);
+    if (st != PV_OK) return st;
+    const size_t n = b->s.size();
+    std::vector<float> env(n, 0.f);
+    for (size_t i = 0; i < n && formant_semitones; ++i) {
+        const float v = formant_semitones[i];
+        if (std::isnan(v)) continue; // off
+        if ((st = formant_value_check(v)) != PV_OK) {
+            g_last_error = "mixed batch: stream " + std::to_string(i) + ": " + g_last_error;
+            return st;
+        }
+        const float e = formant_env_comp_of(b->s[i].d.pitch_scale, v);
+        env[i] = e != 1.0f ? e : 0.f; // (as mode FORMANT_CEPSTRAL skips the stage at pitch scale 1)
+    }
+    HIPC(hipSetDevice(b->device));
+    HIPC(hipDeviceSynchronize());
+    const int cm = phase_mode(b->dev->core.d);
+    std::vector<float> col;
+    int launches = 0;
+    for (pv_mbatch::Group &g : b->groups) {
+        col.clear();
+        g.fx_slots = 0;
+        for (const int32_t i : g.stream_of) {
+            col.push_back(env[(size_t)i]);
+            g.fx_slots += env[(size_t)i] != 0.f ? 1 : 0;
+        }
+        if (!col.empty())
+            HIPC(hipMemcpy2D(b->dev->d_desc.p + g.table_off + offsetof(PoolSlot, env_comp), sizeof(PoolSlot), col.data(),
+                             sizeof(float), sizeof(float), col.size(), hipMemcpyHostToDevice));
+        launches += mb_group_kernels(g, cm);
+    }
+    for (size_t i = 0; i < n; ++i) b->s[i].env_comp = env[i];
+    b->kernel_launches = launches;
     return PV_OK;
 }
 

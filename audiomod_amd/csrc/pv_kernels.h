@@ -260,7 +260,7 @@ void chain_census_enable(bool on); // clears the table either way
 // PV_CENSUS_ANALYZE (a = NC, b = split), PV_CENSUS_PHASE (a = form, b = ring depth 4 / 8 or, for the forms without a
 // ring, peaks per lane 1 / 3), PV_CENSUS_RESAMPLE_RUNG (all four sets: a = rung kResRung*, b = interpolated, c = the
 // launch asked for more than 64 KB of LDS), PV_CENSUS_ANALYSIS_KERNEL (all four sets: a = kAnaKernel*, b = NC 128 ...
-// 4096); -1 for a key that does not exist
+// 4096), PV_CENSUS_CEPSTRAL (all four sets: a = kCepKernel*, b = NC 128 ... 4096); -1 for a key that does not exist
 // The forms of the phase-locked stage (PV_PHASE_FORM_* of the C ABI): match kernel + ring chain kernel; match kernel +
 // chain kernel that loads one step ahead (pv_seq_kernel<1>, or <3> with three peaks per lane); match and ring chain in
 // one launch; the single-launch stream kernel.  Set: launch_seq / launch_phase / launch_stream count under batch.
@@ -269,6 +269,9 @@ enum { kPhaseFormRing = 0, kPhaseFormStep = 1, kPhaseFormFused = 2, kPhaseFormSt
 // its kernel with a frame on two waves; pv_stream_kernel, which analyses inside the single launch.  launch_analyze
 // and launch_stream count under batch, launch_slot_analyze under its set.
 enum { kAnaKernelGeneric = 0, kAnaKernelWave = 1, kAnaKernelSplit = 2, kAnaKernelStream = 3, kAnaKernels = 4 };
+// Which cepstral kernel a launch is (PV_CEP_KERNEL_* of the C ABI): pv_cepstral_kernel; pv_cepstral_wave_kernel, or its
+// role inside pv_stream_kernel; pv_slot_cepstral_wave_kernel.  The first two count under batch, the last under its set.
+enum { kCepKernelGeneric = 0, kCepKernelWave = 1, kCepKernelSlot = 2, kCepKernels = 3 };
 int64_t chain_census_count(int kind, int set, int a, int b, int c, int d);
 
 // pv_resample_kernel: one workgroup = 256 outputs of two rows
@@ -333,7 +336,7 @@ void launch_match(const MatchArgs &a, hipStream_t st);
 void launch_seq(const SeqArgs &a, hipStream_t st);
 void launch_prop(const PropArgs &a, hipStream_t st);
 void launch_synth(const SynthArgs &a, hipStream_t st);
-void launch_cepstral(const CepstralArgs &a, hipStream_t st); // nc 1024 / 2048 only
+void launch_cepstral(const CepstralArgs &a, hipStream_t st); // the wave kernel at nc 1024 / 2048, else the generic one
 void launch_ola(const OlaArgs &a, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -350,7 +353,8 @@ struct PoolSlot {
     int32_t row0;     // first row of the slot (slot index * C)
     int32_t acc_sel;  // ChainArgs::acc_sel of the slot (its own half and "stream starts here" bit)
     int32_t res_ntiles; // tiles of the resampling kernel
-    int32_t pad;
+    float env_comp;     // the slot's formant setting (pv_slot_cepstral_wave_kernel): CepstralArgs::env_comp, 0 = the
+                        // slot does not run the stage
     // byte offsets into the launch's descriptor block (PoolLaunch::desc)
     int64_t pinc_off, cs_off, ro_off, wden_off, res_off, otab_off;
     int64_t out_off;        // float offset of its first output (row 0) in PoolLaunch::out
@@ -402,6 +406,9 @@ void launch_pool_snapshot(const SnapArgs &a, int nsegs, int parts, hipStream_t s
 // Each returns false (launching nothing) when the configuration has no per-slot kernel or it does not fit;
 // launch = false: only that check (pv_pool_create asks it once).
 bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st);
+// The formant setting's stage for every slot of the table, one launch for all three slot-table sets (census_set: the
+// set it counts under).  `a` holds the pool-wide mag base, TR, inv_n and rows = C; Tn, s0 and env_comp come per slot.
+bool launch_slot_cepstral(const CepstralArgs &a, const PoolLaunch &p, int census_set, hipStream_t st);
 bool pool_phase_supported(int hs, int PKP);
 bool launch_pool_phase(const MatchArgs &m, const SeqArgs &a, const PoolLaunch &p, hipStream_t st);
 bool launch_pool_prop(const PropArgs &a, const PoolLaunch &p, hipStream_t st);

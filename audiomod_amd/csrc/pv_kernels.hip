@@ -2389,6 +2389,10 @@ __device__ __forceinline__ void cepstral_wave_role(const CepstralArgs &a, const 
     wave_sync();
     wf_fft_pass<W, 2, true>(v, lane, lds, twi);
     wave_sync();
+    if constexpr (W::NPASS == 4) { // (256 / 512 points: the last radix-4 stage is a pass of its own)
+        wf_fft_pass<W, 3, true>(v, lane, lds, twi);
+        wave_sync();
+    }
 
     // lifter: element e of the transform holds cep[2e], cep[2e+1]; only the first 60 survive
     cf z = cf{0.f, 0.f};
@@ -2421,6 +2425,10 @@ __device__ __forceinline__ void cepstral_wave_role(const CepstralArgs &a, const 
     wave_sync();
     wf_fft_pass<W, 2, false>(v, lane, lds, twf);
     wave_sync();
+    if constexpr (W::NPASS == 4) {
+        wf_fft_pass<W, 3, false>(v, lane, lds, twf);
+        wave_sync();
+    }
 
     // real parts of the real-FFT split (kiss_fftr.c:91-120), exponentiated: the spectral envelope
     float elo[J], ehi[J], emid = 0.f;
@@ -2583,8 +2591,12 @@ __global__ __launch_bounds__(kFftThreads) void pv_cepstral_kernel(const Cepstral
     }
 }
 
+// (the census of the launchers' choices, below: which cepstral kernel a launch is)
+static void census_cepstral(int set, int kernel, int nc);
+
 void launch_cepstral(const CepstralArgs &a, hipStream_t st) {
     const int grid = 8 * ((a.rows + 7) / 8) * a.Tn;
+    census_cepstral(0, a.tb.nc != 1024 && a.tb.nc != 2048 ? kCepKernelGeneric : kCepKernelWave, a.tb.nc);
     if (a.tb.nc != 1024 && a.tb.nc != 2048) {
         const size_t lds = (size_t)(2 * a.tb.nc + 1) * sizeof(float2) + sizeof(float) * (a.tb.hs + 4 + 64);
         launch_big_lds<pv_cepstral_kernel>(dim3(grid), dim3(generic_fft_threads(a.tb.nc)), lds, st, a);
@@ -3279,6 +3291,7 @@ static std::atomic<uint64_t> g_census_rrung[PV_CENSUS_SETS][kResRungs][2][2];
 static std::atomic<uint64_t> g_census_ana[PV_CENSUS_SETS][kCensusNc][2];
 static std::atomic<uint64_t> g_census_phase[PV_CENSUS_SETS][kPhaseForms][4];
 static std::atomic<uint64_t> g_census_akern[PV_CENSUS_SETS][kAnaKernels][6];
+static std::atomic<uint64_t> g_census_cep[PV_CENSUS_SETS][kCepKernels][6];
 static int census_akern_nc_index(int nc) { // fft / 2 of 256 ... 8192 points
     return nc == 128 ? 0 : nc == 256 ? 1 : nc == 512 ? 2 : nc == 1024 ? 3 : nc == 2048 ? 4 : nc == 4096 ? 5 : -1;
 }
@@ -3308,6 +3321,10 @@ static void census_analysis_kernel(int set, int kernel, int nc) {
     if (!g_census_on.load(std::memory_order_relaxed)) return;
     if (census_akern_nc_index(nc) >= 0) g_census_akern[set][kernel][census_akern_nc_index(nc)].fetch_add(1, std::memory_order_relaxed);
 }
+static void census_cepstral(int set, int kernel, int nc) {
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    if (census_akern_nc_index(nc) >= 0) g_census_cep[set][kernel][census_akern_nc_index(nc)].fetch_add(1, std::memory_order_relaxed);
+}
 void chain_census_enable(bool on) {
     g_census_on.store(false, std::memory_order_relaxed);
     for (auto &a : g_census_chain) for (auto &b : a) for (auto &c : b) for (auto &d : c) for (auto &e : d) e.store(0, std::memory_order_relaxed);
@@ -3316,6 +3333,7 @@ void chain_census_enable(bool on) {
     for (auto &a : g_census_ana) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_phase) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_akern) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
+    for (auto &a : g_census_cep) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     g_census_on.store(on, std::memory_order_relaxed);
 }
 int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
@@ -3340,6 +3358,9 @@ int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
     case 5:
         if (a < 0 || a >= kAnaKernels || census_akern_nc_index(b) < 0) return -1;
         return (int64_t)g_census_akern[set][a][census_akern_nc_index(b)].load(std::memory_order_relaxed);
+    case 7: // (PV_CENSUS_CEPSTRAL; 6 is no kind)
+        if (a < 0 || a >= kCepKernels || census_akern_nc_index(b) < 0) return -1;
+        return (int64_t)g_census_cep[set][a][census_akern_nc_index(b)].load(std::memory_order_relaxed);
     default: return -1;
     }
 }
@@ -3970,6 +3991,7 @@ void launch_stream(const StreamArgs &s, hipStream_t st) {
     const size_t lds = stream_lds_bytes(s);
     if (s.coremode == 1) census_phase(0, kPhaseFormStream, 1); // (seq_role<1> on the kernel's 512 threads)
     census_analysis_kernel(0, kAnaKernelStream, s.aa.tb.nc);
+    if (s.cepstral) census_cepstral(0, kCepKernelWave, s.aa.tb.nc);
     if (s.aa.tb.nc == 1024) {
         launch_big_lds<pv_stream_kernel<1024>>(dim3(1), dim3(kStreamThreads), lds, st, s);
     } else {
@@ -4332,6 +4354,35 @@ struct PoolAnalyzeSet { // trailing argument p
 };
 bool launch_pool_analyze(const AnalyzeArgs &a, const PoolLaunch &p, hipStream_t st) {
     return launch_slot_analyze(PoolAnalyzeSet{p}, a, p, st);
+}
+
+// Cepstral formant shift of the slots' magnitude planes (the formant setting of the pools and the mixed batch,
+// pv_*_set_formant): one wave per (row, slice) of a slot, workgroup x = tl * C + c as in the analysis kernel above.  The
+// stage reads the slot table and the planes and nothing else of a set, so the three sets share this kernel.  A slot
+// whose env_comp is 0 does not run the stage: its workgroups read the entry and return.
+template <int NC>
+__global__ __launch_bounds__(64) void pv_slot_cepstral_wave_kernel(const CepstralArgs a, const PoolLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    PV_POISON_LDS(reinterpret_cast<char *>(smem_raw));
+    const PoolSlot ps = p.slots[blockIdx.y];
+    const int tl = __builtin_amdgcn_readfirstlane((int)blockIdx.x / a.rows), row = blockIdx.x - tl * a.rows;
+    if (tl >= ps.Tn || ps.env_comp == 0.f) return; // wave-uniform
+    CepstralArgs v = a;
+    v.mag += (int64_t)ps.row0 * a.TR * a.tb.HP;
+    v.Tn = ps.Tn, v.s0 = ps.s0, v.env_comp = ps.env_comp;
+    cepstral_wave_role<NC>(v, row, tl, reinterpret_cast<cf *>(smem_raw));
+}
+bool launch_slot_cepstral(const CepstralArgs &a, const PoolLaunch &p, int census_set, hipStream_t st) {
+    const dim3 grid(a.rows * p.max_tn, p.nslots);
+    if (census_nc_index(a.tb.nc) < 0 || p.nslots <= 0 || p.max_tn <= 0) return false;
+    census_cepstral(census_set, kCepKernelSlot, a.tb.nc);
+    switch (a.tb.nc) {
+    case 256: hipLaunchKernelGGL((pv_slot_cepstral_wave_kernel<256>), grid, dim3(64), WF<256>::LDS_CF * sizeof(cf), st, a, p); break;
+    case 512: hipLaunchKernelGGL((pv_slot_cepstral_wave_kernel<512>), grid, dim3(64), WF<512>::LDS_CF * sizeof(cf), st, a, p); break;
+    case 1024: hipLaunchKernelGGL((pv_slot_cepstral_wave_kernel<1024>), grid, dim3(64), WF<1024>::LDS_CF * sizeof(cf), st, a, p); break;
+    default: hipLaunchKernelGGL((pv_slot_cepstral_wave_kernel<2048>), grid, dim3(64), WF<2048>::LDS_CF * sizeof(cf), st, a, p); break;
+    }
+    return true;
 }
 
 // phase-locked mode: match + rotation chain of a slot's rows (pv_phase_kernel), one workgroup per (channel, slot)

@@ -233,6 +233,12 @@ def lib():
         getattr(L, name + "_plane_info").argtypes = [C.c_void_p] + ([] if name == "pv_debug_batch" else lead) + [
             C.POINTER(PlaneInfo)]
         getattr(L, name + "_planes").argtypes = [C.c_void_p] + lead + [C.c_int32, C.c_int64] + [C.c_void_p] * 7
+    L.pv_formant_env_comp.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
+    L.pv_set_formant.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    L.pv_batch_set_formant.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    L.pv_pool_set_formant.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_float]
+    L.pv_pool_get_formant.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    L.pv_mbatch_set_formant.argtypes = [C.c_void_p, C.c_void_p]
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -338,6 +344,37 @@ def analysis_census_read():
                 if n > 0:
                     out[(name, kernel, nc)] = n
     return out
+
+
+CEPSTRAL_KERNELS = ("generic", "wave", "slot")  # PV_CEP_KERNEL_*: the cepstral formant stage's kernels
+
+
+def cepstral_census_read():
+    """The non-zero keys of the census' kind PV_CENSUS_CEPSTRAL, the cepstral formant stage of all four sets: {(set, kernel, nc):
+    launches} with `set` one of CENSUS_SETS ("batch" counts the batch path and the single-stream engine, mode
+    formant_cepstral and the formant setting alike), `kernel` one of CEPSTRAL_KERNELS and nc half the fft size."""
+    count = lib().pv_debug_chain_census_count
+    out = {}
+    for i, name in enumerate(CENSUS_SETS):
+        for k, kernel in enumerate(CEPSTRAL_KERNELS):
+            for nc in ANALYSIS_NC:
+                n = count(7, i, k, nc, 0, 0)
+                if n > 0:
+                    out[(name, kernel, nc)] = n
+    return out
+
+
+def formant_env_comp(pitch, formant):
+    """Host only: the env_comp (float32) of a stream shifted by `pitch` semitones with the formant setting at `formant`
+    semitones (include/audiomod_pv.h "Formant setting"): the pitch scale itself at 0."""
+    v = C.c_float(0)
+    _check(lib().pv_formant_env_comp(float(pitch), float(formant), C.byref(v)), "pv_formant_env_comp")
+    return np.float32(v.value)
+
+
+def _formant_args(st):
+    """(on, value) of the C ABI for a setting given as semitones or None (off)"""
+    return (0, 0.0) if st is None else (1, float(st))
 
 
 RES_RUNGS = ("ref4", "vec8", "vec16", "mfma", "vec2", "vec4")  # PV_RES_RUNG_*: the resampling kernels
@@ -501,6 +538,11 @@ class PhaseVocoder:
         _check(self.L.pv_get_info(self.h, C.byref(i)), "pv_get_info")
         return i.as_dict()
 
+    def set_formant(self, st):
+        """The formant setting for the slices of later calls: semitones the formants move by (0: they stay, whatever
+        the pitch does), or None for off.  Modes normal_pitchshift and time_stretch only."""
+        _check(self.L.pv_set_formant(self.h, *_formant_args(st)), "pv_set_formant")
+
     def plane_info(self):
         """Diagnostics: which slices of a row the plane tap can read now, and which planes exist (pv_plane_info)"""
         return _plane_info("pv_debug", self.h, ())
@@ -627,6 +669,12 @@ class Batch:
         i = Info()
         _check(self.L.pv_batch_get_info(self.h, C.byref(i)), "pv_batch_get_info")
         return i.as_dict()
+
+    def set_formant(self, st):
+        """The formant setting (see PhaseVocoder.set_formant), one value for every stream, for the launches enqueued
+        after the call; returns self."""
+        _check(self.L.pv_batch_set_formant(self.h, *_formant_args(st)), "pv_batch_set_formant")
+        return self
 
     def plane_info(self):
         """Diagnostics: which slices of a row the plane tap can read now, and which planes exist (pv_plane_info)"""
@@ -758,6 +806,18 @@ class MixedBatch:
             raise PvError("MixedBatch.redraw: %d streams for an object of %d" % (len(streams), len(self.streams)))
         _check(self.L.pv_mbatch_redraw(self.h, _mixed_streams(streams)), "pv_mbatch_redraw")
         self.streams = streams
+        self._refresh()
+
+    def set_formant(self, values):
+        """The formant setting per stream: a list of semitones with None (or NaN) for off, or None for all off.
+        Synchronises the device; kernel_launches is refreshed.  A redraw() resets every stream to off."""
+        if values is None:
+            _check(self.L.pv_mbatch_set_formant(self.h, None), "pv_mbatch_set_formant")
+        else:
+            if len(values) != len(self.streams):
+                raise PvError("MixedBatch.set_formant: %d values for an object of %d" % (len(values), len(self.streams)))
+            v = np.array([np.nan if x is None else float(x) for x in values], np.float32)
+            _check(self.L.pv_mbatch_set_formant(self.h, v.ctypes.data), "pv_mbatch_set_formant")
         self._refresh()
 
     def last_build_timing(self):
@@ -1197,8 +1257,22 @@ class StreamPool:
         return [int(s) for s in slots] if many else int(slots[0])
 
     def fork(self, slot):
-        """A second slot of this pool with the slot's history: both return the same bits from here on."""
-        return self.restore(self.save(int(slot)))
+        """A second slot of this pool with the slot's history: both return the same bits from here on (a blob does not
+        carry the formant setting, so the new slot gets the slot's setting here)."""
+        s = self.restore(self.save(int(slot)))
+        self.set_formant(s, self.get_formant(slot))
+        return s
+
+    def set_formant(self, slot, st):
+        """The slot's formant setting (see PhaseVocoder.set_formant) for the slices of later feeds: semitones, or None
+        for off.  Host state only; a slot opens, and is restored, with the setting off."""
+        _check(self.L.pv_pool_set_formant(self.h, int(slot), *_formant_args(st)), "pv_pool_set_formant")
+
+    def get_formant(self, slot):
+        """The slot's formant setting: semitones, or None when off."""
+        on, v = C.c_int(0), C.c_float(0)
+        _check(self.L.pv_pool_get_formant(self.h, int(slot), C.byref(on), C.byref(v)), "pv_pool_get_formant")
+        return float(v.value) if on.value else None
 
     def last_launches(self):
         """Kernels launched by the last feed() or feed_device(); 1 after a save() or restore() of any number of slots."""

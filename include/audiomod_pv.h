@@ -147,6 +147,50 @@ int32_t pv_retrieve(pv_engine *e, float *const *out, int32_t n);
 int pv_get_info(const pv_engine *e, pv_info *info);
 
 /* ----------------------------------------------------------------------------------------------
+ * Formant setting: the cepstral envelope shift of PV_MODE_FORMANT_CEPSTRAL (the reference's
+ * formantShiftSlice(channel, env_comp)) as a run-time setting of an object of the two plain modes, with the
+ * formants moved independently of the pitch.  A stream's setting is off (the default) or on at formant_semitones:
+ *   ratio    = formant_semitones == 0 ? 1.0f : (float)pow(2.0, formant_semitones / 12)   (float quotient, double pow,
+ *                                                                                         as the pitch scale is made)
+ *   env_comp = pitch_scale / ratio                                                        (float quotient)
+ * With the knob at 0 env_comp is pv_info.pitch_scale bit for bit -- mode FORMANT_CEPSTRAL's value: formant-preserving
+ * shift; at +x the formants move up x semitones, at the pitch's own value they follow the pitch (env_comp 1).  The
+ * stage runs for a slice when the setting is on and env_comp != 1.0f (the mode likewise skips it at pitch scale 1),
+ * between the phase stage and synthesis, exactly where the mode's launch sits; it rewrites the slice's magnitude plane
+ * in place, so the pv_debug_*_planes taps return the shifted magnitudes, as they do for the mode.  With the setting
+ * off an object launches what it always launched.  The stage has one arithmetic under either pv_set_arithmetic value.
+ * Scope (every entry point, decided before any device call; a refused call changes nothing): cfg.mode NORMAL_SHIFT or
+ * NORMAL_STRETCH, anything else PV_ERR_UNSUPPORTED (for FORMANT_CEPSTRAL pv_last_error() says that the mode already
+ * fixes it); a non-finite formant_semitones or |formant_semitones| > 48: PV_ERR_INVALID_ARG.  on == 0 ignores the value.
+ *   pv_formant_env_comp     : host only: the env_comp of a stream shifted by pitch_semitones with the knob at
+ *                             formant_semitones (PV_ERR_INVALID_ARG for NULL, a non-finite pitch, a value out of range)
+ *   pv_set_formant          : the slices of later pv_feed calls
+ *   pv_batch_set_formant    : one value for the batch; the launches enqueued after the call (pv_batch_run,
+ *                             pv_batch_run_span).  Nothing enqueued earlier is waited for or changed
+ *   pv_pool_set_formant     : per slot, changeable between feeds: the slices of later pv_pool_feed /
+ *                             pv_pool_feed_device calls.  Host state only -- no wait while device feeds are in flight.
+ *                             pv_pool_open* starts a slot with the setting off.  A snapshot blob does not carry the
+ *                             setting (its format is unchanged): pv_pool_restore leaves the new slot OFF and the caller
+ *                             sets it again.  pv_pool_last_launches grows by one for a feed's launch group in which at
+ *                             least one listed slot runs the stage; PV_ERR_INVALID_ARG for a slot that is not open
+ *   pv_pool_get_formant     : the slot's setting (either pointer may be NULL); formant_semitones reads 0 when off
+ *   pv_mbatch_set_formant   : per stream, formant_semitones[nstreams]: NaN = off; NULL = all off.  The slot tables are
+ *                             resident on the device: the call synchronises the device (as pv_mbatch_redraw does), writes
+ *                             them and recomputes pv_mbatch_kernel_launches (+ 1 per launch group that holds a stream
+ *                             running the stage).  pv_mbatch_run, _run_pcm and _run_pcm_host follow.  pv_mbatch_redraw
+ *                             resets every stream to off: the object is again what a new one would be
+ * -------------------------------------------------------------------------------------------- */
+struct pv_batch; /* (the objects of the sections below) */
+struct pv_pool;
+struct pv_mbatch;
+int pv_formant_env_comp(float pitch_semitones, float formant_semitones, float *env_comp);
+int pv_set_formant(pv_engine *e, int on, float formant_semitones);
+int pv_batch_set_formant(struct pv_batch *b, int on, float formant_semitones);
+int pv_pool_set_formant(struct pv_pool *p, int32_t slot, int on, float formant_semitones);
+int pv_pool_get_formant(const struct pv_pool *p, int32_t slot, int *on, float *formant_semitones);
+int pv_mbatch_set_formant(struct pv_mbatch *b, const float *formant_semitones);
+
+/* ----------------------------------------------------------------------------------------------
  * Stream pool: up to `capacity` independent LIVE streams of one configuration on one device, each
  * with the semantics of a pv_engine (same cfg, same pv_set_arithmetic setting when the pool is
  * created): fed the same blocks and retrieved between calls, a slot returns bit for bit what that
@@ -565,6 +609,9 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
  *                        (fft size / 2: 128 ... 4096).  The batch set counts the batch path and the single-stream
  *                        engine, the vocoder modes' carrier launch included.  Read through the call only: neither
  *                        census file lists it.  PV_CENSUS_ANALYZE stays what it was
+ *   PV_CENSUS_CEPSTRAL : the cepstral formant stage of all four sets: a = the kernel launched (PV_CEP_KERNEL_*), b = NC
+ *                        (fft size / 2: 128 ... 4096).  The batch set counts the batch path and the single-stream engine
+ *                        (mode FORMANT_CEPSTRAL and the formant setting alike).  Read through the call only
  * Process-wide and off by default (a launch then tests one flag).  pv_debug_chain_census(on) clears the counts and
  * switches counting on or off; pv_debug_chain_census_count returns a key's count, -1 for a key that does not exist.
  * If the environment variable AUDIOMOD_PV_CHAIN_CENSUS names a file when the library is loaded, the census is on from
@@ -577,6 +624,10 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
 #define PV_CENSUS_PHASE 3
 #define PV_CENSUS_RESAMPLE_RUNG 4
 #define PV_CENSUS_ANALYSIS_KERNEL 5
+#define PV_CENSUS_CEPSTRAL 7 /* (6 is no kind: -1 for every key, as for any other number) */
+#define PV_CEP_KERNEL_GENERIC 0 /* pv_cepstral_kernel: LDS butterflies, any size */
+#define PV_CEP_KERNEL_WAVE 1    /* a slice per wave: pv_cepstral_wave_kernel (fft 2048 / 4096), or inside the stream kernel */
+#define PV_CEP_KERNEL_SLOT 2    /* pv_slot_cepstral_wave_kernel: the slot-table sets (fft 512 ... 4096) */
 #define PV_ANA_KERNEL_GENERIC 0 /* pv_analyze_kernel: LDS butterflies, any size (fft 256 and 8192) */
 #define PV_ANA_KERNEL_WAVE 1    /* a frame per wave (fft 512 ... 4096): pv_analyze_wave_kernel, pv_pool_ / pv_pmix_ / pv_mb_ */
 #define PV_ANA_KERNEL_SPLIT 2   /* a 4096-point frame on two waves */

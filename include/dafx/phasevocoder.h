@@ -2,8 +2,8 @@
 //
 // Same public surface as the reference class (reference include/dafx/phasevocoder.h:42-117):
 // constructor signature and defaults (:54), processBlock / outputReady (real-time, :74,80),
-// processInData / getOutData / getOutSamples (offline, :76-78), no-op setParams / getParams
-// (:62-72) and the mode / coremode macros (:22-36).  Underneath it binds the C ABI of
+// processInData / getOutData / getOutSamples (offline, :76-78), setParams / getParams (:62-72, empty
+// bodies there; here they carry one key of this engine's own, below) and the mode / coremode macros (:22-36).  Underneath it binds the C ABI of
 // include/audiomod_pv.h instead of the reference's phasevocodercore.
 #pragma once
 
@@ -39,8 +39,13 @@ class phasevocoder : public modbase, public modbase_offline {
                  int coremode = PHASE_LOCKED, int fftsize = 2048, int hopsize = 0);
     ~phasevocoder();
 
-    void setParams(std::map<std::string, float> params) { (void)params; }
-    void getParams(std::map<std::string, float> &params) { (void)params; }
+    // One key, an extension of this engine: "formant_semitones" turns the formant setting on at that value for the
+    // slices of later calls (audiomod_pv.h "Formant setting": modes NORMAL_SHIFT and NORMAL_STRETCH; 0 keeps the
+    // formants where they are whatever the pitch does), a NaN turns it off.  A refused value is reported on stderr and
+    // changes nothing, like every other entry point.  Other keys are ignored, as the reference ignores all of them.
+    // getParams adds the key while the setting is on.
+    void setParams(std::map<std::string, float> params);
+    void getParams(std::map<std::string, float> &params);
 
     void processBlock(float *const *bufferData, int num_samples);
     void processInData(float *const *inData, int num_in_samples);
@@ -54,6 +59,8 @@ class phasevocoder : public modbase, public modbase_offline {
     pv_engine *engine_;
     int mode_;
     bool outready_;
+    bool formant_on_;
+    float formant_semitones_;
 };
 
 } // namespace audiomod

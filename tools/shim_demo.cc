@@ -1,10 +1,12 @@
 // tools/shim_demo.cc -- drives the drop-in audiomod::phasevocoder exactly like the reference CLI's two loops
 // (reference main/main.cc:471-510 offline, :561-572 real-time) on a raw planar float32 file.
-// usage: shim_demo api in.f32 out.f32 counts.txt ch frames sr timeratio semis mode coremode fft block flush
-// (same argument order as oracle/ref_driver.cc, so tests can compare the two programs' outputs directly)
+// usage: shim_demo api in.f32 out.f32 counts.txt ch frames sr timeratio semis mode coremode fft block flush [formant]
+// (same argument order as oracle/ref_driver.cc, so tests can compare the two programs' outputs directly; the optional
+// last argument goes through setParams as "formant_semitones", this engine's extension, and must come back from getParams)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -26,6 +28,15 @@ int main(int argc, char **argv) {
         if (fread(in[c].data(), 4, frames, f) != (size_t)frames) return 1;
     fclose(f);
     audiomod::phasevocoder pv(sr, ch, timeratio, semis, mode, coremode, fftsize);
+    if (argc > 15) {
+        const float formant = (float)atof(argv[15]);
+        std::map<std::string, float> params;
+        pv.getParams(params);
+        if (!params.empty()) return 3; // off by default: nothing to report
+        pv.setParams({{"formant_semitones", formant}, {"some_other_key", 1.0f}});
+        pv.getParams(params);
+        if (params.size() != 1 || params["formant_semitones"] != formant) return 3;
+    }
     modbase *rt = &pv;
     modbase_offline *off = &pv;
     std::vector<std::vector<float>> bs(ch, std::vector<float>(block)), os(ch, std::vector<float>(block * 64));
