@@ -183,6 +183,7 @@ struct BatchJob {
     int64_t out_frames = 0; // as pv_mbatch_layout plans it (batch route)
     bool batch_route = false, failed = false, done = false;
     std::string reason;
+    int64_t slices = 0; // (mixed-batch route: the stream's slices, for the whisper table's estimate)
     long written = 0;
     void fail(const std::string &why) {
         if (!failed && !done) failed = true, reason = why;
@@ -207,10 +208,12 @@ std::string engine_error(int st) { return std::string(pv_strerror(st)) + ": " + 
 
 // one group (equal rate and channels) of jobs the mixed batch accepts, sub-batch by sub-batch
 void run_group_batched(const Model &model, const pv_config &cfg, std::vector<BatchJob *> &jobs, float amount, int64_t budget,
-                       int device, const Formant &fx) {
+                       int device, const Formant &fx, bool whisper) {
     const int C = cfg.channels, block = pvcli::block_size(cfg.sample_rate), flush = model.stretch ? 0 : 1;
     std::vector<pvcli::ClipSize> sizes;
-    for (const BatchJob *j : jobs) sizes.push_back(pvcli::ClipSize{j->frames, j->out_frames, j->bits / 8});
+    for (const BatchJob *j : jobs)
+        sizes.push_back(pvcli::ClipSize{j->frames, j->out_frames, j->bits / 8,
+                                        whisper ? j->slices * C * (int64_t)(cfg.fftsize / 2 + 8) * 4 : 0});
     pv_mbatch *mb = nullptr;
     size_t mb_clips = 0;
     PinnedBuf h_in, h_out;
@@ -242,6 +245,10 @@ void run_group_batched(const Model &model, const pv_config &cfg, std::vector<Bat
         if (st == PV_OK && fx.on) { // (a re-drawn object is back to off, like a new one)
             const std::vector<float> knob(n, fx.semitones);
             st = pv_mbatch_set_formant(mb, knob.data());
+        }
+        if (st == PV_OK && whisper) { // (likewise: a re-drawn object is all robotic)
+            const std::vector<int32_t> voice(n, PV_VOICE_WHISPER);
+            st = pv_mbatch_set_voice(mb, voice.data());
         }
         if (st != PV_OK) {
             fail_all(engine_error(st));
@@ -380,7 +387,9 @@ int batch_main(int argc, char **argv) {
         cfg.channels = first.channels;
         cfg.time_ratio = model->stretch ? amount : 1.0f;
         cfg.pitch_semitones = model->stretch ? 0.0f : amount;
-        cfg.mode = model->mode;
+        // whisper: a ROBOTIC mixed batch with every stream's voice set (the voice setting) -- the same streams, bit for bit
+        const bool whisper = model->mode == WHISPER;
+        cfg.mode = whisper ? ROBOTIC : model->mode;
         cfg.coremode = model->takes_args ? atoi(pos[1]) : PHASE_LOCKED;
         cfg.fftsize = model->takes_args ? atoi(pos[2]) : 2048;
         cfg.hopsize = 0;
@@ -392,12 +401,12 @@ int batch_main(int argc, char **argv) {
             const pv_mbatch_stream s{j.frames, model->stretch ? a : 1.0f, model->stretch ? 0.0f : a};
             // a job the mixed batch's layout refuses (a mode or size outside its scope, no frames, a pitch whose
             // filter does not fit) takes the single-file route
-            if (pv_mbatch_layout(&cfg, &s, 1, block, flush, &j.out_frames, nullptr, nullptr, nullptr, nullptr, nullptr) == PV_OK) {
+            if (pv_mbatch_layout(&cfg, &s, 1, block, flush, &j.out_frames, &j.slices, nullptr, nullptr, nullptr, nullptr) == PV_OK) {
                 j.batch_route = true;
                 batched.push_back(&j);
             }
         }
-        if (!batched.empty()) run_group_batched(*model, cfg, batched, amount, budget, device, fx);
+        if (!batched.empty()) run_group_batched(*model, cfg, batched, amount, budget, device, fx, whisper);
     }
     for (BatchJob &j : jobs) {
         if (j.failed || j.done || j.batch_route) continue;

@@ -269,6 +269,8 @@ inline int block_size(int rate) { return rate / 100 < 480 ? 480 : rate / 100; } 
 struct ClipSize {
     int64_t frames = 0, out_frames = 0;
     int bytes_per_sample = 2;
+    int64_t table_bytes = 0; // whisper: the clip's own phases, slices x channels x (fftsize / 2 + 8) floats -- an upper
+                             // bound of its share: a sub-batch holds one table, the longest clip's
 };
 constexpr int64_t kDescriptorBytesPerOutFrame = 14; // per output frame and stream
 
@@ -286,7 +288,7 @@ inline int64_t clip_estimate(const ClipSize &c, int channels) {
     };
     const int64_t per_channel =
         add(mul(c.out_frames, kDescriptorBytesPerOutFrame + 4 + 2), mul(c.frames, 4 + (int64_t)c.bytes_per_sample));
-    return mul(per_channel, channels);
+    return add(mul(per_channel, channels), c.table_bytes < 0 ? 0 : c.table_bytes);
 }
 
 // [begin, end) ranges in order: none holds more than 65535 / channels clips, none exceeds `budget_bytes` by

@@ -25,6 +25,7 @@
 #include "pv_wavefft.h"
 #include "pv_plan.h"
 #include "pv_snapshot.h"
+#include "pv_whisper.h"
 
 namespace pv {
 
@@ -1432,8 +1433,15 @@ struct pv_pool {
         // the formant setting (pv_pool_set_formant): host state, read when a feed builds the slot's PoolSlot
         bool fx_on = false;
         float fx_semitones = 0.f;
+        // the voice setting (pv_pool_set_voice): host state, read when a feed builds the slot's PoolSlot
+        int voice = PV_VOICE_ROBOTIC;
     };
     std::vector<Slot> slots;
+    // The voice setting's device side, allocated by the first feed (or restore) that has a whisper slot: the generator
+    // state rows [cap + 1][kWhisperStatePitch] -- row `cap` is the constant fresh state, which a stream's first launch
+    // reads instead of its own row -- and the phases of one launch group, [cap][kStreamChunk][C][HP]
+    DevBuf<uint32_t> d_wstate;
+    DevBuf<float> d_wphase;
     // Mixed pool (pv_pool_create_mixed): the range a slot's pitch / time ratio may take, and what the buffers were sized
     // for (checked again for every slot at open)
     bool mixed = false;
@@ -2602,7 +2610,8 @@ static bool pool_slot_ok(const pv_pool *p, int32_t slot) {
     return p && slot >= 0 && slot < p->cap && p->slots[(size_t)slot].open;
 }
 
-static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true, const PoolLaunch *fx = nullptr);
+static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true, const PoolLaunch *fx = nullptr,
+                             const float *whisper = nullptr);
 
 // Core::init and pool_create allocate with DevBuf::alloc, whose zero fill is on the default stream; nothing orders that
 // stream against the pool's own non-blocking one.  pv_pool_create therefore ends with a wait for the fills, so that no
@@ -2936,6 +2945,7 @@ static void pool_slot_begin(pv_pool *p, int32_t s, std::unique_ptr<Derived> own,
     sl.tap_n = 0;
     sl.acc_half = 0;
     sl.fx_on = false, sl.fx_semitones = 0.f;
+    sl.voice = PV_VOICE_ROBOTIC;
     sl.outq.assign((size_t)c.C, std::vector<float>());
     sl.outq_head = 0;
     sl.open = true;
@@ -2995,6 +3005,7 @@ static char *pool_snap_buffer(const pv_pool *p, int buf, size_t *bytes) {
 // the kernel takes its bounds from these sizes.)
 static int pool_snap_check_buffers(const pv_pool *p, const snap::Header &h) {
     for (int b = 0; b < snap::kBufCount; ++b) {
+        if (b == snap::kBufWhisper) continue; // (d_wstate: cap + 1 rows of the entry's size, made on demand)
         size_t have = 0;
         const char *base = pool_snap_buffer(p, b, &have);
         const int64_t per = snap::seg_bytes(h, b);
@@ -3123,6 +3134,116 @@ int pv_pool_get_formant(const pv_pool *p, int32_t slot, int *on, float *formant_
     return PV_OK;
 }
 
+// ---- the voice setting (audiomod_pv.h "Voice setting"): what the slot-table forms share
+// the state of a stream that has drawn nothing: the words that follow rand()'s 310 warm-up draws (pv_whisper.h)
+static const std::vector<uint32_t> &whisper_fresh_state() {
+    static const std::vector<uint32_t> fresh = [] {
+        std::vector<uint32_t> v((size_t)kWhisperHist);
+        WhisperRng rng;
+        for (uint32_t &w : v) w = rng.next_word();
+        return v;
+    }();
+    return fresh;
+}
+static int voice_scope_check(const pv_config &cfg) {
+    if (cfg.mode == PV_MODE_ROBOTIC) return PV_OK;
+    g_last_error = "voice setting: the voice belongs to ROBOTIC objects (create the pool or mixed batch with mode ROBOTIC)";
+    return PV_ERR_UNSUPPORTED;
+}
+static int voice_value_check(int voice) {
+    if (voice == PV_VOICE_ROBOTIC || voice == PV_VOICE_WHISPER) return PV_OK;
+    g_last_error = "voice setting: unknown voice " + std::to_string(voice);
+    return PV_ERR_INVALID_ARG;
+}
+// floats of one slot's region of the phase buffer
+static size_t pool_wphase_stride(const pv_pool *p) { return (size_t)kStreamChunk * p->core.C * p->core.HP; }
+// the pool's generator buffers, made in stream order by the first call that needs them
+static int pool_voice_buffers(pv_pool *p) {
+    if (p->d_wstate.p && p->d_wphase.p) return PV_OK;
+    int st;
+    if ((st = p->d_wstate.alloc_on((size_t)(p->cap + 1) * kWhisperStatePitch, p->stream)) != PV_OK) return st;
+    if ((st = p->d_wphase.alloc_on((size_t)p->cap * pool_wphase_stride(p), p->stream)) != PV_OK) return st;
+    HIPC(hipMemcpyAsync(p->d_wstate.p + (size_t)p->cap * kWhisperStatePitch, whisper_fresh_state().data(),
+                        (size_t)kWhisperHist * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    return PV_OK;
+}
+
+// The slot's voice: host state that the next feed's descriptor building reads, as the formant setting.  Only before the
+// slot's first slice: a change in mid-stream has no reference to be held to.
+int pv_pool_set_voice(pv_pool *p, int32_t slot, int voice) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p) return PV_ERR_INVALID_ARG;
+    int st = voice_scope_check(p->core.d.cfg);
+    if (st != PV_OK) return st;
+    if (!pool_slot_ok(p, slot)) {
+        g_last_error = "stream pool: slot " + std::to_string(slot) + " is not open";
+        return PV_ERR_INVALID_ARG;
+    }
+    if ((st = voice_value_check(voice)) != PV_OK) return st;
+    pv_pool::Slot &sl = p->slots[(size_t)slot];
+    if (sl.slices != 0) {
+        g_last_error = "voice setting: slot " + std::to_string(slot) + " has processed slices (the voice is set before the first)";
+        return PV_ERR_INVALID_ARG;
+    }
+    sl.voice = voice;
+    return PV_OK;
+}
+
+int pv_pool_get_voice(const pv_pool *p, int32_t slot, int *voice) {
+    if (!pool_slot_ok(p, slot)) return PV_ERR_INVALID_ARG;
+    if (voice) *voice = p->slots[(size_t)slot].voice;
+    return PV_OK;
+}
+
+// Diagnostics: the production generator kernel alone.  One stream from the fresh state, `ncalls` launches of counts[i]
+// draws each with the state carried in device memory between them (the first reads the fresh row, as a slot's first
+// launch does); the phases of all launches, concatenated, to out.
+int pv_debug_whisper_phases(const int64_t *counts, int32_t ncalls, float *out, int device) {
+    g_last_error.clear();
+    if (ncalls < 0 || (ncalls > 0 && !counts)) return PV_ERR_INVALID_ARG;
+    int64_t total = 0;
+    for (int32_t i = 0; i < ncalls; ++i) {
+        if (counts[i] < 0 || counts[i] > 0x7fffffff) return PV_ERR_INVALID_ARG;
+        total += counts[i];
+    }
+    if (total > 0 && !out) return PV_ERR_INVALID_ARG;
+    if (count_gfx950() <= 0) {
+        g_last_error = "no gfx950 (MI355X) device visible: this library has no CPU fallback";
+        return PV_ERR_NO_DEVICE;
+    }
+    HIPC(hipSetDevice(device));
+    DevBuf<uint32_t> state; // rows: fresh, the stream's
+    DevBuf<float> phases;
+    DevBuf<WhisperJob> jobs;
+    int st;
+    if ((st = state.alloc(2 * (size_t)kWhisperStatePitch)) != PV_OK || (st = phases.alloc((size_t)total)) != PV_OK) return st;
+    std::vector<WhisperJob> hj((size_t)ncalls);
+    int64_t off = 0;
+    bool first = true;
+    for (int32_t i = 0; i < ncalls; ++i) {
+        WhisperJob &wj = hj[(size_t)i];
+        wj.src_off = first && counts[i] > 0 ? 0 : kWhisperStatePitch;
+        wj.dst_off = kWhisperStatePitch;
+        wj.out_off = off;
+        wj.count = counts[i];
+        wj.per = counts[i] > 0 ? (int32_t)counts[i] : 1, wj.pitch = 0; // (one row: draw i at out_off + i)
+        if (counts[i] > 0) first = false;
+        off += counts[i];
+    }
+    if ((st = jobs.upload(hj)) != PV_OK) return st;
+    HIPC(hipMemcpy(state.p, whisper_fresh_state().data(), (size_t)kWhisperHist * sizeof(uint32_t), hipMemcpyHostToDevice));
+    for (int32_t i = 0; i < ncalls; ++i) {
+        if (counts[i] == 0) continue;
+        launch_whisper(state.p, phases.p, jobs.p + i, 1, PV_CENSUS_SET_BATCH, 1024, nullptr);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "voice generator launch", __LINE__);
+    }
+    HIPC(hipDeviceSynchronize());
+    if (total > 0) HIPC(hipMemcpy(out, phases.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+    return PV_OK;
+}
+
 int32_t pv_pool_retrieve(pv_pool *p, int32_t slot, float *const *out, int32_t n) {
     if (!pool_slot_ok(p, slot) || n < 0 || (n > 0 && !out)) return -1;
     pv_pool::Slot &sl = p->slots[(size_t)slot];
@@ -3164,7 +3285,10 @@ static CepstralArgs slot_cepstral_args(const Core &c) {
 // the stages of one launch group for every slot in it (Core's argument builders with rows = C);
 // launch = false: launch nothing, only ask the launchers whether this configuration fits them (pv_pool_create)
 // fx: the table of the group's slots that run the formant stage (null: none does)
-static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch, const PoolLaunch *fx) {
+// whisper: the phase buffer where the group holds a whisper slot (PoolSlot::wh_off), drawn by the caller's generator
+// launch; else null
+static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch, const PoolLaunch *fx,
+                             const float *whisper) {
     const Core &c = p->core;
     const Derived &d = c.d;
     hipStream_t st = p->stream;
@@ -3197,7 +3321,8 @@ static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch
         if (!launch_slot_cepstral(slot_cepstral_args(c), *fx, PV_CENSUS_SET_POOL, st)) return refused("formant");
         if ((rc = launched("pool formant launch")) != PV_OK) return rc;
     }
-    const SynthArgs sa = c.synth_args(c.C);
+    SynthArgs sa = c.synth_args(c.C);
+    if (whisper) sa.whisper = whisper;
     const ChainArgs ca = c.chain_args(c.C);
     if (!launch_pool_synth_chain(sa, ca, pl, st, launch)) return refused("synthesis + overlap-add");
     if (launch && (rc = launched("pool synthesis + overlap-add launch")) != PV_OK) return rc;
@@ -3226,7 +3351,8 @@ static size_t variant_group_end(const std::vector<VariantRun> &runs, size_t a) {
     return e;
 }
 static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const PoolParams *q,
-                                 const std::vector<VariantRun> &runs, int *nlaunch, const PoolLaunch *fx) {
+                                 const std::vector<VariantRun> &runs, int *nlaunch, const PoolLaunch *fx,
+                                 const float *whisper) {
     const Core &c = p->core;
     const Derived &d = c.d; // (only what every slot shares: sizes, mode, coremode)
     hipStream_t st = p->stream;
@@ -3272,6 +3398,7 @@ static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const P
         sa.do_freq_comp = ra0.dfc;
         sa.freq_comp = 1;
         sa.fixed_gain = 1;
+        if (whisper) sa.whisper = whisper;
         ChainArgs ca = c.chain_args(c.C);
         ca.stream = stream;
         ca.resample = ra0.res;
@@ -3502,6 +3629,8 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         int nslots, ningest, max_tn, max_tiles, max_in;
         int64_t fx_off; // the entries of the slots that run the formant stage, once more: that launch's table
         int fx_nslots, fx_max_tn;
+        int64_t wj_off; // the generator's jobs: one per whisper slot of the group
+        int nwj;
     };
     std::vector<Group> grp((size_t)groups + 1); // (+ the final ingest of what the call leaves unconsumed)
     std::vector<PoolSlot> table, fx_table;
@@ -3511,6 +3640,7 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
     std::vector<std::vector<VariantRun>> vruns((size_t)groups);
     std::vector<int> vkey;
     std::vector<PoolIngest> ingest;
+    std::vector<WhisperJob> wjobs;
     std::vector<int32_t> pinc;
     std::vector<float> wden, wden_hi;
     std::vector<ChainSlice> cs;
@@ -3531,11 +3661,13 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         sl.uploaded = upto;
     };
     for (int32_t i = 0; i < count; ++i) p->slots[(size_t)slots[i]].fed += n[i];
+    bool any_whisper = false;
     for (int gi = 0; gi < groups; ++gi) {
         Group &g = grp[(size_t)gi];
-        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         table.clear();
         fx_table.clear();
+        wjobs.clear();
         ingest.clear();
         params.clear();
         vkey.clear();
@@ -3586,6 +3718,18 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
             ps.out_off = out_base[(size_t)i] + (ka - k0[(size_t)i]);
             ps.out_stride_row = to_caller ? io.out_pitch : out_cnt[(size_t)i];
             ps.k_base = ka;
+            ps.wh_off = -1;
+            if (sl.voice == PV_VOICE_WHISPER) {
+                // the slot's draws of this launch, in the reference's order: slice-major, channel, bins 0 .. hs.  A
+                // stream's first launch starts from the pool's fresh state, every later one from the slot's own row
+                WhisperJob wj{};
+                wj.src_off = (int64_t)(t0 == 0 ? p->cap : slots[i]) * kWhisperStatePitch;
+                wj.dst_off = (int64_t)slots[i] * kWhisperStatePitch;
+                wj.out_off = ps.wh_off = (int64_t)slots[i] * (int64_t)pool_wphase_stride(p);
+                wj.count = (int64_t)Tn * C * (sd.hs + 1);
+                wj.per = sd.hs + 1, wj.pitch = c.HP;
+                wjobs.push_back(wj);
+            }
             if (sl.fx_on) {
                 const float env_comp = formant_env_comp_of(sd.pitch_scale, sl.fx_semitones);
                 if (env_comp != 1.0f) { // (as mode FORMANT_CEPSTRAL skips the stage at pitch scale 1)
@@ -3648,12 +3792,15 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         g.table_off = put(table.data(), table.size() * sizeof(PoolSlot));
         g.fx_nslots = (int)fx_table.size();
         g.fx_off = put(fx_table.data(), fx_table.size() * sizeof(PoolSlot));
+        g.nwj = (int)wjobs.size();
+        g.wj_off = put(wjobs.data(), wjobs.size() * sizeof(WhisperJob));
+        any_whisper = any_whisper || !wjobs.empty();
         g.ningest = (int)ingest.size();
         g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
     }
     {
         Group &g = grp[(size_t)groups];
-        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         ingest.clear();
         for (int32_t i = 0; i < count; ++i) add_ingest(i, p->slots[(size_t)slots[i]].fed, g);
         g.ningest = (int)ingest.size();
@@ -3685,6 +3832,7 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
     }
     memcpy(blk->h.p, blob.data(), blob.size());
     char *const d_desc = blk->d.p;
+    if (any_whisper && (st = pool_voice_buffers(p)) != PV_OK) return fail(st);
     // 4. the copies and the launches.  pv_pool_feed: the previous call has finished with both staging buffers.
     // pv_pool_feed_device: the pool's stream first waits for what the caller's stream holds now (the producer of d_in,
     // the last reader of d_out).
@@ -3723,11 +3871,20 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         fx.nslots = g.fx_nslots;
         fx.max_tn = g.fx_max_tn;
         const PoolLaunch *const fxp = g.fx_nslots > 0 ? &fx : nullptr;
+        const float *whisper = nullptr;
+        if (g.nwj > 0) { // the group's whisper slots draw their phases: one launch, one wave per slot
+            launch_whisper(p->d_wstate.p, p->d_wphase.p, reinterpret_cast<const WhisperJob *>(d_desc + g.wj_off), g.nwj,
+                           p->mixed ? PV_CENSUS_SET_PMIX : PV_CENSUS_SET_POOL, c.d.fft.nc, p->stream);
+            ++nlaunch;
+            const hipError_t we = hipGetLastError();
+            if (we != hipSuccess) return fail(hip_fail(we, "voice generator launch", __LINE__));
+            whisper = p->d_wphase.p;
+        }
         if (p->mixed) {
             const PoolParams *q = reinterpret_cast<const PoolParams *>(d_desc + params_off[(size_t)gi]);
-            if ((st = pool_mix_launch_group(p, pl, q, vruns[(size_t)gi], &nlaunch, fxp)) != PV_OK) return fail(st);
+            if ((st = pool_mix_launch_group(p, pl, q, vruns[(size_t)gi], &nlaunch, fxp, whisper)) != PV_OK) return fail(st);
         } else {
-            if ((st = pool_launch_group(p, pl, true, fxp)) != PV_OK) return fail(st);
+            if ((st = pool_launch_group(p, pl, true, fxp, whisper)) != PV_OK) return fail(st);
             nlaunch += 2 + (cm == 0 || cm == 1 ? 1 : 0) + (c.d.resample && pl.max_tiles > 0 ? 1 : 0) + (fxp ? 1 : 0);
         }
     }
@@ -3866,6 +4023,7 @@ static void pool_snap_header(const pv_pool *p, const pv_pool::Slot &sl, snap::He
     pool_snap_geometry(p, h);
     h.time_ratio = sl.d->cfg.time_ratio;
     h.pitch_semitones = sl.d->cfg.pitch_semitones;
+    if (sl.voice == PV_VOICE_WHISPER) h.mode = PV_MODE_WHISPER; // (the stream is that engine's: a version-2 blob)
     snap::fill_sizes(h, (int32_t)sl.chain->live.size(), pool_slot_pending(sl));
 }
 // the first field in which a blob's pool differs from this one (nullptr: none).  Both sides are pools' own derived
@@ -3875,7 +4033,7 @@ static const char *pool_snap_mismatch(const snap::Header &blob, const snap::Head
     if (blob.f != pool.f) return name
     PV_SNAP_FIELD(sample_rate, "sample rate");
     PV_SNAP_FIELD(channels, "channels");
-    PV_SNAP_FIELD(mode, "mode");
+    if ((blob.mode == PV_MODE_WHISPER ? PV_MODE_ROBOTIC : blob.mode) != pool.mode) return "mode"; // (the voice setting)
     PV_SNAP_FIELD(coremode, "coremode");
     PV_SNAP_FIELD(N, "FFT size");
     PV_SNAP_FIELD(hopsize, "hop setting");
@@ -3926,12 +4084,14 @@ static int pool_snap_reserve(pv_pool *p, size_t stage_bytes, size_t nsegs) {
 // The call's segment table: entry i of `slot_of` is staged at i * snap::device_bytes(h), its buffers in directory
 // order, each padded to 16 bytes -- a blob's payload as it is.  Returns the number of segments; *parts: workgroups per
 // segment (about 64 KB each, and about 4096 workgroups in all at the most).
-static int pool_snap_table(pv_pool *p, const snap::Header &h, const std::vector<int32_t> &slot_of, int *parts) {
+// (hd[i]: blob i's header -- a whisper slot's payload has one segment more; stage_off[i]: where it is staged)
+static int pool_snap_table(pv_pool *p, const std::vector<snap::Header> &hd, const std::vector<int32_t> &slot_of,
+                           const std::vector<int64_t> &stage_off, int *parts) {
     int n = 0;
     int64_t largest = 0;
-    const int64_t dev = snap::device_bytes(h);
     for (size_t i = 0; i < slot_of.size(); ++i) {
-        int64_t off = (int64_t)i * dev;
+        const snap::Header &h = hd[i];
+        int64_t off = stage_off[i];
         for (int b = 0; b < snap::kBufCount; ++b)
             if (const int64_t per = snap::seg_bytes(h, b)) {
                 p->h_seg.p[n++] = SnapSeg{b, 0, (int64_t)slot_of[i] * per, off, per};
@@ -3948,7 +4108,7 @@ static SnapArgs pool_snap_args(const pv_pool *p, bool to_stage) {
     SnapArgs a{};
     for (int b = 0; b < snap::kBufCount; ++b) {
         size_t have;
-        a.bufs[b] = pool_snap_buffer(p, b, &have);
+        a.bufs[b] = b == snap::kBufWhisper ? reinterpret_cast<char *>(p->d_wstate.p) : pool_snap_buffer(p, b, &have);
     }
     a.segs = p->seg_dev;
     a.stage = p->d_snap.p;
@@ -3956,6 +4116,22 @@ static SnapArgs pool_snap_args(const pv_pool *p, bool to_stage) {
     return a;
 }
 static_assert(snap::kBufCount <= kSnapBufs, "SnapArgs holds every buffer of a blob");
+
+// where each blob's device payload is staged, one behind the other; returns the total
+static int64_t pool_snap_stage_layout(const std::vector<snap::Header> &hd, std::vector<int64_t> &stage_off) {
+    int64_t total = 0;
+    stage_off.clear();
+    for (const snap::Header &h : hd) {
+        stage_off.push_back(total);
+        total += snap::device_bytes(h);
+    }
+    return total;
+}
+static bool pool_snap_any_voice(const std::vector<snap::Header> &hd) {
+    for (const snap::Header &h : hd)
+        if (h.mode == PV_MODE_WHISPER) return true;
+    return false;
+}
 
 int64_t pv_pool_snapshot_bytes(const pv_pool *p, int32_t slot) {
     if (!pool_slot_ok(p, slot)) return -1;
@@ -4000,18 +4176,20 @@ int pv_pool_save(pv_pool *p, int32_t count, const int32_t *slots, void *const *b
     if ((st = pool_snap_check_buffers(p, hd[0])) != PV_OK) return st;
     HIPC(hipSetDevice(c.device));
     if ((st = pool_drain(p)) != PV_OK) return st; // (the device feeds in flight come first, as for pv_pool_feed)
-    const int64_t dev = snap::device_bytes(hd[0]);
-    if ((st = pool_snap_reserve(p, (size_t)dev * (size_t)count, (size_t)count * snap::kBufCount)) != PV_OK) return st;
+    std::vector<int64_t> stage_off;
+    const int64_t dev_total = pool_snap_stage_layout(hd, stage_off);
+    if ((st = pool_snap_reserve(p, (size_t)dev_total, (size_t)count * snap::kBufCount)) != PV_OK) return st;
+    if (pool_snap_any_voice(hd) && (st = pool_voice_buffers(p)) != PV_OK) return st;
     auto fail = [&](int code) {
         p->poisoned = code;
         p->poison_reason = g_last_error.empty() ? pv_strerror(code) : g_last_error;
         return code;
     };
     int parts = 1;
-    const int nsegs = pool_snap_table(p, hd[0], std::vector<int32_t>(slots, slots + count), &parts);
+    const int nsegs = pool_snap_table(p, hd, std::vector<int32_t>(slots, slots + count), stage_off, &parts);
     launch_pool_snapshot(pool_snap_args(p, true), nsegs, parts, p->stream);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(p->h_snap.p, p->d_snap.p, (size_t)dev * (size_t)count, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->h_snap.p, p->d_snap.p, (size_t)dev_total, hipMemcpyDeviceToHost, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     if (e != hipSuccess) return fail(hip_fail(e, "stream pool save", __LINE__));
     p->last_launches = 1;
@@ -4029,7 +4207,7 @@ int pv_pool_save(pv_pool *p, int32_t count, const int32_t *slots, void *const *b
         uint8_t *blob = static_cast<uint8_t *>(blobs[i]);
         snap::encode_head(h, hs, pend.data(), pool_slot_pending(sl), blob);
         uint8_t *q = blob + snap::payload_offset(h);
-        memcpy(q, p->h_snap.p + (size_t)i * (size_t)dev, (size_t)dev);
+        memcpy(q, p->h_snap.p + (size_t)stage_off[(size_t)i], (size_t)snap::device_bytes(h));
         for (int b = 0; b < snap::kBufCount; ++b) // (the padding between segments is zeros whatever the staging held)
             if (const int64_t per = snap::seg_bytes(h, b)) {
                 memset(q + per, 0, (size_t)(snap::pad16(per) - per));
@@ -4095,8 +4273,10 @@ int pv_pool_restore(pv_pool *p, int32_t count, const void *const *blobs, const i
     // 2. the device side
     HIPC(hipSetDevice(c.device));
     if ((st = pool_drain(p)) != PV_OK) return st;
-    const int64_t dev = snap::device_bytes(hd[0]); // (the same for every blob: it follows from the geometry)
-    if ((st = pool_snap_reserve(p, (size_t)dev * (size_t)count, (size_t)count * snap::kBufCount)) != PV_OK) return st;
+    std::vector<int64_t> stage_off; // (a whisper slot's payload has one segment more than a robotic one's)
+    const int64_t dev_total = pool_snap_stage_layout(hd, stage_off);
+    if ((st = pool_snap_reserve(p, (size_t)dev_total, (size_t)count * snap::kBufCount)) != PV_OK) return st;
+    if (pool_snap_any_voice(hd) && (st = pool_voice_buffers(p)) != PV_OK) return st;
     // a mixed pool's table arena, as pv_pool_open_with: each entry is held from here on, so that two blobs of one new
     // ratio share it
     std::vector<int> tab((size_t)count, -1);
@@ -4110,16 +4290,16 @@ int pv_pool_restore(pv_pool *p, int32_t count, const void *const *blobs, const i
             ++p->tabs[(size_t)tab[(size_t)i]].refs;
         }
     for (int32_t i = 0; i < count; ++i)
-        memcpy(p->h_snap.p + (size_t)i * (size_t)dev, static_cast<const uint8_t *>(blobs[i]) + snap::payload_offset(hd[(size_t)i]),
-               (size_t)dev);
+        memcpy(p->h_snap.p + (size_t)stage_off[(size_t)i],
+               static_cast<const uint8_t *>(blobs[i]) + snap::payload_offset(hd[(size_t)i]), (size_t)snap::device_bytes(hd[(size_t)i]));
     auto fail = [&](int code) {
         p->poisoned = code;
         p->poison_reason = g_last_error.empty() ? pv_strerror(code) : g_last_error;
         return code;
     };
     int parts = 1;
-    const int nsegs = pool_snap_table(p, hd[0], dst, &parts);
-    hipError_t e = hipMemcpyAsync(p->d_snap.p, p->h_snap.p, (size_t)dev * (size_t)count, hipMemcpyHostToDevice, p->stream);
+    const int nsegs = pool_snap_table(p, hd, dst, stage_off, &parts);
+    hipError_t e = hipMemcpyAsync(p->d_snap.p, p->h_snap.p, (size_t)dev_total, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess) {
         launch_pool_snapshot(pool_snap_args(p, false), nsegs, parts, p->stream);
         e = hipGetLastError();
@@ -4141,6 +4321,7 @@ int pv_pool_restore(pv_pool *p, int32_t count, const void *const *blobs, const i
         sl.fed = hs.fed, sl.uploaded = hs.uploaded, sl.slices = hs.slices;
         sl.tap_n = 0; // (a blob carries the recurrences' state, not the planes of its last launch)
         sl.acc_half = hs.acc_half;
+        if (h.mode == PV_MODE_WHISPER) sl.voice = PV_VOICE_WHISPER; // (its state row came with the payload)
         for (int ch = 0; ch < c.C && h.pending > 0; ++ch) {
             sl.outq[(size_t)ch].resize((size_t)h.pending);
             memcpy(sl.outq[(size_t)ch].data(), snap::pending_of(blobs[i], h, ch), (size_t)h.pending * sizeof(float));
@@ -4209,6 +4390,7 @@ struct pv_mbatch {
         int tab = -1, lds_floats = 0, tab_bytes = 0;
         std::vector<Span> wden, otab;
         float env_comp = 0.f; // the formant setting (pv_mbatch_set_formant): its PoolSlot::env_comp, 0 = off
+        int voice = PV_VOICE_ROBOTIC; // the voice setting (pv_mbatch_set_voice)
     };
     std::vector<Stream> s; // (sized once per draw: the plans' builders keep references into it)
     int64_t in_floats = 0, out_floats = 0;
@@ -4221,6 +4403,10 @@ struct pv_mbatch {
     };
     std::vector<Group> groups;
     int kernel_launches = 0; // kernels per run
+    // The voice setting (pv_mbatch_set_voice): the phase table the whisper streams share, [slices][C][HP] from draw 0;
+    // nothing exists before the first call with a whisper stream.
+    DevBuf<float> d_voice;
+    bool voice_on = false; // a stream has the whisper voice: the fused kernel's launches get the table
     bool tap_ran = false;    // pv_debug_mbatch_planes: a run since creation or the last redraw
     // what creation fixed (a redraw re-reads neither the arithmetic setting nor the environment)
     pv_config cfg{};
@@ -4407,6 +4593,7 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
         sa.do_freq_comp = ra0.dfc;
         sa.freq_comp = 1;
         sa.fixed_gain = 1;
+        if (b->voice_on) sa.whisper = b->d_voice.p;
         ChainArgs ca = c.chain_args(c.C);
         ca.stream = stream;
         ca.resample = ra0.res;
@@ -4678,6 +4865,7 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                 e.ps.out_off = k0; // (+ the stream's own offset, below)
                 e.ps.out_stride_row = t.plan.out_frames;
                 e.ps.k_base = k0;
+                e.ps.wh_off = -1; // (pv_mbatch_set_voice patches it)
                 e.q.two_pi_hop = sd.two_pi_hop;
                 e.q.hop = sd.hop;
                 e.q.do_freq_comp = sd.do_freq_comp ? 1 : 0;
@@ -4964,6 +5152,7 @@ int pv_mbatch_redraw(pv_mbatch *b, const pv_mbatch_stream *s) {
     b->groups = std::move(nb->groups);
     b->in_floats = nb->in_floats, b->out_floats = nb->out_floats, b->kernel_launches = nb->kernel_launches;
     b->pcm.resident = false; // (the next PCM run builds its job table for the new offsets)
+    b->voice_on = false;     // (every stream of the new draw is robotic: its tables say -1)
     b->tap_ran = false;      // (the planes still hold the previous draw's slices)
     b->plan_us = mb_us(t_begin, t_planned), b->host_us = mb_us(t_planned, t_host), b->device_us = mb_us(t_host, t_done);
     return PV_OK;
@@ -5070,6 +5259,72 @@ int pv_mbatch_set_formant(pv_mbatch *b, const float *formant_semitones) {
     }
     for (size_t i = 0; i < n; ++i) b->s[i].env_comp = env[i];
     b->kernel_launches = launches;
+    return PV_OK;
+}
+
+// pv_mbatch_set_voice: audiomod_pv.h.  Every run starts every stream at draw 0, so the whisper streams share ONE table
+// of phases, [slices of the longest whisper stream][C][HP], drawn here by one generator launch -- a wave per 64 rows,
+// each from the state the host's jump-ahead gives it; a run launches nothing more than before.  The resident slot tables get each entry's offset into it (its first slice
+// times C * HP, or -1), one strided copy per group, behind a device synchronisation as in pv_mbatch_set_formant.
+int pv_mbatch_set_voice(pv_mbatch *b, const int32_t *voice) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!b) return PV_ERR_INVALID_ARG;
+    int st = voice_scope_check(b->cfg);
+    if (st != PV_OK) return st;
+    const size_t n = b->s.size();
+    int64_t slices = 0;
+    for (size_t i = 0; i < n && voice; ++i) {
+        if ((st = voice_value_check(voice[i])) != PV_OK) {
+            g_last_error = "mixed batch: stream " + std::to_string(i) + ": " + g_last_error;
+            return st;
+        }
+        if (voice[i] == PV_VOICE_WHISPER) slices = std::max(slices, (int64_t)b->s[i].plan.slices.size());
+    }
+    const Core &c = b->dev->core;
+    const int64_t row = (int64_t)c.C * c.HP;
+    HIPC(hipSetDevice(b->device));
+    HIPC(hipDeviceSynchronize());
+    if (slices > 0) {
+        // The table's rows in chunks of kVoiceChunkRows, one wave each: chunk k starts k * D draws on, from a state the
+        // host makes by jump-ahead (pv_whisper.h) -- chunk by chunk, each from the one before.
+        constexpr int64_t kVoiceChunkRows = 64;
+        const int32_t per = c.d.hs + 1;
+        const int64_t rows = slices * c.C, nchunks = (rows + kVoiceChunkRows - 1) / kVoiceChunkRows;
+        std::vector<uint32_t> states((size_t)nchunks * kWhisperStatePitch, 0);
+        std::vector<WhisperJob> jobs((size_t)nchunks);
+        uint32_t poly[31];
+        whisper_jump_poly((uint64_t)kVoiceChunkRows * per, poly);
+        memcpy(states.data(), whisper_fresh_state().data(), (size_t)kWhisperHist * sizeof(uint32_t));
+        for (int64_t k = 0; k < nchunks; ++k) {
+            if (k > 0) whisper_state_jump(&states[(size_t)(k - 1) * kWhisperStatePitch], poly, &states[(size_t)k * kWhisperStatePitch]);
+            WhisperJob &wj = jobs[(size_t)k];
+            wj.src_off = k * kWhisperStatePitch, wj.dst_off = -1; // (the next run starts afresh: no state is kept)
+            wj.out_off = k * kVoiceChunkRows * c.HP;
+            wj.count = std::min(kVoiceChunkRows, rows - k * kVoiceChunkRows) * per;
+            wj.per = per, wj.pitch = c.HP;
+        }
+        if ((size_t)(slices * row) > b->d_voice.n && (st = b->d_voice.alloc((size_t)(slices * row))) != PV_OK) return st;
+        DevBuf<uint32_t> d_states;
+        DevBuf<WhisperJob> d_jobs;
+        if ((st = d_states.upload(states)) != PV_OK || (st = d_jobs.upload(jobs)) != PV_OK) return st;
+        launch_whisper(d_states.p, b->d_voice.p, d_jobs.p, (int)nchunks, PV_CENSUS_SET_MB, c.d.fft.nc, nullptr);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "voice generator launch", __LINE__);
+        HIPC(hipDeviceSynchronize()); // (a run may follow on any stream; the two buffers above go)
+    }
+    std::vector<int64_t> col;
+    for (pv_mbatch::Group &g : b->groups) {
+        col.clear();
+        const int64_t gi = &g - b->groups.data();
+        for (const int32_t i : g.stream_of)
+            col.push_back(voice && voice[(size_t)i] == PV_VOICE_WHISPER ? gi * b->Tc * row : (int64_t)-1);
+        if (!col.empty())
+            HIPC(hipMemcpy2D(b->dev->d_desc.p + g.table_off + offsetof(PoolSlot, wh_off), sizeof(PoolSlot), col.data(),
+                             sizeof(int64_t), sizeof(int64_t), col.size(), hipMemcpyHostToDevice));
+    }
+    for (size_t i = 0; i < n; ++i) b->s[i].voice = voice ? voice[i] : PV_VOICE_ROBOTIC;
+    b->voice_on = slices > 0;
     return PV_OK;
 }
 

@@ -260,7 +260,8 @@ void chain_census_enable(bool on); // clears the table either way
 // PV_CENSUS_ANALYZE (a = NC, b = split), PV_CENSUS_PHASE (a = form, b = ring depth 4 / 8 or, for the forms without a
 // ring, peaks per lane 1 / 3), PV_CENSUS_RESAMPLE_RUNG (all four sets: a = rung kResRung*, b = interpolated, c = the
 // launch asked for more than 64 KB of LDS), PV_CENSUS_ANALYSIS_KERNEL (all four sets: a = kAnaKernel*, b = NC 128 ...
-// 4096), PV_CENSUS_CEPSTRAL (all four sets: a = kCepKernel*, b = NC 128 ... 4096); -1 for a key that does not exist
+// 4096), PV_CENSUS_CEPSTRAL (all four sets: a = kCepKernel*, b = NC 128 ... 4096), PV_CENSUS_VOICE (the generator's
+// launches: a = NC 128 ... 4096); -1 for a key that does not exist
 // The forms of the phase-locked stage (PV_PHASE_FORM_* of the C ABI): match kernel + ring chain kernel; match kernel +
 // chain kernel that loads one step ahead (pv_seq_kernel<1>, or <3> with three peaks per lane); match and ring chain in
 // one launch; the single-launch stream kernel.  Set: launch_seq / launch_phase / launch_stream count under batch.
@@ -273,6 +274,12 @@ enum { kAnaKernelGeneric = 0, kAnaKernelWave = 1, kAnaKernelSplit = 2, kAnaKerne
 // role inside pv_stream_kernel; pv_slot_cepstral_wave_kernel.  The first two count under batch, the last under its set.
 enum { kCepKernelGeneric = 0, kCepKernelWave = 1, kCepKernelSlot = 2, kCepKernels = 3 };
 int64_t chain_census_count(int kind, int set, int a, int b, int c, int d);
+void census_voice(int set, int nc); // PV_CENSUS_VOICE (a = NC 128 ... 4096): one generator launch, counted by launch_whisper
+
+// The voice setting's generator (pv_whisper.hip, pv_whisper.h): one wave per job draws the job's phases from its state
+// row and leaves the row advanced.  state: rows of kWhisperStatePitch words; out: the phase buffer; jobs: device memory.
+struct WhisperJob;
+void launch_whisper(uint32_t *state, float *out, const WhisperJob *jobs, int njobs, int census_set, int nc, hipStream_t st);
 
 // pv_resample_kernel: one workgroup = 256 outputs of two rows
 struct ResTile {
@@ -360,6 +367,9 @@ struct PoolSlot {
     int64_t out_off;        // float offset of its first output (row 0) in PoolLaunch::out
     int64_t out_stride_row; // floats between its rows there
     int64_t k_base;         // output index of out_off
+    int64_t wh_off;         // the voice setting: float offset of the slot's phases [Tn][C][HP] of this launch in
+                            // SynthArgs::whisper (drawn by pv_whisper_kernel); -1: the slot stays robotic.  Read only
+                            // where the launch's SynthArgs::whisper is set
 };
 struct PoolLaunch {
     const PoolSlot *slots; // [nslots]

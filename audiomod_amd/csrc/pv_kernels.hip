@@ -3292,6 +3292,7 @@ static std::atomic<uint64_t> g_census_ana[PV_CENSUS_SETS][kCensusNc][2];
 static std::atomic<uint64_t> g_census_phase[PV_CENSUS_SETS][kPhaseForms][4];
 static std::atomic<uint64_t> g_census_akern[PV_CENSUS_SETS][kAnaKernels][6];
 static std::atomic<uint64_t> g_census_cep[PV_CENSUS_SETS][kCepKernels][6];
+static std::atomic<uint64_t> g_census_voice[PV_CENSUS_SETS][6];
 static int census_akern_nc_index(int nc) { // fft / 2 of 256 ... 8192 points
     return nc == 128 ? 0 : nc == 256 ? 1 : nc == 512 ? 2 : nc == 1024 ? 3 : nc == 2048 ? 4 : nc == 4096 ? 5 : -1;
 }
@@ -3325,6 +3326,10 @@ static void census_cepstral(int set, int kernel, int nc) {
     if (!g_census_on.load(std::memory_order_relaxed)) return;
     if (census_akern_nc_index(nc) >= 0) g_census_cep[set][kernel][census_akern_nc_index(nc)].fetch_add(1, std::memory_order_relaxed);
 }
+void census_voice(int set, int nc) { // (pv_whisper.hip launch_whisper)
+    if (!g_census_on.load(std::memory_order_relaxed)) return;
+    if (census_akern_nc_index(nc) >= 0) g_census_voice[set][census_akern_nc_index(nc)].fetch_add(1, std::memory_order_relaxed);
+}
 void chain_census_enable(bool on) {
     g_census_on.store(false, std::memory_order_relaxed);
     for (auto &a : g_census_chain) for (auto &b : a) for (auto &c : b) for (auto &d : c) for (auto &e : d) e.store(0, std::memory_order_relaxed);
@@ -3334,6 +3339,7 @@ void chain_census_enable(bool on) {
     for (auto &a : g_census_phase) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_akern) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
     for (auto &a : g_census_cep) for (auto &b : a) for (auto &c : b) c.store(0, std::memory_order_relaxed);
+    for (auto &a : g_census_voice) for (auto &b : a) b.store(0, std::memory_order_relaxed);
     g_census_on.store(on, std::memory_order_relaxed);
 }
 int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
@@ -3361,6 +3367,9 @@ int64_t chain_census_count(int kind, int set, int a, int b, int c, int d) {
     case 7: // (PV_CENSUS_CEPSTRAL; 6 is no kind)
         if (a < 0 || a >= kCepKernels || census_akern_nc_index(b) < 0) return -1;
         return (int64_t)g_census_cep[set][a][census_akern_nc_index(b)].load(std::memory_order_relaxed);
+    case 8: // (PV_CENSUS_VOICE)
+        if (census_akern_nc_index(a) < 0) return -1;
+        return (int64_t)g_census_voice[set][census_akern_nc_index(a)].load(std::memory_order_relaxed);
     default: return -1;
     }
 }
@@ -4481,6 +4490,10 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     if (sv.npk) sv.npk += r * s.TR;
     if (sv.modes) sv.modes += r * s.TR;
     if (sv.rot) sv.rot += r * s.TR * s.PKP;
+    if constexpr (kPlainCore < 0) { // the voice setting: a whisper slot of a ROBOTIC object reads its drawn phases
+        sv.whisper = (s.whisper && ps.wh_off >= 0) ? s.whisper + ps.wh_off : nullptr;
+        if (sv.whisper) sv.robotic = 0;
+    }
     ChainArgs cv = c;
     cv.Tn = ps.Tn;
     cv.t0 = ps.t0;
@@ -4723,6 +4736,10 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     if (sv.npk) sv.npk += r * s.TR;
     if (sv.modes) sv.modes += r * s.TR;
     if (sv.rot) sv.rot += r * s.TR * s.PKP;
+    if constexpr (kPlainCore < 0) { // the voice setting: a whisper slot of a ROBOTIC object reads its drawn phases
+        sv.whisper = (s.whisper && ps.wh_off >= 0) ? s.whisper + ps.wh_off : nullptr;
+        if (sv.whisper) sv.robotic = 0;
+    }
     ChainArgs cv = c;
     cv.Tn = ps.Tn;
     cv.t0 = ps.t0;
@@ -4961,6 +4978,10 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     if (sv.npk) sv.npk += r * s.TR;
     if (sv.modes) sv.modes += r * s.TR;
     if (sv.rot) sv.rot += r * s.TR * s.PKP;
+    if constexpr (kPlainCore < 0) { // the voice setting: a whisper slot of a ROBOTIC object reads its drawn phases
+        sv.whisper = (s.whisper && ps.wh_off >= 0) ? s.whisper + ps.wh_off : nullptr;
+        if (sv.whisper) sv.robotic = 0;
+    }
     ChainArgs cv = c;
     cv.Tn = ps.Tn;
     cv.t0 = ps.t0;

@@ -598,14 +598,15 @@ WhisperRng::WhisperRng() {
     for (int i = 0; i < 310; ++i) (void)next_raw();
 }
 
-uint32_t WhisperRng::next_raw() {
+uint32_t WhisperRng::next_word() {
     const uint32_t v = (uint32_t)state_[f_] + (uint32_t)state_[b_];
     state_[f_] = (int32_t)v;
-    const uint32_t out = v >> 1;
     if (++f_ >= 31) f_ = 0;
     if (++b_ >= 31) b_ = 0;
-    return out;
+    return v;
 }
+
+uint32_t WhisperRng::next_raw() { return next_word() >> 1; }
 
 float WhisperRng::next_phase() {
     const float two_pi = (float)(2 * M_PI);

@@ -180,6 +180,8 @@ class WhisperRng {
     WhisperRng();
     float next_phase();
     uint32_t next_raw();
+    uint32_t next_word(); // the full 32-bit state word of the draw (next_raw() is next_word() >> 1): the device
+                          // generator's history is made of these (pv_whisper.h)
 
   private:
     int32_t state_[31];

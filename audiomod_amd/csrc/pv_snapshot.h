@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "pv_plan.h"
+#include "pv_whisper.h"
 
 namespace pv {
 namespace snap {
@@ -29,6 +30,11 @@ static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the blob format is lit
 
 constexpr uint64_t kMagic = 0x4e534c4f4f505650ull; // "PVPOOLSN"
 constexpr uint32_t kVersion = 1;
+// A slot with the WHISPER voice (include/audiomod_pv.h "Voice setting"): the header's mode reads PV_MODE_WHISPER -- the
+// stream is that engine's -- and the directory ends with the slot's generator state row (pv_whisper.h).  Only such blobs
+// carry this version: a robotic slot's blob is version 1, byte for byte what it always was.
+constexpr uint32_t kVersionVoice = 2;
+inline uint32_t version_of(int32_t mode) { return mode == PV_MODE_WHISPER ? kVersionVoice : kVersion; }
 
 // The per-row device buffers a slot carries between calls, in payload order.  Which of them a configuration has follows
 // from its phase stage and from whether its pool keeps an overlap-add stream ring (seg_bytes).
@@ -48,6 +54,7 @@ enum Buf : int32_t {
     kBufStKind,   // kind of the carried state   [C] int32
     kBufAcc,      // accumulator images          [2][C][AR] float
     kBufStream,   // overlap-add stream ring     [C][stream_len] float
+    kBufWhisper,  // generator state row         [kWhisperStatePitch] uint32 (version 2 blobs)
     kBufCount
 };
 
@@ -113,6 +120,7 @@ inline int64_t seg_bytes(const Header &h, int buf) {
     case kBufStKind: return chain ? C * 4 : 0;
     case kBufAcc: return 2 * C * h.AR * 4;
     case kBufStream: return C * (int64_t)h.stream_len * 4;
+    case kBufWhisper: return h.mode == PV_MODE_WHISPER ? (int64_t)kWhisperStatePitch * 4 : 0;
     default: return 0;
     }
 }
@@ -141,7 +149,7 @@ inline uint64_t hash64(const uint8_t *p, size_t n) {
 // configuration and geometry fields, which the caller has set.
 inline void fill_sizes(Header &h, int32_t nlive, int64_t pending) {
     h.magic = kMagic;
-    h.version = kVersion;
+    h.version = version_of(h.mode);
     h.header_bytes = (uint32_t)sizeof(Header);
     h.nlive = nlive;
     h.pending = pending;
@@ -212,7 +220,8 @@ inline const char *validate(const void *blob, int64_t bytes, Header *out) {
     memcpy(&h, p, sizeof h);
     if (h.total_bytes != (uint64_t)bytes) return "its length differs from the one its header states (truncated?)";
     if (h.magic != kMagic) return "not a stream-pool snapshot (magic)";
-    if (h.version != kVersion) return "an unknown format version";
+    if (h.version != kVersion && h.version != kVersionVoice) return "an unknown format version";
+    if (h.version != version_of(h.mode)) return "its format version does not go with its mode";
     if (h.header_bytes != sizeof(Header)) return "header size";
     auto in = [](int64_t v, int64_t lo, int64_t hi) { return v >= lo && v <= hi; };
     if (!in(h.channels, 1, 65535) || !in(h.N, 2, 1 << 16) || h.hs != h.N / 2 || !in(h.ring, 1, 1 << 28) ||

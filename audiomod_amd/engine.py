@@ -239,6 +239,10 @@ def lib():
     L.pv_pool_set_formant.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_float]
     L.pv_pool_get_formant.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int), C.POINTER(C.c_float)]
     L.pv_mbatch_set_formant.argtypes = [C.c_void_p, C.c_void_p]
+    L.pv_pool_set_voice.argtypes = [C.c_void_p, C.c_int32, C.c_int]
+    L.pv_pool_get_voice.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
+    L.pv_mbatch_set_voice.argtypes = [C.c_void_p, C.c_void_p]
+    L.pv_debug_whisper_phases.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int]
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -485,6 +489,38 @@ def whisper_phases(n):
     """First n phases WHISPER mode draws in a fresh reference process (host only)."""
     out = np.zeros(n, np.float32)
     _check(lib().pv_plan_whisper_phases(n, out.ctypes.data), "pv_plan_whisper_phases")
+    return out
+
+
+VOICES = {"robotic": 0, "whisper": 1}  # PV_VOICE_*
+CENSUS_VOICE = 8  # PV_CENSUS_VOICE
+
+
+def _voice_value(v):
+    """a voice as the C ABI takes it: a name of VOICES, or the number itself (passed on unchecked)"""
+    return VOICES[v] if isinstance(v, str) else int(v)
+
+
+def whisper_device_phases(counts, device=0):
+    """Diagnostics: the voice setting's generator kernel alone (pv_debug_whisper_phases).  One stream from the fresh
+    state, one launch per entry of `counts` drawing that many phases, the state carried on the device between them;
+    all phases concatenated, float32.  Equals whisper_phases(sum(counts)) bit for bit."""
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    assert counts.ndim == 1
+    out = np.zeros(max(int(counts.sum()), 1), np.float32)
+    _check(lib().pv_debug_whisper_phases(counts.ctypes.data, len(counts), out.ctypes.data, device), "pv_debug_whisper_phases")
+    return out[:int(counts.sum())]
+
+
+def voice_census_read():
+    """The non-zero keys of the census' kind PV_CENSUS_VOICE, the generator's launches: {(set, nc): count}."""
+    L = lib()
+    out = {}
+    for si, name in enumerate(("batch", "pool", "pmix", "mb")):
+        for nc in (128, 256, 512, 1024, 2048, 4096):
+            n = L.pv_debug_chain_census_count(CENSUS_VOICE, si, nc, 0, 0, 0)
+            if n > 0:
+                out[(name, nc)] = n
     return out
 
 
@@ -820,6 +856,18 @@ class MixedBatch:
             _check(self.L.pv_mbatch_set_formant(self.h, v.ctypes.data), "pv_mbatch_set_formant")
         self._refresh()
 
+    def set_voice(self, voices):
+        """The voice per stream: a list of "robotic" / "whisper", or None for all robotic (pv_mbatch_set_voice; an
+        object of mode robotic).  Stream i with the whisper voice equals Batch(1, frames_i, mode="whisper", ...)."""
+        if voices is None:
+            _check(self.L.pv_mbatch_set_voice(self.h, None), "pv_mbatch_set_voice")
+        else:
+            if len(voices) != len(self.streams):
+                raise PvError("MixedBatch.set_voice: %d values for an object of %d" % (len(voices), len(self.streams)))
+            v = np.array([_voice_value(x) for x in voices], np.int32)
+            _check(self.L.pv_mbatch_set_voice(self.h, v.ctypes.data), "pv_mbatch_set_voice")
+        self._refresh()
+
     def last_build_timing(self):
         """The last creation or redraw in microseconds: dict(plan_us, host_us, device_us) -- planning, the other host
         work up to and including the uploads, the wait for the device build (0 after a creation)."""
@@ -1125,9 +1173,19 @@ class StreamPool:
     def __del__(self):
         self.close_pool()
 
-    def open(self, semitones=None, time_ratio=None):
+    def open(self, semitones=None, time_ratio=None, voice=None):
         """A fresh stream in the lowest free slot, at the given pitch / time ratio (default: the configuration's);
-        returns the slot."""
+        returns the slot.  voice: set_voice() for the new slot (a pool of mode robotic)."""
+        s = self._open(semitones, time_ratio)
+        if voice is not None:
+            try:
+                self.set_voice(s, voice)
+            except Exception:
+                self.close(s)
+                raise
+        return s
+
+    def _open(self, semitones, time_ratio):
         s = C.c_int32(-1)
         if semitones is None and time_ratio is None:
             _check(self.L.pv_pool_open(self.h, C.byref(s)), "pv_pool_open")
@@ -1273,6 +1331,16 @@ class StreamPool:
         on, v = C.c_int(0), C.c_float(0)
         _check(self.L.pv_pool_get_formant(self.h, int(slot), C.byref(on), C.byref(v)), "pv_pool_get_formant")
         return float(v.value) if on.value else None
+
+    def set_voice(self, slot, voice):
+        """The slot's voice, "robotic" or "whisper" (pv_pool_set_voice): a pool of mode robotic, a slot that has
+        processed no slice yet.  A whisper slot is from then on bit for bit a PhaseVocoder of mode whisper."""
+        _check(self.L.pv_pool_set_voice(self.h, int(slot), _voice_value(voice)), "pv_pool_set_voice")
+
+    def get_voice(self, slot):
+        v = C.c_int(0)
+        _check(self.L.pv_pool_get_voice(self.h, int(slot), C.byref(v)), "pv_pool_get_voice")
+        return {n: k for k, n in VOICES.items()}[v.value]
 
     def last_launches(self):
         """Kernels launched by the last feed() or feed_device(); 1 after a save() or restore() of any number of slots."""

@@ -191,6 +191,45 @@ int pv_pool_get_formant(const struct pv_pool *p, int32_t slot, int *on, float *f
 int pv_mbatch_set_formant(struct pv_mbatch *b, const float *formant_semitones);
 
 /* ----------------------------------------------------------------------------------------------
+ * Voice setting: the WHISPER voice as a run-time, per-stream setting of the many-stream objects of mode ROBOTIC.  The
+ * two voices share everything (hop, planner, resampling: the same derived constants) but the phase synthesis gives
+ * each bin: 0 (ROBOTIC) or 2 pi rand() / RAND_MAX (WHISPER).  A stream given the WHISPER voice is from then on, bit
+ * for bit, a pv_engine / pv_batch of one stream of mode WHISPER with the stream's pitch and time ratio: its own rand()
+ * sequence from the default seed, as in one fresh reference process.  The phases are drawn on the device by a
+ * generator kernel (glibc's rand() made parallel over a wave); a stream's generator state is 2728 bytes of device
+ * memory, whatever its age.  With the setting untouched every object launches exactly what it always launched.
+ * Scope (decided before any device call; a refused call changes nothing): objects whose cfg.mode is
+ * PV_MODE_ROBOTIC -- pv_pool_create, pv_pool_create_mixed, pv_mbatch_create; anything else PV_ERR_UNSUPPORTED
+ * (pv_last_error() says that the voice belongs to ROBOTIC objects).  An unknown voice, a slot that is not open, a NULL
+ * object: PV_ERR_INVALID_ARG.  Creating these objects with cfg.mode WHISPER stays refused.
+ *   pv_pool_set_voice   : a slot that has processed no slice yet (pv_info.slices == 0); afterwards
+ *                         PV_ERR_INVALID_ARG (a change of voice in mid-stream has no reference to be held to).  Host
+ *                         state only -- no wait while device feeds are in flight.  pv_pool_open* starts a slot robotic;
+ *                         closing and reopening a slot gives a fresh stream.  pv_pool_last_launches grows by one (the
+ *                         generator) for a feed's launch group that holds at least one whisper slot; robotic and
+ *                         whisper slots share the group's other launches
+ *   pv_pool_get_voice   : the slot's voice (NULL allowed)
+ *   pv_mbatch_set_voice : per stream, voice[nstreams]; NULL = all robotic.  Every run starts every stream at draw 0,
+ *                         so the whisper streams share one table of phases, [slices of the longest of them][channels]
+ *                         [fftsize / 2 + 8] floats, drawn by the call itself; the call synchronises the device like
+ *                         pv_mbatch_set_formant.  A run launches what it launched before: pv_mbatch_kernel_launches
+ *                         does not change.  pv_mbatch_run, _run_pcm and _run_pcm_host follow.  pv_mbatch_redraw resets
+ *                         every stream to robotic
+ * Snapshots: the blob of a whisper slot has format version 2, reports cfg.mode PV_MODE_WHISPER (pv_pool_blob_info) and
+ * carries the slot's generator state; pv_pool_restore accepts it into a ROBOTIC pool only and the slot continues as
+ * the uninterrupted WHISPER engine would.  A robotic slot's blob is version 1, byte for byte what it always was.
+ * -------------------------------------------------------------------------------------------- */
+#define PV_VOICE_ROBOTIC 0
+#define PV_VOICE_WHISPER 1
+int pv_pool_set_voice(struct pv_pool *p, int32_t slot, int voice);
+int pv_pool_get_voice(const struct pv_pool *p, int32_t slot, int *voice);
+int pv_mbatch_set_voice(struct pv_mbatch *b, const int32_t *voice);
+/* Diagnostics: the generator kernel alone.  One stream from the fresh state; `ncalls` consecutive launches drawing
+ * counts[i] phases each (0 ... 2^31 - 1), the state carried in device memory between them; the phases of all launches,
+ * concatenated, to out.  Equals pv_plan_whisper_phases(sum of counts) bit for bit. */
+int pv_debug_whisper_phases(const int64_t *counts, int32_t ncalls, float *out, int device);
+
+/* ----------------------------------------------------------------------------------------------
  * Stream pool: up to `capacity` independent LIVE streams of one configuration on one device, each
  * with the semantics of a pv_engine (same cfg, same pv_set_arithmetic setting when the pool is
  * created): fed the same blocks and retrieved between calls, a slot returns bit for bit what that
@@ -612,6 +651,9 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
  *   PV_CENSUS_CEPSTRAL : the cepstral formant stage of all four sets: a = the kernel launched (PV_CEP_KERNEL_*), b = NC
  *                        (fft size / 2: 128 ... 4096).  The batch set counts the batch path and the single-stream engine
  *                        (mode FORMANT_CEPSTRAL and the formant setting alike).  Read through the call only
+ *   PV_CENSUS_VOICE    : launches of the voice setting's generator kernel: `set` = the set it serves (pool, pmix, mb;
+ *                        pv_debug_whisper_phases counts under batch with a = 1024), a = NC (fft size / 2: 128 ... 4096);
+ *                        b, c and d are ignored.  Read through the call only
  * Process-wide and off by default (a launch then tests one flag).  pv_debug_chain_census(on) clears the counts and
  * switches counting on or off; pv_debug_chain_census_count returns a key's count, -1 for a key that does not exist.
  * If the environment variable AUDIOMOD_PV_CHAIN_CENSUS names a file when the library is loaded, the census is on from
@@ -625,6 +667,7 @@ int pv_debug_sqrt_sweep(uint32_t first_bits, uint64_t count, uint64_t *mismatche
 #define PV_CENSUS_RESAMPLE_RUNG 4
 #define PV_CENSUS_ANALYSIS_KERNEL 5
 #define PV_CENSUS_CEPSTRAL 7 /* (6 is no kind: -1 for every key, as for any other number) */
+#define PV_CENSUS_VOICE 8
 #define PV_CEP_KERNEL_GENERIC 0 /* pv_cepstral_kernel: LDS butterflies, any size */
 #define PV_CEP_KERNEL_WAVE 1    /* a slice per wave: pv_cepstral_wave_kernel (fft 2048 / 4096), or inside the stream kernel */
 #define PV_CEP_KERNEL_SLOT 2    /* pv_slot_cepstral_wave_kernel: the slot-table sets (fft 512 ... 4096) */
