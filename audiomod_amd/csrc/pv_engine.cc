@@ -1502,6 +1502,169 @@ struct pv_pool {
     }
 };
 
+// ---------------------------------------------------------------- slot tables
+// What the three slot-table forms -- stream pool, mixed pool, mixed batch -- build and launch alike.
+
+// A descriptor block as the host writes it: every array 16-byte aligned, known by its offset
+struct DescBlob {
+    std::vector<char> bytes;
+    int64_t put(const void *src, size_t n) {
+        const size_t off = (bytes.size() + 15) & ~(size_t)15;
+        bytes.resize(off + n);
+        if (n) memcpy(bytes.data() + off, src, n);
+        return (int64_t)off;
+    }
+    template <typename T> int64_t put(const std::vector<T> &v) { return put(v.data(), v.size() * sizeof(T)); }
+};
+
+// The PoolParams of a slot whose constants are `d`.  tab: the slot's entry of its table arena (a resampling slot's; the
+// sinc table first, the expanded interpolation rows tab4_off float4s on)
+static PoolParams slot_params(const Derived &d, int tab_bytes, int lds_floats, const float4 *tab, size_t tab4_off) {
+    PoolParams q{};
+    q.two_pi_hop = d.two_pi_hop;
+    q.hop = d.hop;
+    q.do_freq_comp = d.do_freq_comp ? 1 : 0;
+    q.freq_comp = d.freq_comp;
+    q.fixed_gain = d.fixed_gain;
+    if (d.resample) {
+        q.filt_len = d.filt_len;
+        q.oversample = d.oversample;
+        q.sinc_len = (int32_t)d.sinc.size();
+        q.tab_bytes = tab_bytes;
+        q.lds_floats = lds_floats;
+        q.sinc = reinterpret_cast<const float *>(tab);
+        q.tab4 = tab + tab4_off;
+    }
+    return q;
+}
+
+// ... and the image of such an entry, `stride` float4s: the rows expanded as Core::init expands them
+static void slot_tab_image(const Derived &d, size_t stride, size_t tab4_off, std::vector<float4> &img) {
+    img.assign(stride, make_float4(0, 0, 0, 0));
+    memcpy(img.data(), d.sinc.data(), d.sinc.size() * sizeof(float));
+    float4 *t4 = img.data() + tab4_off;
+    for (int off = 0; off < d.oversample && d.interp; ++off)
+        for (int j = 0; j < d.filt_len; ++j) {
+            const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
+            t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+        }
+}
+
+// Contiguous table entries of one kernel variant.  A launch group's table is sorted by variant_key; analysis and the
+// phase stage serve every slot in one launch each, the fused synthesis + overlap-add is launched once per (frequency
+// compensation, resampling, fast) present, the resampling once per (fast, interp) present within it.
+struct VariantRun {
+    int first, count;
+    int dfc, res, fast, interp;
+    int max_tiles, lds_floats, tab_bytes;
+    int max_runs; // (mixed batch: the most runs a slot of the entry splits its slices into; a pool's slots have one)
+};
+// the variant: frequency compensation, resampling, fast kernels, interpolated table (sort order)
+static int variant_key(const Derived &d, bool fast) {
+    return ((d.do_freq_comp ? 1 : 0) << 3) | ((d.resample ? 1 : 0) << 2) | ((fast ? 1 : 0) << 1) |
+           ((d.resample && d.interp) ? 1 : 0);
+}
+// entry k of a table sorted by key, folded into the table's runs (k = 0, 1, ... in turn)
+static void variant_runs_add(std::vector<VariantRun> &vr, int k, int key, int res_ntiles, int lds_floats, int tab_bytes,
+                             int runs) {
+    if (k == 0 || key != ((vr.back().dfc << 3) | (vr.back().res << 2) | (vr.back().fast << 1) | vr.back().interp))
+        vr.push_back(VariantRun{k, 0, key >> 3 & 1, key >> 2 & 1, key >> 1 & 1, key & 1, 0, 0, 0, 1});
+    VariantRun &r = vr.back();
+    ++r.count;
+    r.max_tiles = std::max(r.max_tiles, res_ntiles);
+    r.lds_floats = std::max(r.lds_floats, lds_floats);
+    r.tab_bytes = std::max(r.tab_bytes, tab_bytes);
+    r.max_runs = std::max(r.max_runs, runs);
+}
+// the entries from `a` on that share one launch of the fused kernel: consecutive, they differ in interp only
+static size_t variant_group_end(const std::vector<VariantRun> &runs, size_t a) {
+    size_t e = a + 1;
+    while (e < runs.size() && runs[e].dfc == runs[a].dfc && runs[e].res == runs[a].res && runs[e].fast == runs[a].fast) ++e;
+    return e;
+}
+
+// the end of a slot's overlap-add denominators as the chain kernel reads them: whole quads, four more entries, all 1;
+// reciprocals for the fast kernels
+static void finish_wden(std::vector<float> &wden, bool fast) {
+    wden.resize(((wden.size() + 3) & ~(size_t)3) + 4, 1.f);
+    if (fast)
+        for (float &v : wden) v = 1.0f / v;
+}
+
+// A buffer that grows on demand: `floor` elements at first, doubled until `need` fit.  The contents are not kept.
+static size_t grown_count(size_t have, size_t need, size_t floor) {
+    size_t capn = have ? have : floor;
+    while (capn < need) capn *= 2;
+    return capn;
+}
+template <typename T> static int grow(PinBuf<T> &b, size_t need, size_t floor) { return b.alloc(grown_count(b.n, need, floor)); }
+template <typename T> static int grow(DevBuf<T> &b, size_t need, size_t floor, hipStream_t st) {
+    return b.alloc_on(grown_count(b.n, need, floor), st);
+}
+
+// What a launch group says of each launch.  who: "pool" / "mixed batch", in front of a failed launch's name;
+// no_kernel: in front of the stage a launcher refuses; count: where the launches are counted, if anywhere;
+// launch = false: nothing is launched, the launchers are only asked whether the configuration fits them.
+struct LaunchCheck {
+    const char *who, *no_kernel;
+    int *count;
+    bool launch;
+    int refused(const char *stage) const {
+        g_last_error = std::string(no_kernel) + stage + " kernel for this configuration";
+        return PV_ERR_UNSUPPORTED;
+    }
+    int launched(const char *stage) const {
+        if (!launch) return PV_OK;
+        if (count) ++*count;
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? PV_OK : hip_fail(e, (std::string(who) + " " + stage + " launch").c_str(), __LINE__);
+    }
+    // accepted: what the stage's launcher returned
+    int after(bool accepted, const char *stage) const { return accepted ? launched(stage) : refused(stage); }
+};
+
+// The fused synthesis + overlap-add and the resampling of a launch group whose table `pl` is sorted by variant (`runs`).
+// Each launch takes the group's variant in place of stream 0's: whether to compensate, to resample, to take the fast
+// kernel; the compensation factor and the gain themselves are per slot (PoolParams), the block's are neutral.
+// synth(sa, ca, sub, first, max_runs) and res(ra, rs, first) launch on the entries from `first` on.
+template <typename Synth, typename Res>
+static int launch_variant_groups(const Core &c, const PoolLaunch &pl, const std::vector<VariantRun> &runs, float *stream,
+                                 const float *whisper, const LaunchCheck &lc, Synth synth, Res res) {
+    int rc;
+    for (size_t a = 0; a < runs.size();) {
+        const size_t e = variant_group_end(runs, a);
+        const VariantRun &ra0 = runs[a];
+        const int nslots = runs[e - 1].first + runs[e - 1].count - ra0.first;
+        const PoolLaunch sub{pl.slots + ra0.first, pl.desc, pl.out, nslots, pl.max_tn, pl.max_tiles};
+        int max_runs = 1;
+        for (size_t k = a; k < e; ++k) max_runs = std::max(max_runs, runs[k].max_runs);
+        SynthArgs sa = c.synth_args(c.C);
+        sa.do_freq_comp = ra0.dfc;
+        sa.freq_comp = 1;
+        sa.fixed_gain = 1;
+        if (whisper) sa.whisper = whisper;
+        ChainArgs ca = c.chain_args(c.C);
+        ca.stream = stream;
+        ca.resample = ra0.res;
+        ca.fast = ra0.fast;
+        if ((rc = lc.after(synth(sa, ca, sub, ra0.first, max_runs), "synthesis + overlap-add")) != PV_OK) return rc;
+        for (size_t k = a; k < e && ra0.res; ++k) {
+            const VariantRun &rv = runs[k];
+            if (rv.max_tiles <= 0 && lc.launch) continue; // (no output completed: nothing to launch; a probe still asks)
+            const PoolLaunch rs{pl.slots + rv.first, pl.desc, pl.out, rv.count, pl.max_tn, rv.max_tiles};
+            ResArgs ra = c.res_args(c.C); // (not the uniform part: each slot brings its own filter set-up, PoolParams)
+            ra.stream = stream;
+            ra.interp = rv.interp;
+            ra.lds_floats = rv.lds_floats; // (the largest of the entries' slots)
+            ra.tab_bytes = rv.tab_bytes;
+            ra.fast = rv.fast;
+            if ((rc = lc.after(res(ra, rs, rv.first), "resampling")) != PV_OK) return rc;
+        }
+        a = e;
+    }
+    return PV_OK;
+}
+
 extern "C" {
 
 const char *pv_strerror(int s) {
@@ -2907,15 +3070,8 @@ static int pool_tab_acquire(pv_pool *p, const Derived &d, int *out) {
         for (size_t i = 0; i < p->tabs.size() && tab < 0; ++i)
             if (p->tabs[i].refs == 0) tab = (int)i;
         // (at most one entry per open slot: a free one exists)
-        std::vector<float4> img(p->tab_stride, make_float4(0, 0, 0, 0));
-        memcpy(img.data(), d.sinc.data(), d.sinc.size() * sizeof(float));
-        float4 *t4 = img.data() + (size_t)(p->max_sinc + 3) / 4;
-        if (d.interp) // (as Core::init expands them)
-            for (int off = 0; off < d.oversample; ++off)
-                for (int j = 0; j < d.filt_len; ++j) {
-                    const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
-                    t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
-                }
+        std::vector<float4> img;
+        slot_tab_image(d, p->tab_stride, (size_t)(p->max_sinc + 3) / 4, img);
         HIPC(hipSetDevice(c.device));
         // (a free entry may still be read by the in-flight device feeds of the slot that released it)
         if (const int ds = pool_drain(p)) return ds;
@@ -3282,148 +3438,66 @@ static CepstralArgs slot_cepstral_args(const Core &c) {
     return a;
 }
 
-// the stages of one launch group for every slot in it (Core's argument builders with rows = C);
-// launch = false: launch nothing, only ask the launchers whether this configuration fits them (pv_pool_create)
+// What a pool's launch group runs once for every slot in it, whatever the slots' variants: analysis, the phase stage
+// and the formant stage (Core's argument builders with rows = C).
+// q: a mixed pool's PoolParams table, parallel to pl.slots (null: a uniform pool)
 // fx: the table of the group's slots that run the formant stage (null: none does)
+static int pool_launch_front(const pv_pool *p, const PoolLaunch &pl, const PoolParams *q, const LaunchCheck &lc,
+                             const PoolLaunch *fx) {
+    const Core &c = p->core;
+    hipStream_t st = p->stream;
+    const int cm = phase_mode(c.d);
+    int rc;
+    if (!lc.launch) return PV_OK; // (pv_pool_create's question goes to the launchers after these)
+    AnalyzeArgs aa = c.analyze_args(c.C); // (its hop is stream 0's: a mixed pool's kernel takes each slot's from PoolParams)
+    aa.ia = pool_ring_addr(p);
+    if ((rc = lc.after(q ? launch_pmix_analyze(aa, pl, q, st) : launch_pool_analyze(aa, pl, st), "analysis")) != PV_OK) return rc;
+    if (cm == 1) {
+        const MatchArgs ma = c.match_args(c.C);
+        const SeqArgs qa = c.seq_args(c.C);
+        if ((rc = lc.after(q ? launch_pmix_phase(ma, qa, pl, q, st) : launch_pool_phase(ma, qa, pl, st), "phase")) != PV_OK) return rc;
+    } else if (cm == 0) {
+        const PropArgs pa = c.prop_args(c.C);
+        if ((rc = lc.after(q ? launch_pmix_prop(pa, pl, q, st) : launch_pool_prop(pa, pl, st), "propagation")) != PV_OK) return rc;
+    }
+    if (!fx) return PV_OK;
+    return lc.after(launch_slot_cepstral(slot_cepstral_args(c), *fx, q ? PV_CENSUS_SET_PMIX : PV_CENSUS_SET_POOL, st), "formant");
+}
+
+// the stages of a uniform pool's launch group
+// launch = false: launch nothing, only ask the launchers whether this configuration fits them (pv_pool_create)
 // whisper: the phase buffer where the group holds a whisper slot (PoolSlot::wh_off), drawn by the caller's generator
 // launch; else null
 static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch, const PoolLaunch *fx,
                              const float *whisper) {
     const Core &c = p->core;
-    const Derived &d = c.d;
     hipStream_t st = p->stream;
-    const int cm = phase_mode(d);
-    auto refused = [](const char *what) {
-        g_last_error = std::string("stream pool: no per-slot ") + what + " kernel for this configuration";
-        return PV_ERR_UNSUPPORTED;
-    };
-    auto launched = [](const char *what) -> int {
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
-    };
+    const LaunchCheck lc{"pool", "stream pool: no per-slot ", nullptr, launch};
     int rc;
-    AnalyzeArgs aa = c.analyze_args(c.C);
-    aa.ia = pool_ring_addr(p);
-    if (launch && !launch_pool_analyze(aa, pl, st)) return refused("analysis");
-    if (launch && (rc = launched("pool analysis launch")) != PV_OK) return rc;
-    if (!launch) {
-    } else if (cm == 1) {
-        const MatchArgs ma = c.match_args(c.C);
-        const SeqArgs qa = c.seq_args(c.C);
-        if (!launch_pool_phase(ma, qa, pl, st)) return refused("phase");
-        if ((rc = launched("pool phase launch")) != PV_OK) return rc;
-    } else if (cm == 0) {
-        const PropArgs pa = c.prop_args(c.C);
-        if (!launch_pool_prop(pa, pl, st)) return refused("propagation");
-        if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
-    }
-    if (launch && fx) {
-        if (!launch_slot_cepstral(slot_cepstral_args(c), *fx, PV_CENSUS_SET_POOL, st)) return refused("formant");
-        if ((rc = launched("pool formant launch")) != PV_OK) return rc;
-    }
+    if ((rc = pool_launch_front(p, pl, nullptr, lc, fx)) != PV_OK) return rc;
     SynthArgs sa = c.synth_args(c.C);
     if (whisper) sa.whisper = whisper;
     const ChainArgs ca = c.chain_args(c.C);
-    if (!launch_pool_synth_chain(sa, ca, pl, st, launch)) return refused("synthesis + overlap-add");
-    if (launch && (rc = launched("pool synthesis + overlap-add launch")) != PV_OK) return rc;
-    if (d.resample) {
-        const ResArgs ra = c.res_args_uniform(c.C);
-        if (!launch_pool_resample(ra, pl, st, launch)) return refused("resampling");
-        if (launch && (rc = launched("pool resampling launch")) != PV_OK) return rc;
-    }
-    return PV_OK;
+    if ((rc = lc.after(launch_pool_synth_chain(sa, ca, pl, st, launch), "synthesis + overlap-add")) != PV_OK) return rc;
+    if (!c.d.resample) return PV_OK;
+    return lc.after(launch_pool_resample(c.res_args_uniform(c.C), pl, st, launch), "resampling");
 }
 
-// A mixed pool's launch group: the slots of the table are ordered by kernel variant (VariantRun: contiguous entries of
-// one variant).  Analysis and the phase stage serve every slot in one launch each; the fused synthesis + overlap-add
-// is launched once per (frequency compensation, resampling, fast) present, the resampling once per (fast, interp)
-// present within it.  Returns the number of kernels launched in *nlaunch.
-struct VariantRun {
-    int first, count;
-    int dfc, res, fast, interp;
-    int max_tiles, lds_floats, tab_bytes;
-    int max_runs; // (mixed batch: the most runs a slot of the entry splits its slices into; a pool's slots have one)
-};
-// the entries from `a` on that share one launch of the fused kernel: consecutive, they differ in interp only
-static size_t variant_group_end(const std::vector<VariantRun> &runs, size_t a) {
-    size_t e = a + 1;
-    while (e < runs.size() && runs[e].dfc == runs[a].dfc && runs[e].res == runs[a].res && runs[e].fast == runs[a].fast) ++e;
-    return e;
-}
+// A mixed pool's launch group: the slots of the table are ordered by kernel variant (`runs`), each with its entry of
+// the PoolParams table `q`.  Counts the kernels it launches in *nlaunch.
 static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const PoolParams *q,
                                  const std::vector<VariantRun> &runs, int *nlaunch, const PoolLaunch *fx,
                                  const float *whisper) {
     const Core &c = p->core;
-    const Derived &d = c.d; // (only what every slot shares: sizes, mode, coremode)
     hipStream_t st = p->stream;
-    const int cm = phase_mode(d);
-    auto refused = [](const char *what) {
-        g_last_error = std::string("stream pool: no per-slot ") + what + " kernel for this configuration";
-        return PV_ERR_UNSUPPORTED;
-    };
-    auto launched = [nlaunch](const char *what) -> int {
-        ++*nlaunch;
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
-    };
-    int rc;
-    AnalyzeArgs aa = c.analyze_args(c.C); // (its hop is stream 0's: the kernel takes each slot's from PoolParams)
-    aa.ia = pool_ring_addr(p);
-    if (!launch_pmix_analyze(aa, pl, q, st)) return refused("analysis");
-    if ((rc = launched("pool analysis launch")) != PV_OK) return rc;
-    if (cm == 1) {
-        const MatchArgs ma = c.match_args(c.C);
-        const SeqArgs qa = c.seq_args(c.C);
-        if (!launch_pmix_phase(ma, qa, pl, q, st)) return refused("phase");
-        if ((rc = launched("pool phase launch")) != PV_OK) return rc;
-    } else if (cm == 0) {
-        const PropArgs pa = c.prop_args(c.C);
-        if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
-        if ((rc = launched("pool propagation launch")) != PV_OK) return rc;
-    }
-    if (fx) { // (one launch for every variant: the stage does not depend on it)
-        if (!launch_slot_cepstral(slot_cepstral_args(c), *fx, PV_CENSUS_SET_PMIX, st)) return refused("formant");
-        if ((rc = launched("pool formant launch")) != PV_OK) return rc;
-    }
-    float *stream = c.stream.p ? c.stream.p : p->mix_stream.p;
-    for (size_t a = 0; a < runs.size();) {
-        const size_t b = variant_group_end(runs, a);
-        const VariantRun &ra0 = runs[a];
-        PoolLaunch sub = pl;
-        sub.slots = pl.slots + ra0.first;
-        sub.nslots = runs[b - 1].first + runs[b - 1].count - ra0.first;
-        // the group's variant in place of stream 0's: whether to compensate, to resample, to take the fast kernel;
-        // the compensation factor and the gain themselves are per slot (PoolParams), the block's are neutral
-        SynthArgs sa = c.synth_args(c.C);
-        sa.do_freq_comp = ra0.dfc;
-        sa.freq_comp = 1;
-        sa.fixed_gain = 1;
-        if (whisper) sa.whisper = whisper;
-        ChainArgs ca = c.chain_args(c.C);
-        ca.stream = stream;
-        ca.resample = ra0.res;
-        ca.fast = ra0.fast;
-        if (!launch_pmix_synth_chain(sa, ca, sub, q + ra0.first, st)) return refused("synthesis + overlap-add");
-        if ((rc = launched("pool synthesis + overlap-add launch")) != PV_OK) return rc;
-        for (size_t k = a; k < b && ra0.res; ++k) {
-            const VariantRun &rv = runs[k];
-            if (rv.max_tiles <= 0) continue; // (dropped slices only: no output completed)
-            PoolLaunch rs = pl;
-            rs.slots = pl.slots + rv.first;
-            rs.nslots = rv.count;
-            rs.max_tiles = rv.max_tiles;
-            ResArgs ra = c.res_args(c.C); // (not the uniform part: each slot brings its own filter set-up, PoolParams)
-            ra.stream = stream;
-            ra.interp = rv.interp;
-            ra.lds_floats = rv.lds_floats; // (the largest of the run's slots)
-            ra.tab_bytes = rv.tab_bytes;
-            ra.fast = rv.fast;
-            if (!launch_pmix_resample(ra, rs, q + rv.first, st)) return refused("resampling");
-            if ((rc = launched("pool resampling launch")) != PV_OK) return rc;
-        }
-        a = b;
-    }
-    return PV_OK;
+    const LaunchCheck lc{"pool", "stream pool: no per-slot ", nlaunch, true};
+    if (const int rc = pool_launch_front(p, pl, q, lc, fx)) return rc;
+    return launch_variant_groups(
+        c, pl, runs, c.stream.p ? c.stream.p : p->mix_stream.p, whisper, lc,
+        [&](const SynthArgs &sa, const ChainArgs &ca, const PoolLaunch &sub, int first, int) {
+            return launch_pmix_synth_chain(sa, ca, sub, q + first, st);
+        },
+        [&](const ResArgs &ra, const PoolLaunch &rs, int first) { return launch_pmix_resample(ra, rs, q + first, st); });
 }
 
 // What the two entry points of a feed differ in (pv_pool_feed: host pointers in, the slots' host FIFOs out, the pool's
@@ -3440,328 +3514,328 @@ struct PoolCall {
     int32_t *out_frames = nullptr; // [count]: what the call delivers per slot
 };
 
-static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int32_t *n, const PoolCall &io) {
-    const float *const *in = io.in;
-    g_last_error.clear();
-    plan_reason_clear();
-    if (!p || count < 0 || (count > 0 && (!slots || !n || (io.device && !io.out_frames)))) return PV_ERR_INVALID_ARG;
+// One call of pool_feed: its arguments, and what each phase leaves for the ones after it.
+struct PoolFeed {
+    pv_pool *p;
+    int32_t count;
+    const int32_t *slots, *n;
+    const PoolCall &io;
+    std::chrono::steady_clock::time_point t_call;
+    std::vector<std::vector<SliceRec>> fresh; // plan: the slices each entry's samples complete
+    pv_pool::DescBlock *blk = nullptr;        // take_block
+    // place: where the call's new samples are read and its output is written
+    bool to_caller = false; // the kernels write the caller's rows themselves
+    std::vector<int64_t> stage_off, out_base, out_cnt, k0, call_base;
+    size_t stage_total = 0, out_total = 0;
+    int groups = 0;
+    const void *ingest_src = nullptr;
+    float *launch_out = nullptr;
+    // describe: the descriptors of every group, one block
+    struct Group {
+        int64_t table_off = 0, ingest_off = 0;
+        int nslots = 0, ningest = 0, max_tn = 0, max_tiles = 0, max_in = 0;
+        int64_t fx_off = 0; // the entries of the slots that run the formant stage, once more: that launch's table
+        int fx_nslots = 0, fx_max_tn = 0;
+        int64_t wj_off = 0; // the generator's jobs: one per whisper slot of the group
+        int nwj = 0;
+        int64_t params_off = 0;     // mixed pool: the group's PoolParams table (parallel to the PoolSlot table)
+        std::vector<VariantRun> vr; // ... and its variant runs
+    };
+    std::vector<Group> grp; // (+ the final ingest of what the call leaves unconsumed)
+    bool any_whisper = false;
+    int64_t egress_off = 0; // int16 output: what the egress kernel converts, per entry
+    int negress = 0, max_egress = 0;
+    DescBlob blob;
+    std::vector<PoolIngest> ingest; // the group being described: its ingest list and generator jobs
+    std::vector<WhisperJob> wjobs;
+    std::vector<int32_t> pinc, ro; // pool_describe_slot's scratch
+    std::vector<float> wden, wden_hi;
+    std::vector<ChainSlice> cs;
+    std::vector<ResTile> res_tiles;
+    std::vector<uint2> res_otab;
+    pv_pool::Slot &slot(int32_t i) const { return p->slots[(size_t)slots[i]]; }
+};
+
+// 1. the arguments
+static int pool_feed_check(const PoolFeed &f) {
+    const pv_pool *p = f.p;
+    const PoolCall &io = f.io;
+    if (!p || f.count < 0 || (f.count > 0 && (!f.slots || !f.n || (io.device && !io.out_frames)))) return PV_ERR_INVALID_ARG;
     if (p->poisoned) {
         g_last_error = "pool unusable after an earlier failure: " + p->poison_reason;
         return p->poisoned;
     }
-    Core &c = p->core;
-    const int C = c.C;
-    {
-        std::vector<char> seen((size_t)p->cap, 0);
-        for (int32_t i = 0; i < count; ++i) {
-            const int32_t s = slots[i];
-            const char *bad = !pool_slot_ok(p, s) ? "is not open" : seen[(size_t)s] ? "is listed twice" : n[i] < 0 ? "has a negative size" : nullptr;
-            if (!bad && io.device) {
-                const pv_pool::Slot &sl = p->slots[(size_t)s];
-                if (!sl.outq.empty() && sl.outq[0].size() > sl.outq_head)
-                    bad = "still holds output of pv_pool_feed: retrieve it first";
-                else if (n[i] > io.in_pitch) bad = "has more frames than the input pitch";
-                else if (n[i] > 0 && !io.d_in) bad = "has no input";
-            } else if (!bad && n[i] > 0) {
-                if (!in) bad = "has no input";
-                else
-                    for (int ch = 0; ch < C && !bad; ++ch)
-                        if (!in[(size_t)i * C + ch]) bad = "has no input";
-            }
-            if (bad) {
-                g_last_error = "stream pool: slot " + std::to_string(s) + " " + bad;
-                return PV_ERR_INVALID_ARG;
-            }
-            seen[(size_t)s] = 1;
+    const int C = p->core.C;
+    std::vector<char> seen((size_t)p->cap, 0);
+    for (int32_t i = 0; i < f.count; ++i) {
+        const int32_t s = f.slots[i], n = f.n[i];
+        const char *bad = !pool_slot_ok(p, s) ? "is not open" : seen[(size_t)s] ? "is listed twice" : n < 0 ? "has a negative size" : nullptr;
+        if (!bad && io.device) {
+            const pv_pool::Slot &sl = p->slots[(size_t)s];
+            if (!sl.outq.empty() && sl.outq[0].size() > sl.outq_head)
+                bad = "still holds output of pv_pool_feed: retrieve it first";
+            else if (n > io.in_pitch) bad = "has more frames than the input pitch";
+            else if (n > 0 && !io.d_in) bad = "has no input";
+        } else if (!bad && n > 0) {
+            if (!io.in) bad = "has no input";
+            else
+                for (int ch = 0; ch < C && !bad; ++ch)
+                    if (!io.in[(size_t)i * C + ch]) bad = "has no input";
         }
+        if (bad) {
+            g_last_error = "stream pool: slot " + std::to_string(s) + " " + bad;
+            return PV_ERR_INVALID_ARG;
+        }
+        seen[(size_t)s] = 1;
     }
-    p->last_launches = 0;
-    if (count == 0) return PV_OK;
-    const auto t_call = std::chrono::steady_clock::now();
-    // 1. plan every slot; all or nothing
-    std::vector<std::vector<SliceRec>> fresh((size_t)count);
-    {
-        std::vector<Planner::State> before((size_t)count);
-        auto undo = [&](int32_t upto) {
-            for (int32_t j = 0; j <= upto; ++j) p->slots[(size_t)slots[j]].planner->restore(before[(size_t)j]);
-        };
-        for (int32_t i = 0; i < count; ++i) {
-            Planner &pl = *p->slots[(size_t)slots[i]].planner;
-            before[(size_t)i] = pl.save();
-            const int st = pl.feed(n[i], fresh[(size_t)i]);
-            if (st != PV_OK) {
-                undo(i);
-                g_last_error = "stream pool: slot " + std::to_string(slots[i]) + ": " +
-                               (g_last_error.empty() ? std::string(plan_reason()) : g_last_error);
-                return st;
-            }
-        }
-        // the device feed delivers everything the call makes available (nothing was pending before it: checked above);
-        // the retrieve is booked now, the samples follow in stream order
-        // (every count is checked before the first is written: a refusal leaves the caller's array as it was)
-        for (int32_t i = 0; i < count && io.device; ++i) {
-            const int32_t got = p->slots[(size_t)slots[i]].planner->available();
-            if (got > io.out_pitch || (got > 0 && !io.d_out)) {
-                undo(count - 1);
-                g_last_error = "stream pool: slot " + std::to_string(slots[i]) +
-                               (got > io.out_pitch ? " returns " + std::to_string(got) + " frames, more than the output pitch"
-                                                   : std::string(" has no output buffer"));
-                return PV_ERR_INVALID_ARG;
-            }
-        }
-        for (int32_t i = 0; i < count && io.device; ++i) {
-            Planner &pl = *p->slots[(size_t)slots[i]].planner;
-            io.out_frames[i] = pl.retrieve(pl.available());
-        }
-    }
-    // from here on device state and host bookkeeping move together; a failure poisons the pool
-    auto fail = [&](int code) {
-        p->poisoned = code;
-        p->poison_reason = g_last_error.empty() ? pv_strerror(code) : g_last_error;
-        return code;
+    return PV_OK;
+}
+
+// 2. plan every slot; all or nothing: a refusal puts every planner back and leaves the caller's out_frames as it was
+static int pool_feed_plan(PoolFeed &f) {
+    const PoolCall &io = f.io;
+    const int32_t count = f.count;
+    f.fresh.resize((size_t)count);
+    std::vector<Planner::State> before((size_t)count);
+    auto undo = [&](int32_t upto) {
+        for (int32_t j = 0; j <= upto; ++j) f.slot(j).planner->restore(before[(size_t)j]);
     };
-    {
-        const hipError_t e = hipSetDevice(c.device);
-        if (e != hipSuccess) return fail(hip_fail(e, "hipSetDevice", __LINE__));
-    }
-    int st;
-    // The call's descriptor block.  pv_pool_feed: its own, after every device feed in flight has finished (their
-    // output and any late error of theirs come first).  pv_pool_feed_device: the ring's next, once the call that used
-    // it last has finished.
-    pv_pool::DescBlock *blk = &p->sync_desc;
-    if (!io.device) {
-        if ((st = pool_drain(p)) != PV_OK) return st;
-    } else {
-        if (!p->ring_ready) { // (everything a device feed allocates in the common case, at the first one)
-            for (pv_pool::DescBlock &b : p->ring_desc) {
-                if ((st = b.h.alloc(256 * 1024)) != PV_OK || (st = b.d.alloc_on(256 * 1024, p->stream)) != PV_OK) return fail(st);
-                hipError_t e = hipEventCreateWithFlags(&b.entry, hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&b.done, hipEventDisableTiming);
-                if (e != hipSuccess) return fail(hip_fail(e, "descriptor ring events", __LINE__));
-            }
-            p->ring_ready = true;
-        }
-        blk = &p->ring_desc[p->ring_next];
-        p->ring_next = (p->ring_next + 1) % kPoolDescRing;
-        if (blk->busy) {
-            blk->busy = false;
-            const hipError_t e = hipEventSynchronize(blk->done);
-            if (e != hipSuccess) return fail(hip_fail(e, "stream pool device feed", __LINE__));
-        }
-    }
-    // 2. where the call's new samples are read and its output is written.  pv_pool_feed: the samples packed
-    // [slot][C][n] into the staging buffer (one copy), the output packed [slot][C][cnt] in the mapped host arena.
-    // pv_pool_feed_device: the caller's buffers as they are (int16 output: packed in a device arena, converted after
-    // the launches).
-    const bool to_caller = io.device && io.wire == PV_WIRE_F32; // the kernels write the caller's rows themselves
-    std::vector<int64_t> stage_off((size_t)count), out_base((size_t)count), out_cnt((size_t)count), k0((size_t)count);
-    std::vector<int64_t> call_base((size_t)count);
-    size_t stage_total = 0, out_total = 0;
-    int groups = 0;
     for (int32_t i = 0; i < count; ++i) {
-        stage_off[(size_t)i] = io.device ? (int64_t)i * C * io.in_pitch : (int64_t)stage_total;
-        stage_total += (size_t)C * n[i];
-        const std::vector<SliceRec> &f = fresh[(size_t)i];
-        out_base[(size_t)i] = to_caller ? (int64_t)i * C * io.out_pitch : (int64_t)out_total;
-        out_cnt[(size_t)i] = f.empty() ? 0 : f.back().K0 + f.back().cnt - f.front().K0;
-        k0[(size_t)i] = f.empty() ? 0 : f.front().K0;
-        out_total += (size_t)C * out_cnt[(size_t)i];
-        const int g = (int)((f.size() + kStreamChunk - 1) / kStreamChunk);
-        if (g > groups) groups = g;
-        call_base[(size_t)i] = p->slots[(size_t)slots[i]].fed;
+        Planner &pl = *f.slot(i).planner;
+        before[(size_t)i] = pl.save();
+        const int st = pl.feed(f.n[i], f.fresh[(size_t)i]);
+        if (st != PV_OK) {
+            undo(i);
+            g_last_error = "stream pool: slot " + std::to_string(f.slots[i]) + ": " +
+                           (g_last_error.empty() ? std::string(plan_reason()) : g_last_error);
+            return st;
+        }
     }
-    const void *ingest_src = io.d_in;
-    float *launch_out = static_cast<float *>(io.d_out);
+    // the device feed delivers everything the call makes available (nothing was pending before it: checked above);
+    // the retrieve is booked now, the samples follow in stream order
+    // (every count is checked before the first is written)
+    for (int32_t i = 0; i < count && io.device; ++i) {
+        const int32_t got = f.slot(i).planner->available();
+        if (got > io.out_pitch || (got > 0 && !io.d_out)) {
+            undo(count - 1);
+            g_last_error = "stream pool: slot " + std::to_string(f.slots[i]) +
+                           (got > io.out_pitch ? " returns " + std::to_string(got) + " frames, more than the output pitch"
+                                               : std::string(" has no output buffer"));
+            return PV_ERR_INVALID_ARG;
+        }
+    }
+    for (int32_t i = 0; i < count && io.device; ++i) {
+        Planner &pl = *f.slot(i).planner;
+        io.out_frames[i] = pl.retrieve(pl.available());
+    }
+    return PV_OK;
+}
+
+// 3. the call's descriptor block.  pv_pool_feed: its own, after every device feed in flight has finished (their
+// output and any late error of theirs come first).  pv_pool_feed_device: the ring's next, once the call that used
+// it last has finished.
+static int pool_feed_take_block(PoolFeed &f) {
+    pv_pool *p = f.p;
+    int st;
+    f.blk = &p->sync_desc;
+    if (!f.io.device) return pool_drain(p);
+    if (!p->ring_ready) { // (everything a device feed allocates in the common case, at the first one)
+        for (pv_pool::DescBlock &b : p->ring_desc) {
+            if ((st = b.h.alloc(256 * 1024)) != PV_OK || (st = b.d.alloc_on(256 * 1024, p->stream)) != PV_OK) return st;
+            hipError_t e = hipEventCreateWithFlags(&b.entry, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&b.done, hipEventDisableTiming);
+            if (e != hipSuccess) return hip_fail(e, "descriptor ring events", __LINE__);
+        }
+        p->ring_ready = true;
+    }
+    f.blk = &p->ring_desc[p->ring_next];
+    p->ring_next = (p->ring_next + 1) % kPoolDescRing;
+    if (f.blk->busy) {
+        f.blk->busy = false;
+        const hipError_t e = hipEventSynchronize(f.blk->done);
+        if (e != hipSuccess) return hip_fail(e, "stream pool device feed", __LINE__);
+    }
+    return PV_OK;
+}
+
+// 4. where the call's new samples are read and its output is written.  pv_pool_feed: the samples packed
+// [slot][C][n] into the staging buffer (one copy), the output packed [slot][C][cnt] in the mapped host arena.
+// pv_pool_feed_device: the caller's buffers as they are (int16 output: packed in a device arena, converted after
+// the launches).
+static int pool_feed_place(PoolFeed &f) {
+    pv_pool *p = f.p;
+    const PoolCall &io = f.io;
+    const int32_t count = f.count;
+    const int C = p->core.C;
+    int st;
+    f.to_caller = io.device && io.wire == PV_WIRE_F32;
+    for (std::vector<int64_t> *v : {&f.stage_off, &f.out_base, &f.out_cnt, &f.k0, &f.call_base}) v->resize((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        f.stage_off[(size_t)i] = io.device ? (int64_t)i * C * io.in_pitch : (int64_t)f.stage_total;
+        f.stage_total += (size_t)C * f.n[i];
+        const std::vector<SliceRec> &fr = f.fresh[(size_t)i];
+        f.out_base[(size_t)i] = f.to_caller ? (int64_t)i * C * io.out_pitch : (int64_t)f.out_total;
+        f.out_cnt[(size_t)i] = fr.empty() ? 0 : fr.back().K0 + fr.back().cnt - fr.front().K0;
+        f.k0[(size_t)i] = fr.empty() ? 0 : fr.front().K0;
+        f.out_total += (size_t)C * f.out_cnt[(size_t)i];
+        f.groups = std::max(f.groups, (int)((fr.size() + kStreamChunk - 1) / kStreamChunk));
+        f.call_base[(size_t)i] = f.slot(i).fed;
+    }
+    f.ingest_src = io.d_in;
+    f.launch_out = static_cast<float *>(io.d_out);
     if (io.device) {
-        if (!to_caller) {
-            if (out_total > p->d_arena.n) {
-                size_t capn = p->d_arena.n ? p->d_arena.n : 1 << 16;
-                while (capn < out_total) capn *= 2;
-                // (the calls in flight still use the old arena)
-                const hipError_t e = hipStreamSynchronize(p->stream);
-                if (e != hipSuccess) return fail(hip_fail(e, "stream pool device feed", __LINE__));
-                if ((st = p->d_arena.alloc_on(capn, p->stream)) != PV_OK) return fail(st);
-            }
-            launch_out = p->d_arena.p;
+        if (f.to_caller) return PV_OK;
+        if (f.out_total > p->d_arena.n) {
+            // (the calls in flight still use the old arena)
+            const hipError_t e = hipStreamSynchronize(p->stream);
+            if (e != hipSuccess) return hip_fail(e, "stream pool device feed", __LINE__);
+            if ((st = grow(p->d_arena, f.out_total, 1 << 16, p->stream)) != PV_OK) return st;
         }
-    } else {
-        if (stage_total > p->h_stage.n) {
-            size_t capn = p->h_stage.n ? p->h_stage.n : 1 << 16;
-            while (capn < stage_total) capn *= 2;
-            if ((st = p->h_stage.alloc(capn)) != PV_OK) return fail(st);
-#ifdef PV_POOL_MAPPED_INGEST // (measurement build: the ingest kernel reads the page-locked staging over the bus)
-            void *sp = nullptr;
-            const hipError_t e = hipHostGetDevicePointer(&sp, p->h_stage.p, 0);
-            if (e != hipSuccess) return fail(hip_fail(e, "staging mapping", __LINE__));
-            p->stage_src = static_cast<float *>(sp);
-#else
-            if ((st = p->d_stage.alloc_on(capn, p->stream)) != PV_OK) return fail(st);
-            p->stage_src = p->d_stage.p;
-#endif
-        }
-        for (int32_t i = 0; i < count; ++i)
-            for (int ch = 0; ch < C; ++ch)
-                if (n[i] > 0)
-                    memcpy(p->h_stage.p + stage_off[(size_t)i] + (size_t)ch * n[i], in[(size_t)i * C + ch], (size_t)n[i] * sizeof(float));
-        if (out_total > p->h_out.n) {
-            size_t capn = p->h_out.n ? p->h_out.n : 1 << 16;
-            while (capn < out_total) capn *= 2;
-            if ((st = p->h_out.alloc(capn)) != PV_OK) return fail(st);
-            void *op = nullptr;
-            const hipError_t e = hipHostGetDevicePointer(&op, p->h_out.p, 0);
-            if (e != hipSuccess) return fail(hip_fail(e, "output arena mapping", __LINE__));
-            p->out_dev = static_cast<float *>(op);
-        }
-        ingest_src = p->stage_src;
-        launch_out = p->out_dev;
+        f.launch_out = p->d_arena.p;
+        return PV_OK;
     }
-    // 3. descriptors of every group, one block: per group its PoolSlot table and ingest list, per slot its phase
-    // increments, run list, run offsets, denominators and resampling tiles
-    std::vector<char> blob;
-    auto put = [&](const void *src, size_t bytes) -> int64_t {
-        const size_t off = (blob.size() + 15) & ~(size_t)15;
-        blob.resize(off + bytes);
-        if (bytes) memcpy(blob.data() + off, src, bytes);
-        return (int64_t)off;
-    };
-    struct Group {
-        int64_t table_off, ingest_off;
-        int nslots, ningest, max_tn, max_tiles, max_in;
-        int64_t fx_off; // the entries of the slots that run the formant stage, once more: that launch's table
-        int fx_nslots, fx_max_tn;
-        int64_t wj_off; // the generator's jobs: one per whisper slot of the group
-        int nwj;
-    };
-    std::vector<Group> grp((size_t)groups + 1); // (+ the final ingest of what the call leaves unconsumed)
+    if (f.stage_total > p->h_stage.n) {
+        if ((st = grow(p->h_stage, f.stage_total, 1 << 16)) != PV_OK) return st;
+#ifdef PV_POOL_MAPPED_INGEST // (measurement build: the ingest kernel reads the page-locked staging over the bus)
+        void *sp = nullptr;
+        const hipError_t e = hipHostGetDevicePointer(&sp, p->h_stage.p, 0);
+        if (e != hipSuccess) return hip_fail(e, "staging mapping", __LINE__);
+        p->stage_src = static_cast<float *>(sp);
+#else
+        if ((st = p->d_stage.alloc_on(p->h_stage.n, p->stream)) != PV_OK) return st;
+        p->stage_src = p->d_stage.p;
+#endif
+    }
+    for (int32_t i = 0; i < count; ++i)
+        for (int ch = 0; ch < C; ++ch)
+            if (f.n[i] > 0)
+                memcpy(p->h_stage.p + f.stage_off[(size_t)i] + (size_t)ch * f.n[i], io.in[(size_t)i * C + ch],
+                       (size_t)f.n[i] * sizeof(float));
+    if (f.out_total > p->h_out.n) {
+        if ((st = grow(p->h_out, f.out_total, 1 << 16)) != PV_OK) return st;
+        void *op = nullptr;
+        const hipError_t e = hipHostGetDevicePointer(&op, p->h_out.p, 0);
+        if (e != hipSuccess) return hip_fail(e, "output arena mapping", __LINE__);
+        p->out_dev = static_cast<float *>(op);
+    }
+    f.ingest_src = p->stage_src;
+    f.launch_out = p->out_dev;
+    return PV_OK;
+}
+
+// entry i's samples up to `upto`, where the slot's ring does not hold them yet, onto the group's ingest list
+static void pool_feed_ingest(PoolFeed &f, int32_t i, int64_t upto, PoolFeed::Group &g) {
+    pv_pool::Slot &sl = f.slot(i);
+    if (upto <= sl.uploaded) return;
+    PoolIngest e{};
+    e.src_off = f.stage_off[(size_t)i] + (sl.uploaded - f.call_base[(size_t)i]);
+    e.src_pitch = f.io.device ? f.io.in_pitch : f.n[i];
+    e.pos = sl.uploaded;
+    e.n = (int32_t)(upto - sl.uploaded);
+    e.row0 = f.slots[i] * f.p->core.C;
+    f.ingest.push_back(e);
+    if (e.n > g.max_in) g.max_in = e.n;
+    sl.uploaded = upto;
+}
+
+// The PoolSlot of entry i for its fresh slices [ta, tb), one launch: its phase increments, run list, run offsets,
+// denominators and resampling tiles go into the blob, its generator job, where the slot whispers, onto f.wjobs;
+// env_comp is set where the slot runs the formant stage
+static PoolSlot pool_describe_slot(PoolFeed &f, int32_t i, int ta, int tb) {
+    const pv_pool *p = f.p;
+    const Core &c = p->core;
+    const int C = c.C, Tn = tb - ta;
+    const int32_t s = f.slots[i];
+    const std::vector<SliceRec> &fr = f.fresh[(size_t)i];
+    pv_pool::Slot &sl = f.slot(i);
+    const Derived &sd = *sl.d;
+    const int64_t t0 = sl.slices + ta;
+    PoolSlot ps{};
+    ps.t0 = t0;
+    ps.s0 = (int32_t)(t0 % c.TR);
+    ps.Tn = Tn;
+    ps.row0 = s * C;
+    ps.acc_sel = sl.acc_half | (t0 == 0 ? 2 : 0);
+    sl.acc_half ^= 1;
+    f.pinc.clear();
+    for (int t = ta; t < tb; ++t) f.pinc.push_back(fr[(size_t)t].phase_inc);
+    ps.pinc_off = f.blob.put(f.pinc);
+    f.wden.clear(), f.wden_hi.clear(), f.cs.clear(), f.ro.clear();
+    const int64_t ka = fr[(size_t)ta].K0, kb = fr[(size_t)tb - 1].K0 + fr[(size_t)tb - 1].cnt;
+    sl.chain->begin_launch(fr[(size_t)ta]);
+    for (int t = ta; t < tb; ++t) sl.chain->add(fr[(size_t)t], INT64_MAX, f.wden, f.wden_hi);
+    sl.chain->end_launch(1, f.cs, f.ro); // (one run)
+    finish_wden(f.wden, sl.fast);
+    ps.cs_off = f.blob.put(f.cs);
+    const int32_t ro4[4] = {0, (int32_t)f.cs.size(), 0, 0};
+    ps.ro_off = f.blob.put(ro4, sizeof ro4);
+    ps.wden_off = f.blob.put(f.wden);
+    f.res_tiles.clear(), f.res_otab.clear();
+    if (sd.resample && kb > ka) build_res_tiles_of(sd, ka, kb, f.res_tiles, f.res_otab);
+    ps.res_ntiles = (int32_t)f.res_tiles.size();
+    ps.res_off = f.blob.put(f.res_tiles);
+    ps.otab_off = f.blob.put(f.res_otab);
+    ps.out_off = f.out_base[(size_t)i] + (ka - f.k0[(size_t)i]);
+    ps.out_stride_row = f.to_caller ? f.io.out_pitch : f.out_cnt[(size_t)i];
+    ps.k_base = ka;
+    ps.wh_off = -1;
+    if (sl.voice == PV_VOICE_WHISPER) {
+        // the slot's draws of this launch, in the reference's order: slice-major, channel, bins 0 .. hs.  A
+        // stream's first launch starts from the pool's fresh state, every later one from the slot's own row
+        WhisperJob wj{};
+        wj.src_off = (int64_t)(t0 == 0 ? p->cap : s) * kWhisperStatePitch;
+        wj.dst_off = (int64_t)s * kWhisperStatePitch;
+        wj.out_off = ps.wh_off = (int64_t)s * (int64_t)pool_wphase_stride(p);
+        wj.count = (int64_t)Tn * C * (sd.hs + 1);
+        wj.per = sd.hs + 1, wj.pitch = c.HP;
+        f.wjobs.push_back(wj);
+    }
+    if (sl.fx_on) {
+        const float env_comp = formant_env_comp_of(sd.pitch_scale, sl.fx_semitones);
+        if (env_comp != 1.0f) ps.env_comp = env_comp; // (as mode FORMANT_CEPSTRAL skips the stage at pitch scale 1)
+    }
+    return ps;
+}
+
+// 5. the descriptors of every group: per group its PoolSlot table and ingest list (a mixed pool: sorted by variant,
+// with the PoolParams table), per slot what pool_describe_slot writes; then the egress list, and all of it into the
+// call's block
+static int pool_feed_describe(PoolFeed &f) {
+    pv_pool *p = f.p;
+    const Core &c = p->core;
+    const int32_t count = f.count;
+    int st;
+    f.grp.assign((size_t)f.groups + 1, PoolFeed::Group());
     std::vector<PoolSlot> table, fx_table;
-    // mixed pool: per group its PoolParams table (parallel to the PoolSlot table) and variant runs
     std::vector<PoolParams> params;
-    std::vector<int64_t> params_off((size_t)groups, 0);
-    std::vector<std::vector<VariantRun>> vruns((size_t)groups);
     std::vector<int> vkey;
-    std::vector<PoolIngest> ingest;
-    std::vector<WhisperJob> wjobs;
-    std::vector<int32_t> pinc;
-    std::vector<float> wden, wden_hi;
-    std::vector<ChainSlice> cs;
-    std::vector<int32_t> ro;
-    std::vector<ResTile> res_tiles;
-    std::vector<uint2> res_otab;
-    auto add_ingest = [&](int32_t i, int64_t upto, Group &g) {
-        pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
-        if (upto <= sl.uploaded) return;
-        PoolIngest e{};
-        e.src_off = stage_off[(size_t)i] + (sl.uploaded - call_base[(size_t)i]);
-        e.src_pitch = io.device ? io.in_pitch : n[i];
-        e.pos = sl.uploaded;
-        e.n = (int32_t)(upto - sl.uploaded);
-        e.row0 = slots[i] * C;
-        ingest.push_back(e);
-        if (e.n > g.max_in) g.max_in = e.n;
-        sl.uploaded = upto;
-    };
-    for (int32_t i = 0; i < count; ++i) p->slots[(size_t)slots[i]].fed += n[i];
-    bool any_whisper = false;
-    for (int gi = 0; gi < groups; ++gi) {
-        Group &g = grp[(size_t)gi];
-        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        table.clear();
-        fx_table.clear();
-        wjobs.clear();
-        ingest.clear();
-        params.clear();
-        vkey.clear();
+    for (int32_t i = 0; i < count; ++i) f.slot(i).fed += f.n[i];
+    for (int gi = 0; gi < f.groups; ++gi) {
+        PoolFeed::Group &g = f.grp[(size_t)gi];
+        table.clear(), fx_table.clear(), params.clear(), vkey.clear();
+        f.wjobs.clear(), f.ingest.clear();
         for (int32_t i = 0; i < count; ++i) {
-            const std::vector<SliceRec> &f = fresh[(size_t)i];
-            const int ta = gi * kStreamChunk;
-            if ((int)f.size() <= ta) continue;
-            const int tb = (int)f.size() - ta < kStreamChunk ? (int)f.size() : ta + kStreamChunk;
-            const int Tn = tb - ta;
-            pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+            const int nf = (int)f.fresh[(size_t)i].size(), ta = gi * kStreamChunk;
+            if (nf <= ta) continue;
+            const int tb = nf - ta < kStreamChunk ? nf : ta + kStreamChunk;
+            const pv_pool::Slot &sl = f.slot(i);
             const Derived &sd = *sl.d;
-            const int64_t t0 = sl.slices + ta;
-            int64_t need = (t0 + Tn - 1) * (int64_t)sd.hop + sd.N;
+            int64_t need = (sl.slices + tb - 1) * (int64_t)sd.hop + sd.N;
             if (need > sl.fed) need = sl.fed;
-            add_ingest(i, need, g);
-            PoolSlot ps{};
-            ps.t0 = t0;
-            ps.s0 = (int32_t)(t0 % c.TR);
-            ps.Tn = Tn;
-            ps.row0 = slots[i] * C;
-            ps.acc_sel = sl.acc_half | (t0 == 0 ? 2 : 0);
-            sl.acc_half ^= 1;
-            pinc.clear();
-            for (int t = ta; t < tb; ++t) pinc.push_back(f[(size_t)t].phase_inc);
-            ps.pinc_off = put(pinc.data(), pinc.size() * sizeof(int32_t));
-            wden.clear();
-            wden_hi.clear();
-            cs.clear();
-            ro.clear();
-            const int64_t ka = f[(size_t)ta].K0, kb = f[(size_t)tb - 1].K0 + f[(size_t)tb - 1].cnt;
-            sl.chain->begin_launch(f[(size_t)ta]);
-            for (int t = ta; t < tb; ++t) sl.chain->add(f[(size_t)t], INT64_MAX, wden, wden_hi);
-            sl.chain->end_launch(1, cs, ro);
-            while (wden.size() & 3) wden.push_back(1.f);
-            for (int k = 0; k < 4; ++k) wden.push_back(1.f);
-            if (sl.fast)
-                for (float &v : wden) v = 1.0f / v;
-            ps.cs_off = put(cs.data(), cs.size() * sizeof(ChainSlice));
-            const int32_t ro4[4] = {0, (int32_t)cs.size(), 0, 0};
-            ps.ro_off = put(ro4, sizeof ro4);
-            ps.wden_off = put(wden.data(), wden.size() * sizeof(float));
-            res_tiles.clear();
-            res_otab.clear();
-            if (sd.resample && kb > ka) build_res_tiles_of(sd, ka, kb, res_tiles, res_otab);
-            ps.res_ntiles = (int32_t)res_tiles.size();
-            ps.res_off = put(res_tiles.data(), res_tiles.size() * sizeof(ResTile));
-            ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
-            ps.out_off = out_base[(size_t)i] + (ka - k0[(size_t)i]);
-            ps.out_stride_row = to_caller ? io.out_pitch : out_cnt[(size_t)i];
-            ps.k_base = ka;
-            ps.wh_off = -1;
-            if (sl.voice == PV_VOICE_WHISPER) {
-                // the slot's draws of this launch, in the reference's order: slice-major, channel, bins 0 .. hs.  A
-                // stream's first launch starts from the pool's fresh state, every later one from the slot's own row
-                WhisperJob wj{};
-                wj.src_off = (int64_t)(t0 == 0 ? p->cap : slots[i]) * kWhisperStatePitch;
-                wj.dst_off = (int64_t)slots[i] * kWhisperStatePitch;
-                wj.out_off = ps.wh_off = (int64_t)slots[i] * (int64_t)pool_wphase_stride(p);
-                wj.count = (int64_t)Tn * C * (sd.hs + 1);
-                wj.per = sd.hs + 1, wj.pitch = c.HP;
-                wjobs.push_back(wj);
-            }
-            if (sl.fx_on) {
-                const float env_comp = formant_env_comp_of(sd.pitch_scale, sl.fx_semitones);
-                if (env_comp != 1.0f) { // (as mode FORMANT_CEPSTRAL skips the stage at pitch scale 1)
-                    ps.env_comp = env_comp;
-                    fx_table.push_back(ps);
-                    if (Tn > g.fx_max_tn) g.fx_max_tn = Tn;
-                }
+            pool_feed_ingest(f, i, need, g);
+            const PoolSlot ps = pool_describe_slot(f, i, ta, tb);
+            if (ps.env_comp != 0.f) { // (the formant stage is on for the slot)
+                fx_table.push_back(ps);
+                if (ps.Tn > g.fx_max_tn) g.fx_max_tn = ps.Tn;
             }
             table.push_back(ps);
-            if (Tn > g.max_tn) g.max_tn = Tn;
+            if (ps.Tn > g.max_tn) g.max_tn = ps.Tn;
             if (ps.res_ntiles > g.max_tiles) g.max_tiles = ps.res_ntiles;
             if (p->mixed) {
-                PoolParams q{};
-                q.two_pi_hop = sd.two_pi_hop;
-                q.hop = sd.hop;
-                q.do_freq_comp = sd.do_freq_comp ? 1 : 0;
-                q.freq_comp = sd.freq_comp;
-                q.fixed_gain = sd.fixed_gain;
-                if (sd.resample) {
-                    q.filt_len = sd.filt_len;
-                    q.oversample = sd.oversample;
-                    q.sinc_len = (int32_t)sd.sinc.size();
-                    q.tab_bytes = sl.tab_bytes;
-                    q.lds_floats = sl.lds_floats;
-                    const float4 *e = p->d_tabs.p + (size_t)sl.tab * p->tab_stride;
-                    q.sinc = reinterpret_cast<const float *>(e);
-                    q.tab4 = e + (size_t)(p->max_sinc + 3) / 4;
-                }
-                params.push_back(q);
-                // the variant: frequency compensation, resampling, fast kernels, interpolated table (sort order)
-                vkey.push_back(((sd.do_freq_comp ? 1 : 0) << 3) | ((sd.resample ? 1 : 0) << 2) | ((sl.fast ? 1 : 0) << 1) |
-                               ((sd.resample && sd.interp) ? 1 : 0));
+                params.push_back(slot_params(sd, sl.tab_bytes, sl.lds_floats,
+                                             sd.resample ? p->d_tabs.p + (size_t)sl.tab * p->tab_stride : nullptr,
+                                             (size_t)(p->max_sinc + 3) / 4));
+                vkey.push_back(variant_key(sd, sl.fast));
             }
         }
         if (p->mixed && !table.empty()) {
@@ -3771,105 +3845,91 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
             std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return vkey[(size_t)x] < vkey[(size_t)y]; });
             std::vector<PoolSlot> t2(table.size());
             std::vector<PoolParams> q2(table.size());
-            std::vector<VariantRun> &vr = vruns[(size_t)gi];
             for (size_t k = 0; k < ord.size(); ++k) {
                 t2[k] = table[(size_t)ord[k]];
                 q2[k] = params[(size_t)ord[k]];
-                const int key = vkey[(size_t)ord[k]];
-                if (k == 0 || key != vkey[(size_t)ord[k - 1]])
-                    vr.push_back(VariantRun{(int)k, 0, key >> 3 & 1, key >> 2 & 1, key >> 1 & 1, key & 1, 0, 0, 0, 1});
-                VariantRun &r = vr.back();
-                ++r.count;
-                if (t2[k].res_ntiles > r.max_tiles) r.max_tiles = t2[k].res_ntiles;
-                if (q2[k].lds_floats > r.lds_floats) r.lds_floats = q2[k].lds_floats;
-                if (q2[k].tab_bytes > r.tab_bytes) r.tab_bytes = q2[k].tab_bytes;
+                variant_runs_add(g.vr, (int)k, vkey[(size_t)ord[k]], t2[k].res_ntiles, q2[k].lds_floats, q2[k].tab_bytes, 1);
             }
             table.swap(t2);
             params.swap(q2);
-            params_off[(size_t)gi] = put(params.data(), params.size() * sizeof(PoolParams));
+            g.params_off = f.blob.put(params);
         }
         g.nslots = (int)table.size();
-        g.table_off = put(table.data(), table.size() * sizeof(PoolSlot));
+        g.table_off = f.blob.put(table);
         g.fx_nslots = (int)fx_table.size();
-        g.fx_off = put(fx_table.data(), fx_table.size() * sizeof(PoolSlot));
-        g.nwj = (int)wjobs.size();
-        g.wj_off = put(wjobs.data(), wjobs.size() * sizeof(WhisperJob));
-        any_whisper = any_whisper || !wjobs.empty();
-        g.ningest = (int)ingest.size();
-        g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
+        g.fx_off = f.blob.put(fx_table);
+        g.nwj = (int)f.wjobs.size();
+        g.wj_off = f.blob.put(f.wjobs);
+        f.any_whisper = f.any_whisper || !f.wjobs.empty();
+        g.ningest = (int)f.ingest.size();
+        g.ingest_off = f.blob.put(f.ingest);
     }
-    {
-        Group &g = grp[(size_t)groups];
-        g = Group{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        ingest.clear();
-        for (int32_t i = 0; i < count; ++i) add_ingest(i, p->slots[(size_t)slots[i]].fed, g);
-        g.ningest = (int)ingest.size();
-        g.ingest_off = put(ingest.data(), ingest.size() * sizeof(PoolIngest));
-    }
+    PoolFeed::Group &last = f.grp[(size_t)f.groups];
+    f.ingest.clear();
+    for (int32_t i = 0; i < count; ++i) pool_feed_ingest(f, i, f.slot(i).fed, last);
+    last.ningest = (int)f.ingest.size();
+    last.ingest_off = f.blob.put(f.ingest);
     for (int32_t i = 0; i < count; ++i) {
-        pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
-        sl.slices += (int64_t)fresh[(size_t)i].size();
-        if (!fresh[(size_t)i].empty()) sl.tap_n = (int)std::min<int64_t>((int64_t)fresh[(size_t)i].size(), c.TR);
+        pv_pool::Slot &sl = f.slot(i);
+        const int64_t nf = (int64_t)f.fresh[(size_t)i].size();
+        sl.slices += nf;
+        if (nf > 0) sl.tap_n = (int)std::min<int64_t>(nf, c.TR);
     }
-    // int16 output: what the egress kernel converts, per entry
-    int64_t egress_off = 0;
-    int negress = 0, max_egress = 0;
-    if (io.device && !to_caller) {
+    if (f.io.device && !f.to_caller) {
         std::vector<PoolEgress> eg;
         for (int32_t i = 0; i < count; ++i) {
-            const int64_t cnt = out_cnt[(size_t)i];
+            const int64_t cnt = f.out_cnt[(size_t)i];
             if (cnt <= 0) continue;
-            eg.push_back(PoolEgress{out_base[(size_t)i], cnt, (int64_t)i * C * io.out_pitch, io.out_pitch, (int32_t)cnt, 0});
-            if (cnt > max_egress) max_egress = (int)cnt;
+            eg.push_back(PoolEgress{f.out_base[(size_t)i], cnt, (int64_t)i * c.C * f.io.out_pitch, f.io.out_pitch, (int32_t)cnt, 0});
+            if (cnt > f.max_egress) f.max_egress = (int)cnt;
         }
-        negress = (int)eg.size();
-        egress_off = put(eg.data(), eg.size() * sizeof(PoolEgress));
+        f.negress = (int)eg.size();
+        f.egress_off = f.blob.put(eg);
     }
-    if (blob.size() > blk->h.n) {
-        size_t capn = blk->h.n ? blk->h.n : 256 * 1024;
-        while (capn < blob.size()) capn *= 2;
-        if ((st = blk->h.alloc(capn)) != PV_OK || (st = blk->d.alloc_on(capn, p->stream)) != PV_OK) return fail(st);
-    }
-    memcpy(blk->h.p, blob.data(), blob.size());
+    pv_pool::DescBlock *blk = f.blk;
+    const size_t bytes = f.blob.bytes.size();
+    if (bytes > blk->h.n)
+        if ((st = grow(blk->h, bytes, 256 * 1024)) != PV_OK || (st = blk->d.alloc_on(blk->h.n, p->stream)) != PV_OK) return st;
+    memcpy(blk->h.p, f.blob.bytes.data(), bytes);
+    return f.any_whisper ? pool_voice_buffers(p) : PV_OK;
+}
+
+// 6. the copies and the launches.  pv_pool_feed: the previous call has finished with both staging buffers.
+// pv_pool_feed_device: the pool's stream first waits for what the caller's stream holds now (the producer of d_in,
+// the last reader of d_out), and the caller's stream then for the block's event behind the launches.
+static int pool_feed_enqueue(PoolFeed &f) {
+    pv_pool *p = f.p;
+    const Core &c = p->core;
+    const PoolCall &io = f.io;
+    pv_pool::DescBlock *blk = f.blk;
     char *const d_desc = blk->d.p;
-    if (any_whisper && (st = pool_voice_buffers(p)) != PV_OK) return fail(st);
-    // 4. the copies and the launches.  pv_pool_feed: the previous call has finished with both staging buffers.
-    // pv_pool_feed_device: the pool's stream first waits for what the caller's stream holds now (the producer of d_in,
-    // the last reader of d_out).
+    int st;
     hipError_t ce = hipSuccess;
     if (io.device) {
         ce = hipEventRecord(blk->entry, io.user);
         if (ce == hipSuccess) ce = hipStreamWaitEvent(p->stream, blk->entry, 0);
-        if (ce != hipSuccess) return fail(hip_fail(ce, "stream pool entry event", __LINE__));
+        if (ce != hipSuccess) return hip_fail(ce, "stream pool entry event", __LINE__);
     }
 #ifndef PV_POOL_MAPPED_INGEST
-    if (stage_total && !io.device)
-        ce = hipMemcpyAsync(p->d_stage.p, p->h_stage.p, stage_total * sizeof(float), hipMemcpyHostToDevice, p->stream);
-    if (ce != hipSuccess) return fail(hip_fail(ce, "input upload", __LINE__));
+    if (f.stage_total && !io.device)
+        ce = hipMemcpyAsync(p->d_stage.p, p->h_stage.p, f.stage_total * sizeof(float), hipMemcpyHostToDevice, p->stream);
+    if (ce != hipSuccess) return hip_fail(ce, "input upload", __LINE__);
 #endif
-    ce = hipMemcpyAsync(d_desc, blk->h.p, blob.size(), hipMemcpyHostToDevice, p->stream);
-    if (ce != hipSuccess) return fail(hip_fail(ce, "descriptor upload", __LINE__));
+    ce = hipMemcpyAsync(d_desc, blk->h.p, f.blob.bytes.size(), hipMemcpyHostToDevice, p->stream);
+    if (ce != hipSuccess) return hip_fail(ce, "descriptor upload", __LINE__);
     int nlaunch = 0;
     const int cm = phase_mode(c.d);
-    for (int gi = 0; gi <= groups; ++gi) {
-        const Group &g = grp[(size_t)gi];
-        launch_pool_ingest(ingest_src, io.wire, p->d_in.p, p->ring, C, reinterpret_cast<const PoolIngest *>(d_desc + g.ingest_off),
+    for (int gi = 0; gi <= f.groups; ++gi) {
+        const PoolFeed::Group &g = f.grp[(size_t)gi];
+        launch_pool_ingest(f.ingest_src, io.wire, p->d_in.p, p->ring, c.C, reinterpret_cast<const PoolIngest *>(d_desc + g.ingest_off),
                            g.ningest, g.max_in, p->stream);
         if (g.ningest > 0 && g.max_in > 0) ++nlaunch;
         const hipError_t ie = hipGetLastError();
-        if (ie != hipSuccess) return fail(hip_fail(ie, "input ingest", __LINE__));
-        if (gi == groups || g.nslots == 0) continue;
-        PoolLaunch pl{};
-        pl.slots = reinterpret_cast<const PoolSlot *>(d_desc + g.table_off);
-        pl.desc = d_desc;
-        pl.out = launch_out;
-        pl.nslots = g.nslots;
-        pl.max_tn = g.max_tn;
-        pl.max_tiles = g.max_tiles;
-        PoolLaunch fx = pl;
-        fx.slots = reinterpret_cast<const PoolSlot *>(d_desc + g.fx_off);
-        fx.nslots = g.fx_nslots;
-        fx.max_tn = g.fx_max_tn;
+        if (ie != hipSuccess) return hip_fail(ie, "input ingest", __LINE__);
+        if (gi == f.groups || g.nslots == 0) continue;
+        auto table_at = [&](int64_t off) { return reinterpret_cast<const PoolSlot *>(d_desc + off); };
+        const PoolLaunch pl{table_at(g.table_off), d_desc, f.launch_out, g.nslots, g.max_tn, g.max_tiles};
+        const PoolLaunch fx{table_at(g.fx_off), d_desc, f.launch_out, g.fx_nslots, g.fx_max_tn, g.max_tiles};
         const PoolLaunch *const fxp = g.fx_nslots > 0 ? &fx : nullptr;
         const float *whisper = nullptr;
         if (g.nwj > 0) { // the group's whisper slots draw their phases: one launch, one wave per slot
@@ -3877,40 +3937,43 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
                            p->mixed ? PV_CENSUS_SET_PMIX : PV_CENSUS_SET_POOL, c.d.fft.nc, p->stream);
             ++nlaunch;
             const hipError_t we = hipGetLastError();
-            if (we != hipSuccess) return fail(hip_fail(we, "voice generator launch", __LINE__));
+            if (we != hipSuccess) return hip_fail(we, "voice generator launch", __LINE__);
             whisper = p->d_wphase.p;
         }
         if (p->mixed) {
-            const PoolParams *q = reinterpret_cast<const PoolParams *>(d_desc + params_off[(size_t)gi]);
-            if ((st = pool_mix_launch_group(p, pl, q, vruns[(size_t)gi], &nlaunch, fxp, whisper)) != PV_OK) return fail(st);
+            const PoolParams *q = reinterpret_cast<const PoolParams *>(d_desc + g.params_off);
+            if ((st = pool_mix_launch_group(p, pl, q, g.vr, &nlaunch, fxp, whisper)) != PV_OK) return st;
         } else {
-            if ((st = pool_launch_group(p, pl, true, fxp, whisper)) != PV_OK) return fail(st);
+            if ((st = pool_launch_group(p, pl, true, fxp, whisper)) != PV_OK) return st;
             nlaunch += 2 + (cm == 0 || cm == 1 ? 1 : 0) + (c.d.resample && pl.max_tiles > 0 ? 1 : 0) + (fxp ? 1 : 0);
         }
     }
-    if (io.device) {
-        // 5'. int16: the arena into the caller's buffer; then the block's event, which the caller's stream waits for
-        if (negress > 0) {
-            launch_pool_egress_i16(p->d_arena.p, static_cast<int16_t *>(io.d_out), C,
-                                   reinterpret_cast<const PoolEgress *>(d_desc + egress_off), negress, max_egress, p->stream);
-            ++nlaunch;
-            const hipError_t ee = hipGetLastError();
-            if (ee != hipSuccess) return fail(hip_fail(ee, "int16 egress", __LINE__));
-        }
-        p->last_launches = nlaunch;
-        ce = hipEventRecord(blk->done, p->stream);
-        if (ce == hipSuccess) {
-            blk->busy = true;
-            ce = hipStreamWaitEvent(io.user, blk->done, 0);
-        }
-        if (ce != hipSuccess) return fail(hip_fail(ce, "stream pool exit event", __LINE__));
-        p->last_host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count();
-        p->last_wait_us = 0;
-        return PV_OK;
+    if (f.negress > 0) { // int16: the arena into the caller's buffer
+
+        launch_pool_egress_i16(p->d_arena.p, static_cast<int16_t *>(io.d_out), c.C,
+                               reinterpret_cast<const PoolEgress *>(d_desc + f.egress_off), f.negress, f.max_egress, p->stream);
+        ++nlaunch;
+        const hipError_t ee = hipGetLastError();
+        if (ee != hipSuccess) return hip_fail(ee, "int16 egress", __LINE__);
     }
     p->last_launches = nlaunch;
-    // 5. wait: a sequence number behind the launches, spun on with a wall-clock bound (or a stream synchronisation
-    // where the device has no stream memory operations)
+    if (!io.device) return PV_OK;
+    // the block's event behind the launches, which the caller's stream waits for
+    ce = hipEventRecord(blk->done, p->stream);
+    if (ce == hipSuccess) {
+        blk->busy = true;
+        ce = hipStreamWaitEvent(io.user, blk->done, 0);
+    }
+    if (ce != hipSuccess) return hip_fail(ce, "stream pool exit event", __LINE__);
+    p->last_host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - f.t_call).count();
+    p->last_wait_us = 0;
+    return PV_OK;
+}
+
+// 7. wait (pv_pool_feed): a sequence number behind the launches, spun on with a wall-clock bound (or a stream
+// synchronisation where the device has no stream memory operations)
+static int pool_feed_wait(PoolFeed &f) {
+    pv_pool *p = f.p;
     hipError_t he = hipSuccess;
     const auto t_wait = std::chrono::steady_clock::now();
     if (p->wait_value) {
@@ -3930,7 +3993,7 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
                 if (__atomic_load_n(fl, __ATOMIC_ACQUIRE) == seq) break;
                 if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(10)) {
                     g_last_error = "stream pool: the call's kernels did not finish within 10 s";
-                    return fail(PV_ERR_HIP);
+                    return PV_ERR_HIP;
                 }
             }
         }
@@ -3938,22 +4001,51 @@ static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int3
         he = hipStreamSynchronize(p->stream);
     }
     if (he == hipSuccess) he = hipGetLastError();
-    if (he != hipSuccess) return fail(hip_fail(he, "stream pool call", __LINE__));
-    {
-        const auto t_done = std::chrono::steady_clock::now();
-        p->last_host_us = std::chrono::duration<double, std::micro>(t_wait - t_call).count();
-        p->last_wait_us = std::chrono::duration<double, std::micro>(t_done - t_wait).count();
-    }
-    // 6. the arena into the slots' FIFOs
-    for (int32_t i = 0; i < count; ++i) {
-        const int64_t cnt = out_cnt[(size_t)i];
+    if (he != hipSuccess) return hip_fail(he, "stream pool call", __LINE__);
+    p->last_wait_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_wait).count();
+    p->last_host_us = std::chrono::duration<double, std::micro>(t_wait - f.t_call).count();
+    return PV_OK;
+}
+
+// 8. deliver (pv_pool_feed): the arena into the slots' FIFOs
+static void pool_feed_deliver(PoolFeed &f) {
+    const int C = f.p->core.C;
+    for (int32_t i = 0; i < f.count; ++i) {
+        const int64_t cnt = f.out_cnt[(size_t)i];
         if (cnt <= 0) continue;
-        pv_pool::Slot &sl = p->slots[(size_t)slots[i]];
+        pv_pool::Slot &sl = f.slot(i);
         for (int ch = 0; ch < C; ++ch) {
-            const float *src = p->h_out.p + out_base[(size_t)i] + (size_t)ch * cnt;
+            const float *src = f.p->h_out.p + f.out_base[(size_t)i] + (size_t)ch * cnt;
             sl.outq[(size_t)ch].insert(sl.outq[(size_t)ch].end(), src, src + cnt);
         }
     }
+}
+
+// A feed in its phases.  1 and 2 refuse and leave the pool as it was.  From hipSetDevice on, device state and host
+// bookkeeping move together: a phase that fails there poisons the pool.
+static int pool_feed(pv_pool *p, int32_t count, const int32_t *slots, const int32_t *n, const PoolCall &io) {
+    g_last_error.clear();
+    plan_reason_clear();
+    PoolFeed f{p, count, slots, n, io};
+    int st;
+    if ((st = pool_feed_check(f)) != PV_OK) return st;
+    p->last_launches = 0;
+    if (count == 0) return PV_OK;
+    f.t_call = std::chrono::steady_clock::now();
+    if ((st = pool_feed_plan(f)) != PV_OK) return st;
+    const hipError_t e = hipSetDevice(p->core.device);
+    st = e == hipSuccess ? PV_OK : hip_fail(e, "hipSetDevice", __LINE__);
+    if (st == PV_OK) st = pool_feed_take_block(f);
+    if (st == PV_OK) st = pool_feed_place(f);
+    if (st == PV_OK) st = pool_feed_describe(f);
+    if (st == PV_OK) st = pool_feed_enqueue(f);
+    if (st == PV_OK && !io.device) st = pool_feed_wait(f);
+    if (st != PV_OK) {
+        p->poisoned = st;
+        p->poison_reason = g_last_error.empty() ? pv_strerror(st) : g_last_error;
+        return st;
+    }
+    if (!io.device) pool_feed_deliver(f);
     return PV_OK;
 }
 
@@ -4055,22 +4147,18 @@ static const char *pool_snap_mismatch(const snap::Header &blob, const snap::Head
 static int pool_snap_reserve(pv_pool *p, size_t stage_bytes, size_t nsegs) {
     int st;
     if (stage_bytes > p->d_snap.n || stage_bytes > p->h_snap.n) {
-        size_t capn = p->d_snap.n ? p->d_snap.n : (size_t)1 << 20;
-        while (capn < stage_bytes) capn *= 2;
-        if ((st = p->d_snap.alloc_on(capn, p->stream)) != PV_OK) {
+        if ((st = grow(p->d_snap, stage_bytes, (size_t)1 << 20, p->stream)) != PV_OK) {
             p->d_snap.release();
             return st;
         }
-        if ((st = p->h_snap.alloc(capn)) != PV_OK) {
+        if ((st = p->h_snap.alloc(p->d_snap.n)) != PV_OK) {
             p->h_snap.n = 0;
             return st;
         }
     }
     if (nsegs > p->h_seg.n || !p->seg_dev) {
-        size_t capn = p->h_seg.n ? p->h_seg.n : 256;
-        while (capn < nsegs) capn *= 2;
         p->seg_dev = nullptr;
-        if ((st = p->h_seg.alloc(capn)) != PV_OK) {
+        if ((st = grow(p->h_seg, nsegs, 256)) != PV_OK) {
             p->h_seg.n = 0;
             return st;
         }
@@ -4532,99 +4620,44 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
     const char *desc = b->dev->d_desc.p;
     const Derived &d = c.d; // (only what every stream shares: sizes, mode, coremode)
     const int cm = phase_mode(d);
-    auto refused = [](const char *what) {
-        g_last_error = std::string("mixed batch: no ") + what + " kernel for this configuration";
-        return PV_ERR_UNSUPPORTED;
-    };
-    auto launched = [launch](const char *what) -> int {
-        if (!launch) return PV_OK;
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PV_OK : hip_fail(e, what, __LINE__);
-    };
+    const LaunchCheck lc{"mixed batch", "mixed batch: no ", nullptr, launch};
     int rc;
-    PoolLaunch pl{};
-    pl.slots = reinterpret_cast<const PoolSlot *>(desc + g.table_off);
-    pl.desc = desc;
-    pl.out = d_out;
-    pl.nslots = g.nslots;
-    pl.max_tn = g.max_tn;
+    const PoolLaunch pl{reinterpret_cast<const PoolSlot *>(desc + g.table_off), desc, d_out, g.nslots, g.max_tn, 0};
     const PoolParams *q = reinterpret_cast<const PoolParams *>(desc + g.params_off);
     const MbSlot *ms = reinterpret_cast<const MbSlot *>(desc + g.mb_off);
     if (launch) {
         AnalyzeArgs aa = c.analyze_args(c.C); // (its hop is stream 0's: the kernel takes each slot's from PoolParams)
         aa.ia.in = d_in; // (no ring: each slot's offset and length are in MbSlot)
         aa.ia.mask = ~0ull;
-        if (!launch_mb_analyze(aa, pl, q, ms, st)) return refused("analysis");
-        if ((rc = launched("mixed batch analysis launch")) != PV_OK) return rc;
+        if ((rc = lc.after(launch_mb_analyze(aa, pl, q, ms, st), "analysis")) != PV_OK) return rc;
     }
     if (cm == 1) {
         const MatchArgs ma = c.match_args(c.C);
         const SeqArgs qa = c.seq_args(c.C);
         if (launch) {
             launch_mb_match(ma, pl, q, st);
-            if ((rc = launched("mixed batch match launch")) != PV_OK) return rc;
-            if (!launch_mb_seq(qa, pl, q, st)) return refused("rotation chain");
-            if ((rc = launched("mixed batch rotation chain launch")) != PV_OK) return rc;
+            if ((rc = lc.launched("match")) != PV_OK) return rc;
+            if ((rc = lc.after(launch_mb_seq(qa, pl, q, st), "rotation chain")) != PV_OK) return rc;
         } else if (!pool_phase_supported(d.hs, c.PKP)) { // (the pool's bound: a deeper ring than launch_mb_seq's)
-            return refused("rotation chain");
+            return lc.refused("rotation chain");
         }
     } else if (cm == 0 && launch) {
         const PropArgs pa = c.prop_args(c.C);
-        if (!launch_pmix_prop(pa, pl, q, st)) return refused("propagation");
-        if ((rc = launched("mixed batch propagation launch")) != PV_OK) return rc;
+        if ((rc = lc.after(launch_pmix_prop(pa, pl, q, st), "propagation")) != PV_OK) return rc;
     }
-    if (launch && g.fx_slots > 0) { // (the whole table: the slots with the setting off leave at their entry's 0)
-        if (!launch_slot_cepstral(slot_cepstral_args(c), pl, PV_CENSUS_SET_MB, st)) return refused("formant");
-        if ((rc = launched("mixed batch formant launch")) != PV_OK) return rc;
-    }
-    float *stream = c.stream.p ? c.stream.p : b->dev->mix_stream.p;
-    const std::vector<VariantRun> &runs = g.vr;
-    for (size_t a = 0; a < runs.size();) {
-        const size_t e = variant_group_end(runs, a);
-        const VariantRun &ra0 = runs[a];
-        PoolLaunch sub = pl;
-        sub.slots = pl.slots + ra0.first;
-        sub.nslots = runs[e - 1].first + runs[e - 1].count - ra0.first;
-        int max_runs = 1;
-        for (size_t k = a; k < e; ++k) max_runs = std::max(max_runs, runs[k].max_runs);
-        // the group's variant in place of stream 0's: whether to compensate, to resample, to take the fast kernel;
-        // the compensation factor and the gain themselves are per slot (PoolParams), the block's are neutral
-        SynthArgs sa = c.synth_args(c.C);
-        sa.do_freq_comp = ra0.dfc;
-        sa.freq_comp = 1;
-        sa.fixed_gain = 1;
-        if (b->voice_on) sa.whisper = b->d_voice.p;
-        ChainArgs ca = c.chain_args(c.C);
-        ca.stream = stream;
-        ca.resample = ra0.res;
-        ca.fast = ra0.fast;
-        if (!launch_mb_synth_chain(sa, ca, sub, q + ra0.first, ms + ra0.first, max_runs, st, launch))
-            return refused("synthesis + overlap-add");
-        if ((rc = launched("mixed batch synthesis + overlap-add launch")) != PV_OK) return rc;
-        for (size_t k = a; k < e && ra0.res; ++k) {
-            const VariantRun &rv = runs[k];
-            if (rv.max_tiles <= 0 && launch) continue; // (dropped or truncated slices only: no output completed)
-            PoolLaunch rs = pl;
-            rs.slots = pl.slots + rv.first;
-            rs.nslots = rv.count;
-            rs.max_tiles = rv.max_tiles;
-            ResArgs ra = c.res_args(c.C); // (not the uniform part: each slot brings its own filter set-up, PoolParams)
-            ra.stream = stream;
-            ra.interp = rv.interp;
-            ra.lds_floats = rv.lds_floats; // (the largest of the entries' slots)
-            ra.tab_bytes = rv.tab_bytes;
-            ra.fast = rv.fast;
-            if (!launch_mb_resample(ra, rs, q + rv.first, st, launch)) return refused("resampling");
-            if ((rc = launched("mixed batch resampling launch")) != PV_OK) return rc;
-        }
-        a = e;
-    }
-    return PV_OK;
+    if (launch && g.fx_slots > 0) // (the whole table: the slots with the setting off leave at their entry's 0)
+        if ((rc = lc.after(launch_slot_cepstral(slot_cepstral_args(c), pl, PV_CENSUS_SET_MB, st), "formant")) != PV_OK) return rc;
+    return launch_variant_groups(
+        c, pl, g.vr, c.stream.p ? c.stream.p : b->dev->mix_stream.p, b->voice_on ? b->d_voice.p : nullptr, lc,
+        [&](const SynthArgs &sa, const ChainArgs &ca, const PoolLaunch &sub, int first, int max_runs) {
+            return launch_mb_synth_chain(sa, ca, sub, q + first, ms + first, max_runs, st, launch);
+        },
+        [&](const ResArgs &ra, const PoolLaunch &rs, int first) { return launch_mb_resample(ra, rs, q + first, st, launch); });
 }
 
 // What a create or redraw has prepared on the host and has yet to put on the device (mb_prepare -> mb_commit).
 struct MbStage {
-    std::vector<char> blob;     // the host-built part of the descriptor block
+    DescBlob blob;              // the host-built part of the descriptor block
     int64_t dev_bytes = 0;      // the device-built part in front of it (redraw; 0: everything is in the blob)
     std::vector<MbWdenJob> wjobs;
     std::vector<MbOtabJob> ojobs;
@@ -4715,7 +4748,7 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
     std::vector<int> live((size_t)G, 0); // streams with slices in the group
     for (const pv_mbatch::Stream &t : b->s)
         for (int g = 0; (int64_t)g * Tc < (int64_t)t.plan.slices.size(); ++g) ++live[(size_t)g];
-    std::vector<char> &blob = stg.blob;
+    DescBlob &blob = stg.blob;
     {
         size_t est = 1 << 20;
         for (const pv_mbatch::Stream &t : b->s)
@@ -4723,14 +4756,8 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                    (on_device ? 0
                               : (size_t)t.plan.out_frames * 14 +
                                     (t.plan.slices.empty() ? 0 : (size_t)(t.plan.slices.back().P + t.d.N) * 5));
-        blob.reserve(est);
+        blob.bytes.reserve(est);
     }
-    auto put = [&](const void *src, size_t bytes) -> int64_t {
-        const size_t off = (blob.size() + 15) & ~(size_t)15;
-        blob.resize(off + bytes);
-        if (bytes) memcpy(blob.data() + off, src, bytes);
-        return (int64_t)off;
-    };
     auto reserve_dev = [&](size_t bytes) -> int64_t { // room in the device-built region (no host copy of it exists)
         const int64_t off = (stg.dev_bytes + 255) & ~(int64_t)255;
         stg.dev_bytes = off + (int64_t)bytes;
@@ -4777,8 +4804,8 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
             if (on_device) { // the per-slice records the denominator kernel reads, for the whole stream
                 s_P.clear(), s_adv.clear(), s_wl.assign((size_t)T, 0);
                 for (const SliceRec &r : sl) s_P.push_back(r.P), s_adv.push_back(r.adv);
-                p_off = put(s_P.data(), s_P.size() * sizeof(int64_t));
-                adv_off = put(s_adv.data(), s_adv.size() * sizeof(int32_t));
+                p_off = blob.put(s_P);
+                adv_off = blob.put(s_adv);
             }
             for (int g = 0; (int64_t)g * Tc < T; ++g) {
                 const int64_t t0 = (int64_t)g * Tc;
@@ -4793,7 +4820,7 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                 e.ps.acc_sel = (g & 1) | (g == 0 ? 2 : 0);
                 pinc.clear();
                 for (int64_t k = t0; k < t1; ++k) pinc.push_back(sl[(size_t)k].phase_inc);
-                e.ps.pinc_off = put(pinc.data(), pinc.size() * sizeof(int32_t));
+                e.ps.pinc_off = blob.put(pinc);
                 wden.clear(), wden_hi.clear(), cs.clear(), ro.clear();
                 const int64_t k0 = cb.begin_launch(sl[(size_t)t0]);
                 for (int64_t k = t0; k < t1; ++k) cb.add(sl[(size_t)k], t.plan.out_frames, wden, wden_hi);
@@ -4816,8 +4843,8 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                 if (b->has_runs_knob) runs_wanted = b->runs_knob;
                 e.ms.runs = cb.end_launch(runs_wanted > 32 ? 32 : runs_wanted, cs, ro);
                 while (ro.size() & 3) ro.push_back(0);
-                e.ps.cs_off = put(cs.data(), cs.size() * sizeof(ChainSlice));
-                e.ps.ro_off = put(ro.data(), ro.size() * sizeof(int32_t));
+                e.ps.cs_off = blob.put(cs);
+                e.ps.ro_off = blob.put(ro);
                 if (on_device) { // (every slice's entries are whole quads: no padding before the four trailing ones)
                     MbWdenJob jb{};
                     jb.total = (int32_t)(cb.wden_count + 4);
@@ -4831,11 +4858,8 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                     stg.wjobs.push_back(jb);
                     t.wden.push_back(pv_mbatch::Span{jb.dst_off, (int64_t)jb.total * (int64_t)sizeof(float), false});
                 } else {
-                    while (wden.size() & 3) wden.push_back(1.f);
-                    for (int k = 0; k < 4; ++k) wden.push_back(1.f);
-                    if (t.fast)
-                        for (float &v : wden) v = 1.0f / v;
-                    e.ps.wden_off = put(wden.data(), wden.size() * sizeof(float));
+                    finish_wden(wden, t.fast);
+                    e.ps.wden_off = blob.put(wden);
                     t.wden.push_back(pv_mbatch::Span{e.ps.wden_off, (int64_t)(wden.size() * sizeof(float)), true});
                 }
                 int64_t ka = sl[(size_t)t0].K0, kb = sl[(size_t)(t1 - 1)].K0 + sl[(size_t)(t1 - 1)].cnt;
@@ -4844,10 +4868,10 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                 res_tiles.clear(), res_otab.clear();
                 if (sd.resample && kb > ka) build_res_tiles_of(sd, ka, kb, res_tiles, res_otab, otab_on_device);
                 e.ps.res_ntiles = (int32_t)res_tiles.size();
-                e.ps.res_off = put(res_tiles.data(), res_tiles.size() * sizeof(ResTile));
+                e.ps.res_off = blob.put(res_tiles);
                 e.otab_in_blob = !(otab_on_device && !res_tiles.empty());
                 if (e.otab_in_blob) {
-                    e.ps.otab_off = put(res_otab.data(), res_otab.size() * sizeof(uint2));
+                    e.ps.otab_off = blob.put(res_otab);
                     t.otab.push_back(pv_mbatch::Span{e.ps.otab_off, (int64_t)(res_otab.size() * sizeof(uint2)), true});
                 } else {
                     MbOtabJob jb{};
@@ -4866,28 +4890,13 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                 e.ps.out_stride_row = t.plan.out_frames;
                 e.ps.k_base = k0;
                 e.ps.wh_off = -1; // (pv_mbatch_set_voice patches it)
-                e.q.two_pi_hop = sd.two_pi_hop;
-                e.q.hop = sd.hop;
-                e.q.do_freq_comp = sd.do_freq_comp ? 1 : 0;
-                e.q.freq_comp = sd.freq_comp;
-                e.q.fixed_gain = sd.fixed_gain;
-                if (sd.resample) {
-                    e.q.filt_len = sd.filt_len;
-                    e.q.oversample = sd.oversample;
-                    e.q.sinc_len = (int32_t)sd.sinc.size();
-                    e.q.tab_bytes = t.tab_bytes;
-                    e.q.lds_floats = t.lds_floats;
-                    const float4 *te = tab_base + (size_t)t.tab * stg.tab_stride;
-                    e.q.sinc = reinterpret_cast<const float *>(te);
-                    e.q.tab4 = te + stg.sinc4;
-                }
-                // the variant: frequency compensation, resampling, fast kernels, interpolated table (sort order)
-                e.key = ((sd.do_freq_comp ? 1 : 0) << 3) | ((sd.resample ? 1 : 0) << 2) | ((t.fast ? 1 : 0) << 1) |
-                        ((sd.resample && sd.interp) ? 1 : 0);
+                e.q = slot_params(sd, t.tab_bytes, t.lds_floats,
+                                  sd.resample ? tab_base + (size_t)t.tab * stg.tab_stride : nullptr, stg.sinc4);
+                e.key = variant_key(sd, t.fast);
                 mine.push_back(e);
             }
             if (on_device) {
-                const int64_t wl_off = put(s_wl.data(), s_wl.size() * sizeof(int32_t));
+                const int64_t wl_off = blob.put(s_wl);
                 for (size_t k = wj0; k < stg.wjobs.size(); ++k) stg.wjobs[k].woff_off = wl_off;
             }
         }
@@ -4924,26 +4933,19 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
             e.ps.pinc_off += shift, e.ps.cs_off += shift, e.ps.ro_off += shift, e.ps.res_off += shift;
             if (!on_device) e.ps.wden_off += shift;
             if (e.otab_in_blob) e.ps.otab_off += shift;
-            if (k == 0 || e.key != ev[k - 1].key)
-                gr.vr.push_back(VariantRun{(int)k, 0, e.key >> 3 & 1, e.key >> 2 & 1, e.key >> 1 & 1, e.key & 1, 0, 0, 0, 1});
-            VariantRun &r = gr.vr.back();
-            ++r.count;
-            r.max_tiles = std::max(r.max_tiles, (int)e.ps.res_ntiles);
-            r.lds_floats = std::max(r.lds_floats, (int)e.q.lds_floats);
-            r.tab_bytes = std::max(r.tab_bytes, (int)e.q.tab_bytes);
-            r.max_runs = std::max(r.max_runs, (int)e.ms.runs);
+            variant_runs_add(gr.vr, (int)k, e.key, e.ps.res_ntiles, e.q.lds_floats, e.q.tab_bytes, e.ms.runs);
             gr.max_tn = std::max(gr.max_tn, (int)e.ps.Tn);
             table.push_back(e.ps), params.push_back(e.q), mbs.push_back(e.ms);
             gr.stream_of.push_back(e.ps.row0 / C);
         }
         gr.nslots = (int)ev.size();
-        gr.table_off = shift + put(table.data(), table.size() * sizeof(PoolSlot));
-        gr.params_off = shift + put(params.data(), params.size() * sizeof(PoolParams));
-        gr.mb_off = shift + put(mbs.data(), mbs.size() * sizeof(MbSlot));
+        gr.table_off = shift + blob.put(table);
+        gr.params_off = shift + blob.put(params);
+        gr.mb_off = shift + blob.put(mbs);
         b->kernel_launches += mb_group_kernels(gr, cm);
     }
-    stg.wjobs_off = shift + put(stg.wjobs.data(), stg.wjobs.size() * sizeof(MbWdenJob));
-    stg.ojobs_off = shift + put(stg.ojobs.data(), stg.ojobs.size() * sizeof(MbOtabJob));
+    stg.wjobs_off = shift + blob.put(stg.wjobs);
+    stg.ojobs_off = shift + blob.put(stg.ojobs);
     return PV_OK;
 }
 
@@ -4963,7 +4965,7 @@ static int mb_commit(pv_mbatch *b, MbStage &stg, bool grow) {
     pv_mbatch::Dev &dv = *b->dev;
     const Core &c = dv.core;
     int st;
-    const size_t need = (size_t)stg.dev_bytes + stg.blob.size();
+    const size_t need = (size_t)stg.dev_bytes + stg.blob.bytes.size();
     if (need > dv.d_desc.n || !dv.d_desc.p) {
         DevBuf<char> fresh;
         if ((st = fresh.alloc(need + (grow ? need / 8 : 0))) != PV_OK) return st;
@@ -4978,21 +4980,12 @@ static int mb_commit(pv_mbatch *b, MbStage &stg, bool grow) {
     dv.tabs = stg.tabs, dv.sinc4 = stg.sinc4, dv.tab_stride = stg.tab_stride, dv.tab_cap = stg.tab_cap;
     std::vector<float4> img;
     for (const auto &up : stg.tab_uploads) {
-        const Derived &d = *up.second;
-        img.assign(dv.tab_stride, make_float4(0, 0, 0, 0));
-        memcpy(img.data(), d.sinc.data(), d.sinc.size() * sizeof(float));
-        float4 *t4 = img.data() + dv.sinc4;
-        if (d.interp) // (as Core::init expands them)
-            for (int off = 0; off < d.oversample; ++off)
-                for (int j = 0; j < d.filt_len; ++j) {
-                    const float *sp = d.sinc.data() + 4 + (j + 1) * d.oversample - off - 2;
-                    t4[(size_t)off * (d.filt_len + 1) + j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
-                }
+        slot_tab_image(*up.second, dv.tab_stride, dv.sinc4, img);
         HIPC(hipMemcpy(dv.d_tabs.p + (size_t)up.first * dv.tab_stride, img.data(), img.size() * sizeof(float4),
                        hipMemcpyHostToDevice));
     }
-    if (!stg.blob.empty())
-        HIPC(hipMemcpy(dv.d_desc.p + stg.dev_bytes, stg.blob.data(), stg.blob.size(), hipMemcpyHostToDevice));
+    if (!stg.blob.bytes.empty())
+        HIPC(hipMemcpy(dv.d_desc.p + stg.dev_bytes, stg.blob.bytes.data(), stg.blob.bytes.size(), hipMemcpyHostToDevice));
     launch_mb_build_wden(reinterpret_cast<const MbWdenJob *>(dv.d_desc.p + stg.wjobs_off), (int)stg.wjobs.size(), stg.wblocks,
                          dv.d_desc.p, c.window.p, nullptr);
     launch_mb_build_otab(reinterpret_cast<const MbOtabJob *>(dv.d_desc.p + stg.ojobs_off), (int)stg.ojobs.size(), stg.oblocks,
