@@ -1326,6 +1326,7 @@ struct pv_batch {
         int res_begin, res_ntiles; // ... and its tiles of the resampling kernel
         int64_t cs_begin;          // ... its run lists in d_cs
         int run_begin, runs;       // ... and their offsets in d_run_off
+        int warm;                  // ... and how many of the lists' entries are warm-up copies (pv_debug_batch_chain_runs)
     };
     DevBuf<ChainSlice> d_cs; // fused path: the run lists of every chunk
     DevBuf<int32_t> d_run_off;
@@ -2012,6 +2013,7 @@ int pv_batch_create(const pv_config *cfg, int32_t nstreams, int64_t frames, int3
         ch.cs_begin = 0;
         ch.run_begin = 0;
         ch.runs = 1;
+        ch.warm = 0;
         const int64_t t1 = t0 + ch.Tn;
         int64_t ka = sl[(size_t)t0].K0;
         int64_t kb = sl[(size_t)(t1 - 1)].K0 + sl[(size_t)(t1 - 1)].cnt;
@@ -2039,6 +2041,7 @@ int pv_batch_create(const pv_config *cfg, int32_t nstreams, int64_t frames, int3
             ch.cs_begin = (int64_t)cs.size();
             ch.run_begin = (int)run_off.size();
             ch.runs = cb.end_launch(runs_wanted > 32 ? 32 : runs_wanted, cs, run_off);
+            for (size_t i = (size_t)ch.cs_begin; i < cs.size(); ++i) ch.warm += (cs[i].flags & 2) ? 1 : 0;
             if (c.d.resample && kb > ka) {
                 ch.res_begin = (int)res_tiles.size();
                 c.build_res_tiles(ka, kb, res_tiles, res_otab);
@@ -5563,6 +5566,13 @@ extern "C" {
 int pv_debug_batch_plane_info(const pv_batch *b, pv_plane_info *info) {
     if (!b || !info) return PV_ERR_INVALID_ARG;
     plane_info_of(b->core, b->tap_begin, b->tap_end, info);
+    return PV_OK;
+}
+int pv_debug_batch_chain_runs(const pv_batch *b, int32_t launch, int32_t *runs, int32_t *warmups) {
+    if (!b || launch < 0 || (size_t)launch >= b->chunks.size()) return PV_ERR_INVALID_ARG;
+    const pv_batch::Chunk &ch = b->chunks[(size_t)launch];
+    if (runs) *runs = ch.runs;
+    if (warmups) *warmups = ch.warm;
     return PV_OK;
 }
 int pv_debug_batch_planes(pv_batch *b, int32_t stream, int32_t channel, int64_t slice, float *mag, float *phase,

@@ -197,6 +197,10 @@ static size_t next_pow2(size_t v) {
     return (size_t)1 << bits;
 }
 
+static thread_local const char *g_plan_reason = "";
+const char *plan_reason() { return g_plan_reason; }
+void plan_reason_clear() { g_plan_reason = ""; }
+
 int derive(const pv_config &cfg, Derived &d) {
     d = Derived();
     d.cfg = cfg;
@@ -250,7 +254,15 @@ int derive(const pv_config &cfg, Derived &d) {
         outHop = (size_t)int(windowSize / window_per_hop);
         inHop = (size_t)int(outHop / hsr);
     }
-    if (inHop < 1 || inHop > windowSize) return PV_ERR_INVALID_ARG;
+    if (inHop < 1) return PV_ERR_INVALID_ARG;
+    if (inHop > windowSize) {
+        // (every mode: a frame of N samples per hop leaves input between two frames unread.  The fixed-advance modes
+        // besides: the shift increment is the hop, and writeSlice overruns its accumulators beyond N -- what try_slice
+        // refuses, slice by slice, for the other modes)
+        g_plan_reason = "input hop above the FFT size: frames would skip input samples (where the mode's shift increment "
+                        "is the hop it also falls outside [1, fftsize]: undefined behaviour in the reference)";
+        return PV_ERR_UNSUPPORTED;
+    }
     d.N = (int)windowSize;
     d.hs = d.N / 2;
     d.H = d.hs + 1;
@@ -303,7 +315,13 @@ int derive(const pv_config &cfg, Derived &d) {
     if (d.robotic || d.whisper || d.constant || d.vocoder) d.min_shift = d.hop;
     else if (d.int_ratio) d.min_shift = (int)(size_t)(d.hop * hsr);
     else d.min_shift = (int)std::lrint(((size_t)d.hop * hsr) / 2);
-    if (d.min_shift < 1) return PV_ERR_INVALID_ARG;
+    if (d.min_shift < 1) {
+        // (the reference runs such a configuration while its increments stay at 1; the engine sizes its frame rings by
+        // the clamp's lower end and has no size for zero)
+        g_plan_reason = "hop too small for this ratio: the smallest shift increment a slice can take, lrint(hop x time "
+                        "ratio x pitch scale / 2), is below 1";
+        return PV_ERR_INVALID_ARG;
+    }
     return PV_OK;
 }
 
@@ -329,10 +347,6 @@ int Planner::next_increment() {
     if (crossed_zero) recovery_ = divergence_ / slices_per_tenth;
     return (int)step;
 }
-
-static thread_local const char *g_plan_reason = "";
-const char *plan_reason() { return g_plan_reason; }
-void plan_reason_clear() { g_plan_reason = ""; }
 
 int Planner::try_slice(std::vector<SliceRec> &out) {
     if (in_fill_ < d_.N) return PV_OK; // inbufReady false -> processOneSlice returns early

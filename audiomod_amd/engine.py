@@ -233,6 +233,7 @@ def lib():
         getattr(L, name + "_plane_info").argtypes = [C.c_void_p] + ([] if name == "pv_debug_batch" else lead) + [
             C.POINTER(PlaneInfo)]
         getattr(L, name + "_planes").argtypes = [C.c_void_p] + lead + [C.c_int32, C.c_int64] + [C.c_void_p] * 7
+    L.pv_debug_batch_chain_runs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.pv_formant_env_comp.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
     L.pv_set_formant.argtypes = [C.c_void_p, C.c_int, C.c_float]
     L.pv_batch_set_formant.argtypes = [C.c_void_p, C.c_int, C.c_float]
@@ -719,6 +720,14 @@ class Batch:
     def planes(self, stream, channel, t):
         """Diagnostics: slice t of the planes of a stream's channel (see _planes); waits for the device"""
         return _planes("pv_debug_batch", self.h, (int(stream),), self.plane_info(), channel, t)
+
+    def chain_runs(self, launch):
+        """Diagnostics, host only: (runs, warm-up entries) of the fused kernel's run lists for launch `launch` (0 ...
+        self.launches - 1), as creation laid them out (pv_debug_batch_chain_runs); launches nothing"""
+        runs, warm = C.c_int32(0), C.c_int32(0)
+        _check(self.L.pv_debug_batch_chain_runs(self.h, int(launch), C.byref(runs), C.byref(warm)),
+               "pv_debug_batch_chain_runs")
+        return runs.value, warm.value
 
     def alloc_out(self):
         import torch

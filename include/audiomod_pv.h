@@ -62,7 +62,10 @@ typedef struct pv_config {
     int32_t mode;     /* PV_MODE_* */
     int32_t coremode; /* PV_CORE_* */
     int32_t fftsize;  /* rounded up to a power of two like the reference (phasevocoderimpl.cc:177-181) */
-    int32_t hopsize;  /* 0 = auto, the only value the reference CLI passes */
+    int32_t hopsize;  /* 0 = auto, the only value the reference CLI passes.  A hop above the FFT size: PV_ERR_UNSUPPORTED
+                       * at creation; one so small that lrint(hop x time ratio x pitch scale / 2) is 0: PV_ERR_INVALID_ARG
+                       * at creation; both with the reason in pv_last_error().  A slice whose shift increment leaves
+                       * [1, fftsize]: PV_ERR_UNSUPPORTED from the call that plans it */
 } pv_config;
 
 /* Derived constants (reference Impl::calculateSizes, phasevocoderimpl.cc:169-263, and the Speex set-up,
@@ -753,6 +756,12 @@ int pv_debug_pool_planes(pv_pool *p, int32_t slot, int32_t channel, int64_t slic
 int pv_debug_mbatch_plane_info(const pv_mbatch *b, int32_t stream, pv_plane_info *info);
 int pv_debug_mbatch_planes(pv_mbatch *b, int32_t stream, int32_t channel, int64_t slice, float *mag, float *phase,
                            int32_t *npk, int32_t *peaks, int32_t *mode, float *rot, float *outphase);
+/* Diagnostics, host only (reads what pv_batch_create laid out; launches nothing): how launch `launch` (0 ...
+ * pv_batch_launches - 1) of a batch splits a row's slices for the fused synthesis + overlap-add kernel -- the number
+ * of runs (one workgroup per row and run; 1 on the tile path) and the number of warm-up entries in their lists, the
+ * copies of earlier frames a later run re-adds before its own (flag bit 1 of a list entry).  Either pointer may be
+ * NULL.  A launch outside the range: PV_ERR_INVALID_ARG. */
+int pv_debug_batch_chain_runs(const pv_batch *b, int32_t launch, int32_t *runs, int32_t *warmups);
 
 #define PV_WIRE_F32 0
 #define PV_WIRE_I16 1

@@ -61,6 +61,27 @@ def test_level_and_corner_cases_match_reference(kind, fft):
         assert np.isfinite(want).all() and (kind == "zero" or np.abs(want).max() > 0)
 
 
+def _ola_rows():
+    from tests import ola_advance_signals as S
+    return S.DEFINED
+
+
+@pytest.mark.parametrize("name", _ola_rows())
+def test_overlap_add_advance_rows_match_reference(name):
+    """The rows of tests/ola_advance_signals.py (advances from 1 to the FFT size, dropped slices, the non-finite samples
+    of an advance of N) through the compiled reference: the same counts, and the same bits wherever the reference's
+    samples are finite -- and non-finite samples at the same positions."""
+    from tests import ola_advance_signals as S
+    row = S.BY_NAME[name]
+    want, wc = O.ref_run(S.clip(name), block=row.block, flush=True, **row.cfg)
+    run = S.oracle(name)
+    assert list(run.counts) == wc
+    fin = np.isfinite(want)
+    assert want.shape == run.y.shape and np.array_equal(np.isfinite(run.y), fin)
+    assert np.array_equal(run.y.view(np.uint32)[fin], want.view(np.uint32)[fin])
+    assert np.count_nonzero(~fin) == S.FIGURES[name][4]
+
+
 def test_realtime_matches_reference():
     x = signals.noise(20000, 2)
     want, wc = O.ref_run(x, api="rt", semitones=-7.0, block=512)
