@@ -24,6 +24,7 @@
 #include "pv_kernels.h"
 #include "pv_wavefft.h"
 #include "pv_plan.h"
+#include "pv_carrier.h"
 #include "pv_snapshot.h"
 #include "pv_whisper.h"
 
@@ -1436,8 +1437,20 @@ struct pv_pool {
         float fx_semitones = 0.f;
         // the voice setting (pv_pool_set_voice): host state, read when a feed builds the slot's PoolSlot
         int voice = PV_VOICE_ROBOTIC;
+        // the carrier setting (pv_pool_set_carrier).  A carrier slot's `d` is the vocoder engine's own derived constants
+        // (own_d, in a uniform pool too), and planner and chain are built from them.  car_pos: the samples of the
+        // slot's carrier its row of the carrier ring holds, [.., car_pos) -- written by the launch groups as far as
+        // their frames reach, so it trails `uploaded` by what no slice has needed yet
+        int carrier = PV_CARRIER_NONE;
+        int64_t car_pos = 0;
     };
     std::vector<Slot> slots;
+    // The carrier setting's device side, allocated by the first feed that has a carrier slot: the carrier ring
+    // [cap][ring] (one row per slot: every channel's carrier is the same sequence), positions as in the input ring, and
+    // the carrier planes [cap][TR][HP] that the group's carrier analysis writes and its synthesis reads.  ctab: the
+    // period tables of the pool's sample rate (host; a feed with carrier slots copies them into its descriptor block)
+    DevBuf<float> d_cring, d_cmag, d_cphase;
+    CarrierTables ctab;
     // The voice setting's device side, allocated by the first feed (or restore) that has a whisper slot: the generator
     // state rows [cap + 1][kWhisperStatePitch] -- row `cap` is the constant fresh state, which a stream's first launch
     // reads instead of its own row -- and the phases of one launch group, [cap][kStreamChunk][C][HP]
@@ -1624,13 +1637,19 @@ struct LaunchCheck {
     int after(bool accepted, const char *stage) const { return accepted ? launched(stage) : refused(stage); }
 };
 
+// The carrier setting's planes for a launch group's synthesis (SynthArgs::cmag / cphase; PoolSlot::car_off indexes
+// them): null where the group holds no carrier slot.
+struct PoolCarrier {
+    const float *cmag = nullptr, *cphase = nullptr;
+};
+
 // The fused synthesis + overlap-add and the resampling of a launch group whose table `pl` is sorted by variant (`runs`).
 // Each launch takes the group's variant in place of stream 0's: whether to compensate, to resample, to take the fast
 // kernel; the compensation factor and the gain themselves are per slot (PoolParams), the block's are neutral.
 // synth(sa, ca, sub, first, max_runs) and res(ra, rs, first) launch on the entries from `first` on.
 template <typename Synth, typename Res>
 static int launch_variant_groups(const Core &c, const PoolLaunch &pl, const std::vector<VariantRun> &runs, float *stream,
-                                 const float *whisper, const LaunchCheck &lc, Synth synth, Res res) {
+                                 const float *whisper, const PoolCarrier &car, const LaunchCheck &lc, Synth synth, Res res) {
     int rc;
     for (size_t a = 0; a < runs.size();) {
         const size_t e = variant_group_end(runs, a);
@@ -1644,6 +1663,7 @@ static int launch_variant_groups(const Core &c, const PoolLaunch &pl, const std:
         sa.freq_comp = 1;
         sa.fixed_gain = 1;
         if (whisper) sa.whisper = whisper;
+        if (car.cmag) sa.cmag = car.cmag, sa.cphase = car.cphase;
         ChainArgs ca = c.chain_args(c.C);
         ca.stream = stream;
         ca.resample = ra0.res;
@@ -2777,7 +2797,7 @@ static bool pool_slot_ok(const pv_pool *p, int32_t slot) {
 }
 
 static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch = true, const PoolLaunch *fx = nullptr,
-                             const float *whisper = nullptr);
+                             const float *whisper = nullptr, const PoolCarrier &car = PoolCarrier());
 
 // Core::init and pool_create allocate with DevBuf::alloc, whose zero fill is on the default stream; nothing orders that
 // stream against the pool's own non-blocking one.  pv_pool_create therefore ends with a wait for the fills, so that no
@@ -3087,10 +3107,9 @@ static int pool_tab_acquire(pv_pool *p, const Derived &d, int *out) {
     return PV_OK;
 }
 
-// Makes slot s an open stream of the given constants with no history (own: a mixed pool's slot's, else null).
-static void pool_slot_begin(pv_pool *p, int32_t s, std::unique_ptr<Derived> own, int tab) {
-    Core &c = p->core;
-    pv_pool::Slot &sl = p->slots[(size_t)s];
+// the slot's constants and what is built from them: planner and chain start from nothing (own: null = the pool's own)
+static void pool_slot_set_constants(pv_pool *p, pv_pool::Slot &sl, std::unique_ptr<Derived> own, int tab) {
+    const Core &c = p->core;
     sl.own_d = std::move(own);
     sl.d = sl.own_d ? sl.own_d.get() : &c.d;
     sl.fast = Core::fast_capable_of(*sl.d, c.fast_arith);
@@ -3100,11 +3119,19 @@ static void pool_slot_begin(pv_pool *p, int32_t s, std::unique_ptr<Derived> own,
     sl.tab_bytes = res_tab_bytes(*sl.d);
     sl.planner.reset(new Planner(*sl.d));
     sl.chain.reset(new ChainBuilder(*sl.d, c.chain_AR, c.chain_smask));
+}
+
+// Makes slot s an open stream of the given constants with no history (own: a mixed pool's slot's, else null).
+static void pool_slot_begin(pv_pool *p, int32_t s, std::unique_ptr<Derived> own, int tab) {
+    Core &c = p->core;
+    pv_pool::Slot &sl = p->slots[(size_t)s];
+    pool_slot_set_constants(p, sl, std::move(own), tab);
     sl.fed = sl.uploaded = sl.slices = 0;
     sl.tap_n = 0;
     sl.acc_half = 0;
     sl.fx_on = false, sl.fx_semitones = 0.f;
     sl.voice = PV_VOICE_ROBOTIC;
+    sl.carrier = PV_CARRIER_NONE, sl.car_pos = 0;
     sl.outq.assign((size_t)c.C, std::vector<float>());
     sl.outq_head = 0;
     sl.open = true;
@@ -3345,6 +3372,10 @@ int pv_pool_set_voice(pv_pool *p, int32_t slot, int voice) {
         g_last_error = "voice setting: slot " + std::to_string(slot) + " has processed slices (the voice is set before the first)";
         return PV_ERR_INVALID_ARG;
     }
+    if (voice == PV_VOICE_WHISPER && sl.carrier != PV_CARRIER_NONE) {
+        g_last_error = "voice setting: slot " + std::to_string(slot) + " has a carrier (a stream is one engine: vocoder or WHISPER)";
+        return PV_ERR_INVALID_ARG;
+    }
     sl.voice = voice;
     return PV_OK;
 }
@@ -3352,6 +3383,196 @@ int pv_pool_set_voice(pv_pool *p, int32_t slot, int voice) {
 int pv_pool_get_voice(const pv_pool *p, int32_t slot, int *voice) {
     if (!pool_slot_ok(p, slot)) return PV_ERR_INVALID_ARG;
     if (voice) *voice = p->slots[(size_t)slot].voice;
+    return PV_OK;
+}
+
+// ---- the carrier setting (audiomod_pv.h "Carrier setting")
+static int carrier_value_check(int carrier) {
+    if (carrier == PV_CARRIER_NONE || carrier == PV_CARRIER_ROSENBERG || carrier == PV_CARRIER_CHORD) return PV_OK;
+    g_last_error = "carrier setting: unknown carrier " + std::to_string(carrier);
+    return PV_ERR_INVALID_ARG;
+}
+// the mode of the engine a carrier slot is, and back (PV_CARRIER_NONE for every other mode)
+static int carrier_mode(int carrier) {
+    return carrier == PV_CARRIER_CHORD ? PV_MODE_VOCODER_CHORD : PV_MODE_VOCODER_ROSENBERG;
+}
+static int carrier_of_mode(int mode) {
+    return mode == PV_MODE_VOCODER_ROSENBERG ? PV_CARRIER_ROSENBERG : mode == PV_MODE_VOCODER_CHORD ? PV_CARRIER_CHORD : PV_CARRIER_NONE;
+}
+
+// The constants of the vocoder engine a carrier slot at this time ratio and pitch is: derive() of the pool's
+// configuration under the carrier's mode -- the engine's own, not a second statement of its rules -- checked against
+// what the pool's launches run and what its per-row buffers were sized for.  Host only; changes nothing in the pool
+// but its (lazily built) carrier tables.  (pv_pool_set_carrier and pv_pool_restore)
+static int pool_carrier_constants(pv_pool *p, float time_ratio, float semis, int carrier, std::unique_ptr<Derived> &own) {
+    const Core &c = p->core;
+    if (!p->mixed && c.d.resample) {
+        g_last_error = "carrier setting: a pool from pv_pool_create runs one resampling variant for all its slots and this "
+                       "one resamples (pitch other than 0), which a vocoder stream never does: create the pool with "
+                       "pv_pool_create_mixed";
+        return PV_ERR_UNSUPPORTED;
+    }
+    own.reset(new Derived());
+    pv_config cs = c.d.cfg;
+    cs.mode = carrier_mode(carrier);
+    cs.time_ratio = time_ratio;
+    cs.pitch_semitones = semis;
+    const int st = derive(cs, *own);
+    if (st != PV_OK) {
+        if (g_last_error.empty()) g_last_error = std::string("carrier setting: the vocoder engine refuses this pitch / time ratio: ") + plan_reason();
+        return st;
+    }
+    const Derived &d = *own;
+    if (p->ctab.v.empty()) carrier_tables(c.d.cfg.sample_rate, p->ctab);
+    const char *big = d.hop > p->max_hop                         ? "input ring (the vocoder's input hop)"
+                      : pool_max_adv(d) > c.chain_max_adv        ? "overlap-add rings (the vocoder's advance)"
+                      : p->ctab.v.size() > (size_t)kCarrierMaxFloats ? "descriptor block (the carrier's period tables at this sample rate)"
+                                                                     : nullptr;
+    if (big) {
+        g_last_error = std::string("carrier setting: the vocoder stream needs more of the pool's ") + big + " than the pool was sized for";
+        return PV_ERR_UNSUPPORTED;
+    }
+    return PV_OK;
+}
+// the pool's carrier ring and planes, made in stream order by the first feed that needs them
+static int pool_carrier_buffers(pv_pool *p) {
+    if (p->d_cring.p && p->d_cmag.p && p->d_cphase.p) return PV_OK;
+    const Core &c = p->core;
+    int st;
+    if ((st = p->d_cring.alloc_on((size_t)p->cap * p->ring, p->stream)) != PV_OK) return st;
+    if ((st = p->d_cmag.alloc_on((size_t)p->cap * c.TR * c.HP, p->stream)) != PV_OK) return st;
+    return p->d_cphase.alloc_on((size_t)p->cap * c.TR * c.HP, p->stream);
+}
+
+// The slot's carrier: host state that the next feed's descriptor building reads, as the voice.  The slot's constants,
+// planner and chain become the vocoder engine's (or the robotic engine's again); what the slot was fed before its
+// first slice stays fed.
+int pv_pool_set_carrier(pv_pool *p, int32_t slot, int carrier) {
+    g_last_error.clear();
+    plan_reason_clear();
+    if (!p) return PV_ERR_INVALID_ARG;
+    if (p->core.d.cfg.mode != PV_MODE_ROBOTIC) {
+        g_last_error = "carrier setting: the carrier belongs to ROBOTIC pools (create the pool with mode ROBOTIC)";
+        return PV_ERR_UNSUPPORTED;
+    }
+    if (!pool_slot_ok(p, slot)) {
+        g_last_error = "stream pool: slot " + std::to_string(slot) + " is not open";
+        return PV_ERR_INVALID_ARG;
+    }
+    int st;
+    if ((st = carrier_value_check(carrier)) != PV_OK) return st;
+    pv_pool::Slot &sl = p->slots[(size_t)slot];
+    if (sl.slices != 0) {
+        g_last_error = "carrier setting: slot " + std::to_string(slot) + " has processed slices (the carrier is set before the first)";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (carrier != PV_CARRIER_NONE && sl.voice == PV_VOICE_WHISPER) {
+        g_last_error = "carrier setting: slot " + std::to_string(slot) + " has the WHISPER voice (a stream is one engine: vocoder or WHISPER)";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (carrier == sl.carrier) return PV_OK;
+    const float time_ratio = sl.d->cfg.time_ratio, semis = sl.d->cfg.pitch_semitones;
+    std::unique_ptr<Derived> own;
+    int tab = -1;
+    if (carrier != PV_CARRIER_NONE) {
+        if ((st = pool_carrier_constants(p, time_ratio, semis, carrier, own)) != PV_OK) return st;
+    } else if (p->mixed) { // back to the robotic slot pv_pool_open_with made
+        if ((st = pool_slot_constants(p, time_ratio, semis, own)) != PV_OK) return st;
+        if (own->resample && (st = pool_tab_acquire(p, *own, &tab)) != PV_OK) return st;
+    }
+    const Planner::State fed = sl.planner->save(); // (no slice yet: the samples waiting for the first frame)
+    pool_release_tab(p, sl);
+    pool_slot_set_constants(p, sl, std::move(own), tab);
+    sl.planner->restore(fed);
+    sl.carrier = carrier;
+    sl.car_pos = 0;
+    return PV_OK;
+}
+
+int pv_pool_get_carrier(const pv_pool *p, int32_t slot, int *carrier) {
+    if (!pool_slot_ok(p, slot)) return PV_ERR_INVALID_ARG;
+    if (carrier) *carrier = p->slots[(size_t)slot].carrier;
+    return PV_OK;
+}
+
+static int carrier_window_check(int32_t sample_rate, int carrier) {
+    if (sample_rate < 1) {
+        g_last_error = "carrier: sample rate below 1";
+        return PV_ERR_INVALID_ARG;
+    }
+    if (carrier != PV_CARRIER_ROSENBERG && carrier != PV_CARRIER_CHORD) {
+        g_last_error = "carrier: unknown carrier " + std::to_string(carrier) + " (ROSENBERG or CHORD)";
+        return PV_ERR_INVALID_ARG;
+    }
+    return PV_OK;
+}
+
+// host only: the closed form itself
+int pv_plan_carrier(int32_t sample_rate, int carrier, int64_t first, int64_t count, float *out) {
+    g_last_error.clear();
+    if (!out || first < 0 || count < 0) return PV_ERR_INVALID_ARG;
+    const int st = carrier_window_check(sample_rate, carrier);
+    if (st != PV_OK) return st;
+    CarrierTables t;
+    carrier_tables(sample_rate, t);
+    const bool chord = carrier == PV_CARRIER_CHORD;
+    const int base = chord ? 1 : 0;
+    uint32_t r[3] = {0, 0, 0};
+    for (int v = 0; v < (chord ? 3 : 1); ++v) r[v] = (uint32_t)(first % t.len[base + v]);
+    for (int64_t i = 0; i < count; ++i) {
+        out[i] = carrier_sample(t.v.data(), t.off, chord ? 1 : 0, r[0], r[1], r[2]);
+        for (int v = 0; v < (chord ? 3 : 1); ++v)
+            if (++r[v] == (uint32_t)t.len[base + v]) r[v] = 0;
+    }
+    return PV_OK;
+}
+
+// Diagnostics: the production carrier kernel alone, njobs windows in ONE launch, concatenated into out.
+int pv_debug_carrier(int32_t sample_rate, int carrier, const int64_t *first, const int32_t *count, int32_t njobs, float *out,
+                     int device) {
+    g_last_error.clear();
+    if (njobs < 0 || (njobs > 0 && (!first || !count)) || !out) return PV_ERR_INVALID_ARG;
+    int st = carrier_window_check(sample_rate, carrier);
+    if (st != PV_OK) return st;
+    int64_t total = 0;
+    int max_n = 0;
+    for (int32_t i = 0; i < njobs; ++i) {
+        if (first[i] < 0 || count[i] < 0) return PV_ERR_INVALID_ARG;
+        total += count[i];
+        max_n = std::max(max_n, (int)count[i]);
+    }
+    CarrierTables t;
+    carrier_tables(sample_rate, t);
+    if (t.v.size() > (size_t)kCarrierMaxFloats) {
+        g_last_error = "carrier: the period tables of this sample rate exceed what a launch carries";
+        return PV_ERR_UNSUPPORTED;
+    }
+    if (count_gfx950() <= 0) {
+        g_last_error = "no gfx950 (MI355X) device visible: this library has no CPU fallback";
+        return PV_ERR_NO_DEVICE;
+    }
+    if (total == 0) return PV_OK;
+    HIPC(hipSetDevice(device));
+    std::vector<CarrierJob> hj;
+    int64_t off = 0;
+    for (int32_t i = 0; i < njobs; ++i) {
+        hj.push_back(carrier_job(t, carrier == PV_CARRIER_CHORD, first[i], count[i], off, 0u));
+        off += count[i];
+    }
+    DevBuf<float> d_out, d_tab;
+    DevBuf<CarrierJob> d_jobs;
+    if ((st = d_out.alloc((size_t)total)) != PV_OK || (st = d_tab.upload(t.v)) != PV_OK || (st = d_jobs.upload(hj)) != PV_OK) return st;
+    CarrierArgs a{};
+    a.out = d_out.p;
+    a.tab = d_tab.p;
+    for (int k = 0; k < kCarrierTabs; ++k) a.off[k] = t.off[k], a.len[k] = t.len[k];
+    a.mask = 0xffffffffu; // (linear: a window of fewer than 2^31 samples from pos 0)
+    a.jobs = d_jobs.p;
+    launch_carrier(a, njobs, max_n, nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "carrier generator launch", __LINE__);
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(out, d_out.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
     return PV_OK;
 }
 
@@ -3471,8 +3692,9 @@ static int pool_launch_front(const pv_pool *p, const PoolLaunch &pl, const PoolP
 // launch = false: launch nothing, only ask the launchers whether this configuration fits them (pv_pool_create)
 // whisper: the phase buffer where the group holds a whisper slot (PoolSlot::wh_off), drawn by the caller's generator
 // launch; else null
+// car: the carrier planes where the group holds a carrier slot (PoolSlot::car_off), written by pool_launch_carrier
 static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch, const PoolLaunch *fx,
-                             const float *whisper) {
+                             const float *whisper, const PoolCarrier &car) {
     const Core &c = p->core;
     hipStream_t st = p->stream;
     const LaunchCheck lc{"pool", "stream pool: no per-slot ", nullptr, launch};
@@ -3480,6 +3702,7 @@ static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch
     if ((rc = pool_launch_front(p, pl, nullptr, lc, fx)) != PV_OK) return rc;
     SynthArgs sa = c.synth_args(c.C);
     if (whisper) sa.whisper = whisper;
+    if (car.cmag) sa.cmag = car.cmag, sa.cphase = car.cphase;
     const ChainArgs ca = c.chain_args(c.C);
     if ((rc = lc.after(launch_pool_synth_chain(sa, ca, pl, st, launch), "synthesis + overlap-add")) != PV_OK) return rc;
     if (!c.d.resample) return PV_OK;
@@ -3490,13 +3713,13 @@ static int pool_launch_group(const pv_pool *p, const PoolLaunch &pl, bool launch
 // the PoolParams table `q`.  Counts the kernels it launches in *nlaunch.
 static int pool_mix_launch_group(const pv_pool *p, const PoolLaunch &pl, const PoolParams *q,
                                  const std::vector<VariantRun> &runs, int *nlaunch, const PoolLaunch *fx,
-                                 const float *whisper) {
+                                 const float *whisper, const PoolCarrier &car) {
     const Core &c = p->core;
     hipStream_t st = p->stream;
     const LaunchCheck lc{"pool", "stream pool: no per-slot ", nlaunch, true};
     if (const int rc = pool_launch_front(p, pl, q, lc, fx)) return rc;
     return launch_variant_groups(
-        c, pl, runs, c.stream.p ? c.stream.p : p->mix_stream.p, whisper, lc,
+        c, pl, runs, c.stream.p ? c.stream.p : p->mix_stream.p, whisper, car, lc,
         [&](const SynthArgs &sa, const ChainArgs &ca, const PoolLaunch &sub, int first, int) {
             return launch_pmix_synth_chain(sa, ca, sub, q + first, st);
         },
@@ -3541,16 +3764,25 @@ struct PoolFeed {
         int fx_nslots = 0, fx_max_tn = 0;
         int64_t wj_off = 0; // the generator's jobs: one per whisper slot of the group
         int nwj = 0;
+        // the carrier setting: the generator's jobs (one per carrier slot whose frames reach past what its row
+        // holds), and the carrier analysis' table -- the group's carrier slots once more, row0 = the slot itself
+        // (one carrier row per slot) -- with its PoolParams (mixed pool)
+        int64_t cj_off = 0, car_off = 0, car_params_off = 0;
+        int ncj = 0, max_cn = 0, car_nslots = 0, car_max_tn = 0;
         int64_t params_off = 0;     // mixed pool: the group's PoolParams table (parallel to the PoolSlot table)
         std::vector<VariantRun> vr; // ... and its variant runs
     };
     std::vector<Group> grp; // (+ the final ingest of what the call leaves unconsumed)
-    bool any_whisper = false;
+    bool any_whisper = false, any_carrier = false;
+    int64_t ctab_off = 0; // the carrier's period tables (where a group has generator jobs)
     int64_t egress_off = 0; // int16 output: what the egress kernel converts, per entry
     int negress = 0, max_egress = 0;
     DescBlob blob;
     std::vector<PoolIngest> ingest; // the group being described: its ingest list and generator jobs
     std::vector<WhisperJob> wjobs;
+    std::vector<CarrierJob> cjobs;
+    std::vector<PoolSlot> car_table;
+    std::vector<PoolParams> car_params;
     std::vector<int32_t> pinc, ro; // pool_describe_slot's scratch
     std::vector<float> wden, wden_hi;
     std::vector<ChainSlice> cs;
@@ -3793,6 +4025,22 @@ static PoolSlot pool_describe_slot(PoolFeed &f, int32_t i, int ta, int tb) {
         wj.per = sd.hs + 1, wj.pitch = c.HP;
         f.wjobs.push_back(wj);
     }
+    ps.car_off = -1;
+    if (sl.carrier != PV_CARRIER_NONE) {
+        // the carrier's frames of this launch lie at the ring positions of the input's: samples up to the last
+        // frame's end, from where the slot's row holds them (a restored slot's: from this launch's first frame)
+        ps.car_off = (int64_t)s * c.TR * c.HP;
+        const int64_t from = std::max(sl.car_pos, t0 * (int64_t)sd.hop), upto = (t0 + Tn - 1) * (int64_t)sd.hop + sd.N;
+        if (upto > from) {
+            f.cjobs.push_back(carrier_job(p->ctab, sl.carrier == PV_CARRIER_CHORD, from, (int32_t)(upto - from),
+                                          (int64_t)s * p->ring, (uint32_t)(from & (int64_t)(p->ring - 1))));
+            sl.car_pos = upto;
+        }
+        PoolSlot cs = ps;
+        cs.row0 = s;
+        f.car_table.push_back(cs);
+        if (p->mixed) f.car_params.push_back(slot_params(sd, 0, 0, nullptr, 0));
+    }
     if (sl.fx_on) {
         const float env_comp = formant_env_comp_of(sd.pitch_scale, sl.fx_semitones);
         if (env_comp != 1.0f) ps.env_comp = env_comp; // (as mode FORMANT_CEPSTRAL skips the stage at pitch scale 1)
@@ -3817,6 +4065,7 @@ static int pool_feed_describe(PoolFeed &f) {
         PoolFeed::Group &g = f.grp[(size_t)gi];
         table.clear(), fx_table.clear(), params.clear(), vkey.clear();
         f.wjobs.clear(), f.ingest.clear();
+        f.cjobs.clear(), f.car_table.clear(), f.car_params.clear();
         for (int32_t i = 0; i < count; ++i) {
             const int nf = (int)f.fresh[(size_t)i].size(), ta = gi * kStreamChunk;
             if (nf <= ta) continue;
@@ -3864,6 +4113,14 @@ static int pool_feed_describe(PoolFeed &f) {
         g.nwj = (int)f.wjobs.size();
         g.wj_off = f.blob.put(f.wjobs);
         f.any_whisper = f.any_whisper || !f.wjobs.empty();
+        g.ncj = (int)f.cjobs.size();
+        g.cj_off = f.blob.put(f.cjobs);
+        for (const CarrierJob &cj : f.cjobs) g.max_cn = std::max(g.max_cn, (int)cj.n);
+        g.car_nslots = (int)f.car_table.size();
+        g.car_off = f.blob.put(f.car_table);
+        g.car_params_off = f.blob.put(f.car_params);
+        for (const PoolSlot &cs : f.car_table) g.car_max_tn = std::max(g.car_max_tn, (int)cs.Tn);
+        f.any_carrier = f.any_carrier || !f.car_table.empty();
         g.ningest = (int)f.ingest.size();
         g.ingest_off = f.blob.put(f.ingest);
     }
@@ -3889,12 +4146,51 @@ static int pool_feed_describe(PoolFeed &f) {
         f.negress = (int)eg.size();
         f.egress_off = f.blob.put(eg);
     }
+    if (f.any_carrier) f.ctab_off = f.blob.put(p->ctab.v);
     pv_pool::DescBlock *blk = f.blk;
     const size_t bytes = f.blob.bytes.size();
     if (bytes > blk->h.n)
         if ((st = grow(blk->h, bytes, 256 * 1024)) != PV_OK || (st = blk->d.alloc_on(blk->h.n, p->stream)) != PV_OK) return st;
     memcpy(blk->h.p, f.blob.bytes.data(), bytes);
+    if (f.any_carrier && (st = pool_carrier_buffers(p)) != PV_OK) return st;
     return f.any_whisper ? pool_voice_buffers(p) : PV_OK;
+}
+
+// A launch group's carrier slots: one launch writes every slot's new carrier samples into its row of the carrier ring,
+// one launch of the set's analysis kernel turns the carrier frames of the group's slices into the slots' carrier planes
+// (find_peaks = 0, one row per slot: as Core::launch_chunk analyses a batch's carrier row).
+static int pool_launch_carrier(const pv_pool *p, int64_t cj_off, int ncj, int max_cn, int64_t car_off, int car_nslots,
+                               int car_max_tn, int64_t car_params_off, const char *d_desc, int64_t ctab_off, float *out,
+                               int *nlaunch) {
+    const Core &c = p->core;
+    CarrierArgs ga{};
+    ga.out = p->d_cring.p;
+    ga.tab = reinterpret_cast<const float *>(d_desc + ctab_off);
+    for (int k = 0; k < kCarrierTabs; ++k) ga.off[k] = p->ctab.off[k], ga.len[k] = p->ctab.len[k];
+    ga.mask = (uint32_t)(p->ring - 1);
+    ga.jobs = reinterpret_cast<const CarrierJob *>(d_desc + cj_off);
+    if (ncj > 0 && max_cn > 0) {
+        launch_carrier(ga, ncj, max_cn, p->stream);
+        ++*nlaunch;
+        const hipError_t ge = hipGetLastError();
+        if (ge != hipSuccess) return hip_fail(ge, "carrier generator launch", __LINE__);
+    }
+    AnalyzeArgs aa = c.analyze_args(c.C);
+    aa.rows = 1;
+    aa.find_peaks = 0;
+    aa.mag = p->d_cmag.p;
+    aa.phase = p->d_cphase.p;
+    aa.ia = InAddr{};
+    aa.ia.in = p->d_cring.p;
+    aa.ia.stride_c = p->ring;
+    aa.ia.stride_s = p->ring;
+    aa.ia.mask = (uint64_t)(p->ring - 1);
+    aa.ia.len = INT64_MAX;
+    const PoolLaunch pl{reinterpret_cast<const PoolSlot *>(d_desc + car_off), d_desc, out, car_nslots, car_max_tn, 0};
+    const LaunchCheck lc{"pool", "stream pool: no per-slot ", nlaunch, true};
+    const bool ok = p->mixed ? launch_pmix_analyze(aa, pl, reinterpret_cast<const PoolParams *>(d_desc + car_params_off), p->stream)
+                             : launch_pool_analyze(aa, pl, p->stream);
+    return lc.after(ok, "carrier analysis");
 }
 
 // 6. the copies and the launches.  pv_pool_feed: the previous call has finished with both staging buffers.
@@ -3943,11 +4239,18 @@ static int pool_feed_enqueue(PoolFeed &f) {
             if (we != hipSuccess) return hip_fail(we, "voice generator launch", __LINE__);
             whisper = p->d_wphase.p;
         }
+        PoolCarrier car{};
+        if (g.car_nslots > 0) { // the group's carrier slots: their carrier samples, then the planes of its frames
+            if ((st = pool_launch_carrier(p, g.cj_off, g.ncj, g.max_cn, g.car_off, g.car_nslots, g.car_max_tn,
+                                          g.car_params_off, d_desc, f.ctab_off, f.launch_out, &nlaunch)) != PV_OK)
+                return st;
+            car.cmag = p->d_cmag.p, car.cphase = p->d_cphase.p;
+        }
         if (p->mixed) {
             const PoolParams *q = reinterpret_cast<const PoolParams *>(d_desc + g.params_off);
-            if ((st = pool_mix_launch_group(p, pl, q, g.vr, &nlaunch, fxp, whisper)) != PV_OK) return st;
+            if ((st = pool_mix_launch_group(p, pl, q, g.vr, &nlaunch, fxp, whisper, car)) != PV_OK) return st;
         } else {
-            if ((st = pool_launch_group(p, pl, true, fxp, whisper)) != PV_OK) return st;
+            if ((st = pool_launch_group(p, pl, true, fxp, whisper, car)) != PV_OK) return st;
             nlaunch += 2 + (cm == 0 || cm == 1 ? 1 : 0) + (c.d.resample && pl.max_tiles > 0 ? 1 : 0) + (fxp ? 1 : 0);
         }
     }
@@ -4119,6 +4422,7 @@ static void pool_snap_header(const pv_pool *p, const pv_pool::Slot &sl, snap::He
     h.time_ratio = sl.d->cfg.time_ratio;
     h.pitch_semitones = sl.d->cfg.pitch_semitones;
     if (sl.voice == PV_VOICE_WHISPER) h.mode = PV_MODE_WHISPER; // (the stream is that engine's: a version-2 blob)
+    if (sl.carrier != PV_CARRIER_NONE) h.mode = carrier_mode(sl.carrier); // (... a vocoder engine's: version 3)
     snap::fill_sizes(h, (int32_t)sl.chain->live.size(), pool_slot_pending(sl));
 }
 // the first field in which a blob's pool differs from this one (nullptr: none).  Both sides are pools' own derived
@@ -4128,7 +4432,9 @@ static const char *pool_snap_mismatch(const snap::Header &blob, const snap::Head
     if (blob.f != pool.f) return name
     PV_SNAP_FIELD(sample_rate, "sample rate");
     PV_SNAP_FIELD(channels, "channels");
-    if ((blob.mode == PV_MODE_WHISPER ? PV_MODE_ROBOTIC : blob.mode) != pool.mode) return "mode"; // (the voice setting)
+    // (the voice and carrier settings: such a stream lives in a ROBOTIC pool)
+    if ((blob.mode == PV_MODE_WHISPER || carrier_of_mode(blob.mode) != PV_CARRIER_NONE ? PV_MODE_ROBOTIC : blob.mode) != pool.mode)
+        return "mode";
     PV_SNAP_FIELD(coremode, "coremode");
     PV_SNAP_FIELD(N, "FFT size");
     PV_SNAP_FIELD(hopsize, "hop setting");
@@ -4344,7 +4650,13 @@ int pv_pool_restore(pv_pool *p, int32_t count, const void *const *blobs, const i
                                            : "a pool from pv_pool_create takes only its configuration's pitch / time ratio");
             return PV_ERR_INVALID_ARG;
         }
-        if (p->mixed) {
+        if (const int carrier = carrier_of_mode(h.mode)) { // a carrier slot's constants are the vocoder engine's
+            const int st = pool_carrier_constants(p, h.time_ratio, h.pitch_semitones, carrier, own[(size_t)i]);
+            if (st != PV_OK) {
+                g_last_error = who + g_last_error;
+                return st;
+            }
+        } else if (p->mixed) {
             const int st = pool_slot_constants(p, h.time_ratio, h.pitch_semitones, own[(size_t)i]);
             if (st != PV_OK) {
                 g_last_error = who + g_last_error;
@@ -4413,6 +4725,9 @@ int pv_pool_restore(pv_pool *p, int32_t count, const void *const *blobs, const i
         sl.tap_n = 0; // (a blob carries the recurrences' state, not the planes of its last launch)
         sl.acc_half = hs.acc_half;
         if (h.mode == PV_MODE_WHISPER) sl.voice = PV_VOICE_WHISPER; // (its state row came with the payload)
+        // (a carrier slot's row of the carrier ring is not in the blob: its next launch group rewrites what its frames
+        // read, from the closed form -- pool_describe_slot starts at the group's first frame)
+        sl.carrier = carrier_of_mode(h.mode);
         for (int ch = 0; ch < c.C && h.pending > 0; ++ch) {
             sl.outq[(size_t)ch].resize((size_t)h.pending);
             memcpy(sl.outq[(size_t)ch].data(), snap::pending_of(blobs[i], h, ch), (size_t)h.pending * sizeof(float));
@@ -4651,7 +4966,8 @@ static int mb_launch_group(const pv_mbatch *b, const pv_mbatch::Group &g, const 
     if (launch && g.fx_slots > 0) // (the whole table: the slots with the setting off leave at their entry's 0)
         if ((rc = lc.after(launch_slot_cepstral(slot_cepstral_args(c), pl, PV_CENSUS_SET_MB, st), "formant")) != PV_OK) return rc;
     return launch_variant_groups(
-        c, pl, g.vr, c.stream.p ? c.stream.p : b->dev->mix_stream.p, b->voice_on ? b->d_voice.p : nullptr, lc,
+        c, pl, g.vr, c.stream.p ? c.stream.p : b->dev->mix_stream.p, b->voice_on ? b->d_voice.p : nullptr,
+        PoolCarrier(), lc, // (the carrier setting is the pools': audiomod_pv.h)
         [&](const SynthArgs &sa, const ChainArgs &ca, const PoolLaunch &sub, int first, int max_runs) {
             return launch_mb_synth_chain(sa, ca, sub, q + first, ms + first, max_runs, st, launch);
         },
@@ -4893,6 +5209,7 @@ static int mb_prepare(pv_mbatch *b, const pv_mbatch_stream *s, bool on_device, M
                 e.ps.out_stride_row = t.plan.out_frames;
                 e.ps.k_base = k0;
                 e.ps.wh_off = -1; // (pv_mbatch_set_voice patches it)
+                e.ps.car_off = -1;
                 e.q = slot_params(sd, t.tab_bytes, t.lds_floats,
                                   sd.resample ? tab_base + (size_t)t.tab * stg.tab_stride : nullptr, stg.sinc4);
                 e.key = variant_key(sd, t.fast);

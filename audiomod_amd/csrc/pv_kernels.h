@@ -281,6 +281,11 @@ void census_voice(int set, int nc); // PV_CENSUS_VOICE (a = NC 128 ... 4096): on
 struct WhisperJob;
 void launch_whisper(uint32_t *state, float *out, const WhisperJob *jobs, int njobs, int census_set, int nc, hipStream_t st);
 
+// The carrier setting's generator (pv_carrier.hip, pv_carrier.h): njobs windows of carrier samples in one launch, grid
+// (ceil(max_n / kCarrierThreads), njobs); a.jobs and a.tab: device memory.
+struct CarrierArgs;
+void launch_carrier(const CarrierArgs &a, int njobs, int max_n, hipStream_t st);
+
 // pv_resample_kernel: one workgroup = 256 outputs of two rows
 struct ResTile {
     int64_t k0;   // first output
@@ -370,6 +375,9 @@ struct PoolSlot {
     int64_t wh_off;         // the voice setting: float offset of the slot's phases [Tn][C][HP] of this launch in
                             // SynthArgs::whisper (drawn by pv_whisper_kernel); -1: the slot stays robotic.  Read only
                             // where the launch's SynthArgs::whisper is set
+    int64_t car_off;        // the carrier setting: float offset of the slot's carrier planes [TR][HP] in
+                            // SynthArgs::cmag / cphase (written by the group's carrier analysis); -1: none.  Read only
+                            // by the pool and pmix sets, and only where the launch's SynthArgs::cmag is set
 };
 struct PoolLaunch {
     const PoolSlot *slots; // [nslots]

@@ -4493,6 +4493,12 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     if constexpr (kPlainCore < 0) { // the voice setting: a whisper slot of a ROBOTIC object reads its drawn phases
         sv.whisper = (s.whisper && ps.wh_off >= 0) ? s.whisper + ps.wh_off : nullptr;
         if (sv.whisper) sv.robotic = 0;
+        // the carrier setting: a carrier slot is a channel vocoder over its own carrier planes (band length as derive())
+        if (s.cmag && ps.car_off >= 0) {
+            sv.cmag = s.cmag + ps.car_off, sv.cphase = s.cphase + ps.car_off;
+            sv.voc_band_len = (2 * NC) / 1024;
+            sv.robotic = 0;
+        }
     }
     ChainArgs cv = c;
     cv.Tn = ps.Tn;
@@ -4739,6 +4745,12 @@ __global__ __launch_bounds__(pool_chain_max_threads(NC, kPlainCore, kFast)) void
     if constexpr (kPlainCore < 0) { // the voice setting: a whisper slot of a ROBOTIC object reads its drawn phases
         sv.whisper = (s.whisper && ps.wh_off >= 0) ? s.whisper + ps.wh_off : nullptr;
         if (sv.whisper) sv.robotic = 0;
+        // the carrier setting: a carrier slot is a channel vocoder over its own carrier planes (band length as derive())
+        if (s.cmag && ps.car_off >= 0) {
+            sv.cmag = s.cmag + ps.car_off, sv.cphase = s.cphase + ps.car_off;
+            sv.voc_band_len = (2 * NC) / 1024;
+            sv.robotic = 0;
+        }
     }
     ChainArgs cv = c;
     cv.Tn = ps.Tn;

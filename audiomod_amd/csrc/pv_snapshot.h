@@ -34,7 +34,18 @@ constexpr uint32_t kVersion = 1;
 // stream is that engine's -- and the directory ends with the slot's generator state row (pv_whisper.h).  Only such blobs
 // carry this version: a robotic slot's blob is version 1, byte for byte what it always was.
 constexpr uint32_t kVersionVoice = 2;
-inline uint32_t version_of(int32_t mode) { return mode == PV_MODE_WHISPER ? kVersionVoice : kVersion; }
+// A slot with a carrier (include/audiomod_pv.h "Carrier setting"): the header's mode reads PV_MODE_VOCODER_ROSENBERG or
+// PV_MODE_VOCODER_CHORD -- the stream is that engine's, and so are the planner state and the live frames.  The payload
+// is a robotic slot's: the slot's row of the carrier ring is NOT saved.  The carrier is a closed form of the sample
+// position, so pv_pool_restore leaves the row to the slot's next launch group, which rewrites everything its frames
+// read (from the group's first frame on); the carrier planes hold nothing that outlives a launch.  Two saves of one
+// stream history are therefore byte-identical whatever the rows held.
+constexpr uint32_t kVersionCarrier = 3;
+inline uint32_t version_of(int32_t mode) {
+    return mode == PV_MODE_WHISPER ? kVersionVoice
+           : (mode == PV_MODE_VOCODER_ROSENBERG || mode == PV_MODE_VOCODER_CHORD) ? kVersionCarrier
+                                                                                   : kVersion;
+}
 
 // The per-row device buffers a slot carries between calls, in payload order.  Which of them a configuration has follows
 // from its phase stage and from whether its pool keeps an overlap-add stream ring (seg_bytes).
@@ -220,7 +231,7 @@ inline const char *validate(const void *blob, int64_t bytes, Header *out) {
     memcpy(&h, p, sizeof h);
     if (h.total_bytes != (uint64_t)bytes) return "its length differs from the one its header states (truncated?)";
     if (h.magic != kMagic) return "not a stream-pool snapshot (magic)";
-    if (h.version != kVersion && h.version != kVersionVoice) return "an unknown format version";
+    if (h.version != kVersion && h.version != kVersionVoice && h.version != kVersionCarrier) return "an unknown format version";
     if (h.version != version_of(h.mode)) return "its format version does not go with its mode";
     if (h.header_bytes != sizeof(Header)) return "header size";
     auto in = [](int64_t v, int64_t lo, int64_t hi) { return v >= lo && v <= hi; };

@@ -244,6 +244,13 @@ def lib():
     L.pv_pool_get_voice.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     L.pv_mbatch_set_voice.argtypes = [C.c_void_p, C.c_void_p]
     L.pv_debug_whisper_phases.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int]
+    # (AUDIOMOD_PV_LIB may name a library built before the carrier setting -- the parent leg of tools/carrier_bench.py --
+    # which has none of these; using the setting on it then raises AttributeError)
+    if hasattr(L, "pv_pool_set_carrier"):
+        L.pv_pool_set_carrier.argtypes = [C.c_void_p, C.c_int32, C.c_int]
+        L.pv_pool_get_carrier.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
+        L.pv_plan_carrier.argtypes = [C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+        L.pv_debug_carrier.argtypes = [C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int]
     L.pv_set_arithmetic.argtypes = [C.c_int]
     L.pv_get_arithmetic.restype = C.c_int
     _lib = L
@@ -511,6 +518,37 @@ def whisper_device_phases(counts, device=0):
     out = np.zeros(max(int(counts.sum()), 1), np.float32)
     _check(lib().pv_debug_whisper_phases(counts.ctypes.data, len(counts), out.ctypes.data, device), "pv_debug_whisper_phases")
     return out[:int(counts.sum())]
+
+
+CARRIERS = {"none": 0, "rosenberg": 1, "chord": 2}  # PV_CARRIER_*
+
+
+def _carrier_value(c):
+    """a carrier as the C ABI takes it: a name of CARRIERS, or the number itself (passed on unchecked)"""
+    return CARRIERS[c] if isinstance(c, str) else int(c)
+
+
+def plan_carrier(sample_rate, carrier, first, count):
+    """`count` samples of the vocoder carrier ("rosenberg" / "chord") from absolute sample index `first`: the closed
+    form (pv_plan_carrier; host only).  Equals plan_table(2, mode="vocoder" / "vocoder_chord") from `first` on."""
+    out = np.zeros(max(int(count), 1), np.float32)
+    _check(lib().pv_plan_carrier(int(sample_rate), _carrier_value(carrier), int(first), int(count), out.ctypes.data),
+           "pv_plan_carrier")
+    return out[:max(int(count), 0)]
+
+
+def carrier_device(sample_rate, carrier, firsts, counts, device=0):
+    """Diagnostics: the carrier setting's generator kernel alone (pv_debug_carrier).  One launch writes the windows
+    (firsts[i], counts[i]); all of them concatenated, float32.  Window i equals plan_carrier(sample_rate, carrier,
+    firsts[i], counts[i]) bit for bit."""
+    firsts = np.ascontiguousarray(firsts, dtype=np.int64)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    assert firsts.ndim == 1 and counts.shape == firsts.shape
+    total = int(counts.astype(np.int64).sum())
+    out = np.zeros(max(total, 1), np.float32)
+    _check(lib().pv_debug_carrier(int(sample_rate), _carrier_value(carrier), firsts.ctypes.data, counts.ctypes.data,
+                                  len(firsts), out.ctypes.data, device), "pv_debug_carrier")
+    return out[:total]
 
 
 def voice_census_read():
@@ -1182,16 +1220,18 @@ class StreamPool:
     def __del__(self):
         self.close_pool()
 
-    def open(self, semitones=None, time_ratio=None, voice=None):
+    def open(self, semitones=None, time_ratio=None, voice=None, carrier=None):
         """A fresh stream in the lowest free slot, at the given pitch / time ratio (default: the configuration's);
-        returns the slot.  voice: set_voice() for the new slot (a pool of mode robotic)."""
+        returns the slot.  voice: set_voice() for the new slot, carrier: set_carrier() (a pool of mode robotic)."""
         s = self._open(semitones, time_ratio)
-        if voice is not None:
-            try:
+        try:
+            if voice is not None:
                 self.set_voice(s, voice)
-            except Exception:
-                self.close(s)
-                raise
+            if carrier is not None:
+                self.set_carrier(s, carrier)
+        except Exception:
+            self.close(s)
+            raise
         return s
 
     def _open(self, semitones, time_ratio):
@@ -1327,7 +1367,9 @@ class StreamPool:
         """A second slot of this pool with the slot's history: both return the same bits from here on (a blob does not
         carry the formant setting, so the new slot gets the slot's setting here)."""
         s = self.restore(self.save(int(slot)))
-        self.set_formant(s, self.get_formant(slot))
+        st = self.get_formant(slot)
+        if st is not None:  # (a restored slot has the setting off, and a pool outside its scope refuses the call)
+            self.set_formant(s, st)
         return s
 
     def set_formant(self, slot, st):
@@ -1350,6 +1392,17 @@ class StreamPool:
         v = C.c_int(0)
         _check(self.L.pv_pool_get_voice(self.h, int(slot), C.byref(v)), "pv_pool_get_voice")
         return {n: k for k, n in VOICES.items()}[v.value]
+
+    def set_carrier(self, slot, carrier):
+        """The slot's carrier, "none", "rosenberg" or "chord" (pv_pool_set_carrier): a pool of mode robotic, a slot that
+        has processed no slice yet.  A carrier slot is from then on bit for bit a PhaseVocoder of mode vocoder /
+        vocoder_chord with the slot's pitch and time ratio."""
+        _check(self.L.pv_pool_set_carrier(self.h, int(slot), _carrier_value(carrier)), "pv_pool_set_carrier")
+
+    def get_carrier(self, slot):
+        v = C.c_int(0)
+        _check(self.L.pv_pool_get_carrier(self.h, int(slot), C.byref(v)), "pv_pool_get_carrier")
+        return {n: k for k, n in CARRIERS.items()}[v.value]
 
     def last_launches(self):
         """Kernels launched by the last feed() or feed_device(); 1 after a save() or restore() of any number of slots."""

@@ -233,6 +233,53 @@ int pv_mbatch_set_voice(struct pv_mbatch *b, const int32_t *voice);
 int pv_debug_whisper_phases(const int64_t *counts, int32_t ncalls, float *out, int device);
 
 /* ----------------------------------------------------------------------------------------------
+ * Carrier setting: the channel vocoder (PV_MODE_VOCODER_ROSENBERG / PV_MODE_VOCODER_CHORD) as a run-time, per-slot
+ * setting of the stream pools of mode ROBOTIC.  A slot given carrier ROSENBERG or CHORD is from then on, bit for bit, a
+ * pv_engine of that vocoder mode with the slot's own time ratio and pitch under the pool's arithmetic setting: every
+ * available / retrieve / out_frames value, every sample, pv_pool_plan_feed, pv_pool_get_info (resample == 0, the
+ * vocoder's hop) and the reference's slice dropping.  The slot's derived constants and planner are that engine's own,
+ * built when the setting is made.  It is NOT one more voice: a vocoder stream never resamples (the pitch only moves the
+ * hop) and its output-ring guard is one hop, so it plans differently from the ROBOTIC stream of the same values.
+ * The carrier needs no state: sample n of a voice is table[n mod (period + 1)] of a host-built period table
+ * (pv_plan_carrier), so a slot's carrier follows from its sample position alone.  On the device a feed's launch group
+ * that holds at least one carrier slot launches 2 kernels more (pv_pool_last_launches): the carrier generator, which
+ * writes each such slot's new samples into its row of a carrier ring (positions as in the input ring), and the set's
+ * analysis kernel on those rows, into per-slot carrier planes that the group's synthesis reads.  Robotic, whisper and
+ * carrier slots share the group's other launches.  Ring and planes are allocated by the first feed that has a carrier
+ * slot; a pool that never uses the setting allocates and launches exactly what it always did.
+ * Scope (decided before any device call; a refused call changes nothing, pv_last_error() says why):
+ *   a NULL pool, a slot that is not open, an unknown carrier                     PV_ERR_INVALID_ARG
+ *   a pool whose cfg.mode is not PV_MODE_ROBOTIC                                 PV_ERR_UNSUPPORTED
+ *   a slot that has processed a slice (pv_info.slices > 0)                       PV_ERR_INVALID_ARG
+ *   a slot whose voice is WHISPER (and pv_pool_set_voice(WHISPER) on a slot
+ *   that has a carrier)                                                          PV_ERR_INVALID_ARG
+ *   a pool from pv_pool_create whose configuration resamples (pitch other than
+ *   0): a uniform pool runs one resampling variant for all slots -- use
+ *   pv_pool_create_mixed, which takes the setting for any slot it could open     PV_ERR_UNSUPPORTED
+ *   a vocoder stream that needs more of a per-row buffer than the pool sized     PV_ERR_UNSUPPORTED (names the buffer)
+ * pv_pool_open* starts a slot at PV_CARRIER_NONE; PV_CARRIER_NONE before the first slice returns the slot to ROBOTIC.
+ * Host state only: no wait while device feeds are in flight.  Creating a pool with the vocoder modes stays refused;
+ * the mixed batch has no carrier setting (there a carrier would change a stream's plan and output layout).
+ * Snapshots: a carrier slot's blob has format version 3 and reports cfg.mode PV_MODE_VOCODER_* (pv_pool_blob_info);
+ * its payload is a robotic slot's -- the carrier row is rewritten from the closed form after pv_pool_restore, which
+ * accepts the blob into a ROBOTIC pool only (the uniform-pool rule above applies).  Robotic (version 1) and whisper
+ * (version 2) blobs stay byte for byte what they are.
+ * -------------------------------------------------------------------------------------------- */
+#define PV_CARRIER_NONE 0
+#define PV_CARRIER_ROSENBERG 1
+#define PV_CARRIER_CHORD 2
+int pv_pool_set_carrier(struct pv_pool *p, int32_t slot, int carrier);
+int pv_pool_get_carrier(const struct pv_pool *p, int32_t slot, int *carrier);
+/* host only, no device: `count` carrier samples from absolute sample index `first` (closed form).  Equals
+ * pv_plan_table(PV_TABLE_CARRIER) of the matching vocoder configuration from `first` on, bit for bit (NaN where that
+ * is NaN: sample rates at which a voice's opening phase has zero length, e.g. 16 kHz).  carrier: ROSENBERG or CHORD;
+ * first, count >= 0; out not NULL. */
+int pv_plan_carrier(int32_t sample_rate, int carrier, int64_t first, int64_t count, float *out);
+/* diagnostics: the carrier kernel alone; njobs windows (first[i], count[i]) in ONE launch, concatenated into out */
+int pv_debug_carrier(int32_t sample_rate, int carrier, const int64_t *first, const int32_t *count, int32_t njobs,
+                     float *out, int device);
+
+/* ----------------------------------------------------------------------------------------------
  * Stream pool: up to `capacity` independent LIVE streams of one configuration on one device, each
  * with the semantics of a pv_engine (same cfg, same pv_set_arithmetic setting when the pool is
  * created): fed the same blocks and retrieved between calls, a slot returns bit for bit what that
